@@ -11,9 +11,9 @@ as the reference does) + the device-side sum of the log-likelihoods (+ for N > 1
 pair: RCCL all-reduces carrying the pairs of up to 64 consecutive steps each, all completed inside the timed region).
 
 K timed steps rotate through 12 distinct resident batches (308 MB of int64, more than the 256 MB Infinity Cache); the
-timed region is repeated `--rounds` times (each round: exactly K steps between barrier + synchronize) and the MEDIAN
-round is reported; by default there are at least 5 rounds and enough of them for ~400 steps in all, because the device
-keeps speeding up over its first ~50 ms of work; `--settle` untimed steps precede every timed region -- `timing` lists every round.
+timed region is one round of exactly K steps between barrier + synchronize (`--rounds R`: R such rounds, the MEDIAN round
+is reported); `--settle` untimed steps precede every timed region, because the device keeps speeding up over its first
+~50 ms of work -- `timing` lists every round.  `--dump-outputs DIR` writes what the last timed step returned (.npy).
 
 Prints ONE JSON line on rank 0 (contract in the task description), with
   roofline     -- the dominant kernel (by HIP-event time per launch, measured here): the contraction flops it EXECUTES
@@ -527,11 +527,10 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=0,
-                    help="rounds of --steps timed steps; the median round is reported.  Default: at least 5 and enough for ~400 "
-                         "steps in all -- the device keeps speeding up over the first ~150 steps (0.135 -> 0.123 ms per step, "
-                         "measured round by round), so with the driver's 20 steps per round the median of 5 rounds would still "
-                         "be a warm-up round")
+    ap.add_argument("--rounds", type=int, default=1,
+                    help="rounds of --steps timed steps; the median round is reported.  Default: one, so that --steps is the "
+                         "number of timed steps (the --settle untimed steps in front of it carry the device past its first "
+                         "~150 steps, over which it keeps speeding up)")
     ap.add_argument("--batches", type=int, default=12,
                     help="distinct resident input batches the steps rotate through (12 x 25.7 MB of int64 > the 256 MB "
                          "Infinity Cache, so no step finds its input cached)")
@@ -564,6 +563,10 @@ def main() -> None:
     ap.add_argument("--sync-collectives", action="store_true",
                     help="with the library's communicator: the all-reduce of every step ON the launch stream (the next step starts "
                          "behind it) instead of on the communicator's own stream beside the next step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned -- the [sum of log-likelihoods, rows] "
+                         "pair of log_likelihood_sum, summed over ranks -- to DIR/ll_sum_count.npy (float64); the inputs depend "
+                         "only on the arguments, so two builds can be compared output for output")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-steps", type=int, default=12, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -768,11 +771,12 @@ def main() -> None:
         pair = last[0].cpu()
         return walls, evms, pair
 
-    if args.rounds <= 0:
-        args.rounds = max(5, -(-400 // max(1, args.steps)))
     # the literal protocol first -- W warm-up steps, then K timed steps, nothing else before them: cold clocks
     cold_walls, _, _ = timed_region(circuit, args.steps, args.warmup, 1, settle=0)
     walls, evms, pair = timed_region(circuit, args.steps, args.warmup, max(1, args.rounds))
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ll_sum_count.npy"), pair.numpy().astype(np.float64))
     spread = list(rank_spread)
     elapsed = float(np.median(walls))  # the median round (each round: exactly K steps between barriers)
     step_ms_events = float(np.median(evms))

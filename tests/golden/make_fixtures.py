@@ -748,7 +748,101 @@ def chow_liu():
         print(name, len(plan.layers), "layers; tree", list(map(int, tree)))
 
 
+# The cases of tests/test_reference_live.py, in the same order (the test reads live_<tag><i>).
+LIVE_FWD = [
+    ((1, 5, 4), "quad-graph", "categorical", "cp", 3, 1, True),
+    ((1, 6, 6), "quad-tree-4", "categorical", "tucker", 2, 1, True),
+    ((2, 4, 4), "quad-tree-2", "gaussian", "cp-t", 3, 1, True),
+    ((1, 8, 8), "poon-domingos", "gaussian", "cp", 2, 1, True),
+    ((1, 4, 6), "random-binary-tree", "binomial", "cp", 3, 1, True),
+    ((1, 6, 6), "quad-graph", "categorical", "cp", 3, 4, False),
+    ((1, 7, 5), "poon-domingos", "binomial", "cp-t", 2, 1, True),
+]
+LIVE_ACT = ["softplus", "positive-clamp", "sigmoid"]
+LIVE_SQ = ["categorical", "gaussian"]
+LIVE_PARAM_NODES = [
+    ("TorchHadamardParameter", {}, [(3, 5), (3, 5)]),
+    ("TorchKroneckerParameter", {}, [(2, 3), (4, 5)]),
+    ("TorchOuterProductParameter", {"dim": 1}, [(3, 2), (3, 4)]),
+    ("TorchReduceSumParameter", {"dim": 0}, [(4, 2, 3)]),
+    ("TorchSumParameter", {}, [(4, 3), (4, 3)]),
+    ("TorchReduceProductParameter", {"dim": 1}, [(3, 6)]),
+    ("TorchReduceLSEParameter", {"dim": 0}, [(4, 2, 3)]),
+    ("TorchOuterSumParameter", {"dim": 1}, [(3, 2), (3, 4)]),
+    ("TorchIndexParameter", {"indices": [2, 0, 2, 4], "dim": 0}, [(5, 3)]),
+    ("TorchGaussianProductMean", {}, [(4, 1), (4, 1), (3, 1), (3, 1)]),
+    ("TorchGaussianProductStddev", {}, [(4, 1), (3, 1)]),
+    ("TorchClampParameter", {"vmin": 1e-18}, [(5, 7)]),
+    ("TorchClampParameter", {"vmin": -0.3, "vmax": 0.4}, [(5, 7)]),
+    ("TorchSoftplusParameter", {}, [(5, 7)]),
+]
+
+
+def _save_live(name, plan, tensors, extra):
+    _save(name, plan, {**{"w_" + k: t.detach().numpy() for k, t in tensors.items()}, **extra})
+
+
+def reference_live():
+    """Further circuits compiled by the reference with its own random parameters (torch.manual_seed(0)), for
+    tests/test_reference_live.py: the folded plan, the literal parameters (w_*), inputs and the reference's outputs."""
+    ctx = PipelineContext(backend="torch", semiring="lse-sum", fold=True, optimize=True)
+    for i, (shape, rg, inp, sp, k, ncls, mix) in enumerate(LIVE_FWD):
+        torch.manual_seed(0)
+        sc = data_modalities.image_data(shape, rg, input_layer=inp, num_input_units=k, sum_product_layer=sp, num_sum_units=k,
+                                        num_classes=ncls, use_mixing_weights=mix)
+        cc = ctx.compile(sc)
+        plan, tensors = plan_from_torch_circuit(cc)
+        d = int(np.prod(shape))
+        g = torch.Generator().manual_seed(1)
+        x = torch.randn((6, d), generator=g) if inp == "gaussian" else torch.randint(0, 256, (6, d), generator=g)
+        _save_live(f"live_fwd{i}", plan, tensors, {"x": x.numpy(), "y": cc(x).numpy()})
+    for i, activation in enumerate(LIVE_ACT):
+        torch.manual_seed(0)
+        sc = data_modalities.image_data((1, 4, 4), "quad-tree-2", input_layer="categorical", num_input_units=3, sum_product_layer="cp",
+                                        num_sum_units=3, sum_weight_param=Parameterization(activation=activation, initialization="normal"))
+        cc = ctx.compile(sc)
+        plan, tensors = plan_from_torch_circuit(cc)
+        x = torch.randint(0, 256, (6, 16), generator=torch.Generator().manual_seed(1))
+        _save_live(f"live_act{i}", plan, tensors, {"x": x.numpy(), "y": cc(x).numpy()})
+    for i, inp in enumerate(LIVE_SQ):
+        torch.manual_seed(0)
+        sc = data_modalities.image_data((1, 4, 4), "quad-tree-2", input_layer=inp, num_input_units=3, sum_product_layer="cp-t",
+                                        num_sum_units=3)
+        cx = PipelineContext(backend="torch", semiring="lse-sum", fold=True, optimize=True)
+        cc = cx.compile(sc)
+        zc = cx.compile(SF.integrate(SF.multiply(sc, sc)))
+        plan, tensors = plan_from_torch_circuit(cc, table=tensor_table())
+        _save_live(f"live_sq{i}", plan, tensors, {"z": zc().numpy()})
+    torch.manual_seed(0)
+    par = Parameterization(activation="none", initialization="normal")
+    sc = data_modalities.image_data((1, 4, 4), "quad-tree-2", input_layer="embedding", num_input_units=3, sum_product_layer="cp-t",
+                                    num_sum_units=3, input_params={"weight": par}, sum_weight_param=par)
+    cx = PipelineContext(backend="torch", semiring="complex-lse-sum", fold=True, optimize=True)
+    cc = cx.compile(sc)
+    zc = cx.compile(SF.integrate(SF.multiply(sc, SF.conjugate(sc))))
+    plan, tensors = plan_from_torch_circuit(cc, table=tensor_table())
+    x = torch.randint(0, 256, (5, 16), generator=torch.Generator().manual_seed(2))
+    _save_live("live_complex_sq", plan, tensors, {"x": x.numpy(), "y": cc(x).numpy(), "z": zc().numpy()})
+
+    from cirkit.backend.torch.parameters import nodes as ref_nodes
+
+    out = {}
+    for i, (cls, kwargs, shapes) in enumerate(LIVE_PARAM_NODES):
+        F = 3
+        g = torch.Generator().manual_seed(5)
+        xs = [torch.randn((F, *s), generator=g) for s in shapes]
+        if "Gaussian" in cls:
+            xs = [x.abs() + 0.3 for x in xs]
+        mod = getattr(ref_nodes, cls)(*shapes, num_folds=F, **kwargs)
+        for j, x in enumerate(xs):
+            out[f"c{i}_x{j}"] = x.numpy()
+        out[f"c{i}_want"] = mod(*xs).numpy()
+        out[f"c{i}_shape"] = np.asarray(mod.shape, dtype=np.int64)
+    np.savez_compressed(os.path.join(HERE, "live_param_nodes.npz"), **out)
+    print("live_param_nodes", len(LIVE_PARAM_NODES), "cases")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["cfg1", "cfg2", "cfg2_cpt", "cfg4", "cfg5", "kats", "tucker", "plans_only", "grads", "grads_k64", "grads_tucker", "grads_param_nodes", "grads_sos", "grads_sq_categorical", "grads_sq_gaussian", "marginals", "templates_extra"]
+    which = sys.argv[1:] or ["cfg1", "cfg2", "cfg2_cpt", "cfg4", "cfg5", "kats", "tucker", "plans_only", "grads", "grads_k64", "grads_tucker", "grads_param_nodes", "grads_sos", "grads_sq_categorical", "grads_sq_gaussian", "marginals", "templates_extra", "reference_live"]
     for w in which:
         globals()[w]()

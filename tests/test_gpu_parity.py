@@ -1224,10 +1224,13 @@ def test_template_circuits_on_the_mfma_kernels(hip_device, rg, shape, sp, K, inp
     from cirkit_amd.initializers import init_plan_tensors
     from cirkit_amd.templates import image_data
 
-    if not use_mixing and rg in ("quad-tree-2", "quad-tree-4", "random-binary-tree"):
-        pytest.skip("no regions with several partitionings")
     plan = image_data(shape, rg, input_layer=inp, num_input_units=K, sum_product_layer=sp, num_sum_units=K,
                       use_mixing_weights=use_mixing)
+    if not use_mixing and rg in ("quad-tree-2", "quad-tree-4", "random-binary-tree"):
+        # no region with several partitionings: the flag must change nothing -- the plan with mixing weights, run as well
+        (da, aa), (db, ab) = plan.to_json(), image_data(shape, rg, input_layer=inp, num_input_units=K, sum_product_layer=sp,
+                                                        num_sum_units=K, use_mixing_weights=True).to_json()
+        assert da == db and set(aa) == set(ab) and all(np.array_equal(aa[k], ab[k]) for k in aa)
     tensors = init_plan_tensors(plan, seed=5)
     x = _random_batch(plan, B, seed=17)
     if inp == "categorical":
