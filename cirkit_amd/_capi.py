@@ -10,7 +10,7 @@ from typing import Any
 # CIRKIT_HIP_LIB: a lab build of the same library (scripts/lab_build.sh, scripts/defect_injection.sh); never a different backend
 _LIB_PATH = os.environ.get("CIRKIT_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libcirkit_hip.so")
 
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 CK_SUM_CAT = 0
 CK_SUM_PROD = 1
@@ -175,6 +175,12 @@ MIX_JOB_DTYPE = [("w", "<u8"), ("out", "<u8"), ("gx", "<u8"), ("dtheta", "<u8"),
                  ("w_out", "<u8"), ("part", "<u8"), ("ticket", "<u8"), ("in_off", "<i4"), ("H", "<i4"), ("g_off", "<i4"),
                  ("n_g", "<i4"), ("row0", "<i4"), ("row1", "<i4"), ("split", "<i4"), ("n_split", "<i4"), ("mode", "<i4"),
                  ("S", "<i4"), ("reserved1", "<i8")]
+# numpy mirror of ck_sample_layer (88 bytes): the walk's DEVICE descriptor table
+SAMPLE_LAYER_DTYPE = [("type", "<i4"), ("F", "<i4"), ("H", "<i4"), ("Ki", "<i4"), ("Ko", "<i4"), ("M", "<i4"), ("fold_off", "<i4"),
+                      ("reserved", "<i4"), ("child", "<u8"), ("cdf", "<u8"), ("cmap", "<u8"), ("choices", "<u8"), ("scope", "<u8"),
+                      ("mean", "<u8"), ("stddev", "<u8")]
+CK_SAMPLE_CATEGORICAL, CK_SAMPLE_GAUSSIAN, CK_SAMPLE_SUM, CK_SAMPLE_CPT, CK_SAMPLE_TUCKER, CK_SAMPLE_HADAMARD, CK_SAMPLE_KRONECKER = range(7)
+CK_SAMPLE_MAX_LDS = 65536
 NSUM_JOB_DTYPE = [("out", "<u8"), ("in_off", "<i4"), ("n_in", "<i4")]
 CAT_JOB_DTYPE = [("x", "<u8"), ("theta", "<u8"), ("table", "<u8"), ("dtheta", "<u8"), ("theta_out", "<u8"), ("m1", "<u8"), ("m2", "<u8"),
                  ("table_out", "<u8"), ("g_off", "<i4"), ("n_g", "<i4"), ("mode", "<i4"), ("reserved", "<i4")]
@@ -302,6 +308,8 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_jobs_mix_bwd": [_p, _i, _p, _i, _l, _p, _p],
     "ck_jobs_nsum": [_p, _i, _p, _l, _p],
     "ck_jobs_root": [C.POINTER(RootLaunch), _p],
+    "ck_sample_cdf": [_p, _l, _l, _l, _i, _p, _l, _i, _i, _p, _p, _p],
+    "ck_sample_walk": [_p, _i, _i, _i, _i, _i, _l, _i, C.c_uint64, _p, _i, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],
     "ck_jobs_gauss_bwd": [_p, _i, _p, _i, _p, _p],
     "ck_opt_step_range": [_p, _p, _p, _p, _p, _l, _p, _p],

@@ -959,6 +959,26 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             views = [v if v is None else v[..., : s.num_output_units] for v, s in zip(views, self.user_plan.layers)]
         return views
 
+    def sample(self, num_samples: int, *, seed: int | None = None, return_choices: bool = False):
+        """Exact samples of ``p(x) = c(x) / Z`` from output fold 0, unit 0 (the reference's ``SamplingQuery``,
+        queries.py:211-275, samples ``[:, 0, 0]`` too); ``(N, D)`` on this device, in the variable order of the user's plan:
+        int64 when every input layer is discrete, fp32 when any is Gaussian.
+
+        Where this differs from the reference: the reference raises on a circuit whose sum weights are not normalised;
+        this sampler weights every draw by the partition functions of the inputs and so samples any monotonic circuit
+        exactly (on a normalised one the distribution is the reference's).  Tucker layers, which have no ``sample()`` in
+        the reference, are sampled too.
+
+        `seed`: an int gives bit-identical samples for the same circuit, parameter values and `num_samples`; None draws
+        the seed from torch's default CPU generator (``torch.manual_seed`` reproduces it).  `return_choices`: also return
+        one int32 ``(F, N)`` tensor per sum / mixing / CP-T / Tucker layer, in plan order, holding the input entry each
+        fold chose in the user's unit numbering (``h * Ki + ki`` sum, ``h`` mixing, ``ki`` CP-T, ``a * Ki + b`` Tucker) or
+        -1 where the fold is not on the sample's induced tree.  Parameters are read from the `TensorStore` at call time;
+        the conditional tables are rebuilt when its values changed (cirkit_amd/sampling.py)."""
+        from .sampling import sample
+
+        return sample(self, num_samples, seed=seed, return_choices=return_choices)
+
     def log_likelihood_sum(self, x: torch.Tensor, out: torch.Tensor | None = None, *, reduce: bool = False) -> torch.Tensor:
         """Device tensor ``[sum_b log p(x_b), B]`` in fp64 -- the two numbers the data-parallel
         all-reduce exchanges (SURVEY.md section 8 e).  Requires a single scalar output.

@@ -35,6 +35,11 @@ class TensorStore:
         self.version = 0  # bumps when a tensor OBJECT is replaced (recorded pointers go stale)
         self.data_version = 0  # bumps on every value change (derived-parameter caches go stale)
         self._volatile = 0  # `state()` calls that could not read a version counter (inference tensors)
+        # in-place writes through raw pointers by kernels that keep their own circuit's derived parameters current (the fused
+        # training step's optimizer epilogues, cirkit_amd/training.py): invisible to `state()` on purpose -- a `touch()`
+        # would make that circuit re-evaluate what the epilogues already wrote -- so derived caches of OTHER consumers
+        # (the sampler's CDF tables, cirkit_amd/sampling.py) compare this count beside `state()`
+        self.raw_writes = 0
         # set by a HipCircuit that padded its unit counts (cirkit_amd/padding.py): values arrive and leave in
         # the shapes of the user's plan
         self._pad = None

@@ -840,6 +840,7 @@ class HipTrainer:
                 B = int(x.shape[0])
                 ll = self._forward(x)
                 self._backward(B, float(global_batch or B), None, with_opt=True)
+                c.store.raw_writes += 1
             return ll
         ll = self.loss_and_grads(x, global_batch=global_batch)
         validate = c.validate_inputs and c._int_input

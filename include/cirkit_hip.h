@@ -1096,6 +1096,47 @@ int ck_comm_wait(ck_comm* comm, void* stream);
 int ck_comm_info(const ck_comm* comm, int32_t out[3], char* origin, int origin_len);
 int ck_comm_destroy(ck_comm* comm);
 
+/* ---- sampling ------------------------------------------------------------------------------------
+ * Exact ancestral sampling of p(x) = c(x) / Z from a monotonic lse-sum circuit, top down.  Replaces the reference's
+ * SamplingQuery (cirkit/backend/torch/queries.py:211-275) and the layers' sample() methods it calls bottom up
+ * (layers/input.py: TorchCategoricalLayer / TorchBinomialLayer / TorchGaussianLayer.sample, layers/inner.py:178-197
+ * TorchKroneckerLayer.sample, :275-299 TorchSumLayer.sample, layers/optimized.py:180-203 TorchCPTLayer.sample).  Unlike the
+ * reference, a unit draws its input in proportion to weight x partition function of that input, so unnormalised circuits
+ * are sampled exactly; Tucker layers (no sample() in the reference) draw a pair of input units.  Random numbers: Philox4x32-10,
+ * counter layout in cirkit_amd/csrc/ck_philox.h. */
+#define CK_SAMPLE_CATEGORICAL 0 /* Categorical / Binomial: a value drawn from the unit's CDF row over the categories        */
+#define CK_SAMPLE_GAUSSIAN 1    /* mean + stddev * z                                                                       */
+#define CK_SAMPLE_SUM 2         /* sum and mixing layers: i over H * Ki, input i / Ki, unit i % Ki                         */
+#define CK_SAMPLE_CPT 3         /* ki over Ki: unit ki of every input                                                      */
+#define CK_SAMPLE_TUCKER 4      /* (a, b) over Ki * Ki: unit a of input 0, unit b of input 1                               */
+#define CK_SAMPLE_HADAMARD 5    /* no draw: unit k of every input                                                          */
+#define CK_SAMPLE_KRONECKER 6   /* no draw: unit k in base Ki, input 0 most significant (inner.py:178-197)                 */
+#define CK_SAMPLE_MAX_LDS 65536 /* bytes of the walk's per-workgroup table: total folds x samples per workgroup x 2        */
+typedef struct ck_sample_layer {
+  int32_t type;            /* CK_SAMPLE_*                                                                                 */
+  int32_t F, H, Ki, Ko, M; /* folds, arity, units in / out, length of a CDF row                                           */
+  int32_t fold_off;        /* global fold id of fold 0 (folds of every layer concatenated in plan order)                  */
+  int32_t reserved;
+  const int32_t* child;    /* (F, H) global fold ids of the inputs (inner layers)                                         */
+  const float* cdf;        /* (F, Ko, M) cumulative unnormalised conditional masses (ck_sample_cdf)                       */
+  const int32_t* cmap;     /* (M) the choice reported for entry i (the user's unit numbering of a padded plan), or NULL   */
+  int32_t* choices;        /* (F, N) chosen entry per sample, -1 off the sample's induced tree; NULL: not recorded        */
+  const int64_t* scope;    /* (F) variable of each fold (input layers)                                                    */
+  const float* mean;       /* (F, Ko) Gaussian layers                                                                     */
+  const float* stddev;     /* (F, Ko)                                                                                     */
+} ck_sample_layer;
+/* cdf (F, R, M) row (f, k): running sums of w[f, k, m] * exp(lz[f, m]) (shifted by the row maximum), w read at
+ * w + f w_sf + k w_sk + m w_sm (w_log != 0: w holds log-weights); lz (F, M) child log partition functions, or NULL.  A zero
+ * weight adds exactly 0.  *flag |= 1 for a negative weight, |= 2 for a NaN weight or a NaN / +inf (log-)term under a positive
+ * weight (the host reads the flag once per parameter state; nothing faults). */
+int ck_sample_cdf(const float* w, int64_t w_sf, int64_t w_sk, int64_t w_sm, int w_log, const float* lz, int64_t F, int R,
+                  int M, float* cdf, int32_t* flag, void* stream);
+/* One launch: N samples of unit root_unit of global fold root_fold, S samples per workgroup (total_folds * S * 2 bytes of
+ * LDS <= CK_SAMPLE_MAX_LDS), layers (a DEVICE array of n_layers descriptors in plan order) walked last to first.  x (N, D):
+ * int64 values (x_float = 0) or fp32 (x_float != 0, required with a Gaussian layer); choices as the descriptors say. */
+int ck_sample_walk(const ck_sample_layer* layers, int n_layers, int root_fold, int root_unit, int total_folds, int S,
+                   int64_t N, int D, uint64_t seed, void* x, int x_float, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
