@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Any
+from typing import Any, Callable
 
 # CIRKIT_HIP_LIB: a lab build of the same library (scripts/lab_build.sh, scripts/defect_injection.sh); never a different backend
 _LIB_PATH = os.environ.get("CIRKIT_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libcirkit_hip.so")
@@ -379,3 +379,40 @@ def call(name: str, *args: Any) -> None:
     """Call an entry point and raise on a non-zero status.  ValueError on CK_ERR_INVALID mirrors the
     reference's shape errors (e.g. TorchSumLayer.__init__, layers/inner.py:237-242)."""
     check(getattr(load(), name)(*args), name)
+
+
+class Program:
+    """A recorded launch list (`ck_program`): `record` captures the calls of this library a callable issues, `launch` replays
+    them.  Its owner closes it where the pointers it holds go stale; `__del__` is only a backstop at interpreter teardown."""
+
+    def __init__(self) -> None:
+        self._h = C.c_void_p()
+        self.num_ops = 0  # launches in the list (fixed once recorded)
+
+    @classmethod
+    def record(cls, body: Callable[[], Any]) -> Program:
+        prog = cls()
+        call("ck_program_begin", C.byref(prog._h))
+        try:
+            body()
+        finally:
+            call("ck_program_end", prog._h)
+        prog.num_ops = int(load().ck_program_num_ops(prog._h))
+        return prog
+
+    def set_input(self, cell: int, ptr: int | None) -> None:
+        call("ck_program_set_input", self._h, cell, ptr)
+
+    def launch(self, stream: int, as_graph: bool = False) -> None:
+        call("ck_program_launch", self._h, 1 if as_graph else 0, stream)
+
+    def close(self) -> None:
+        if self._h.value is not None:
+            load().ck_program_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self) -> None:  # pragma: no cover - interpreter teardown order
+        try:
+            self.close()
+        except Exception:
+            pass

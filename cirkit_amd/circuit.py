@@ -16,7 +16,6 @@ with ~10 ATen launches per layer.
 
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Mapping
 
@@ -48,8 +47,8 @@ class _Binding:
         self.xt_i: torch.Tensor | None = None  # (D, B) int32 staging copy
         self.leftover: dict[int, tuple[torch.Tensor, torch.Tensor]] = {}
         self.cp_tabs: dict[int, torch.Tensor] = {}  # device-address tables of the weight matrices (keep alive)
-        self.program = None  # ck_program*
-        self.program_ll = None  # the same followed by ck_ll_sum
+        self.program: capi.Program | None = None
+        self.program_ll: capi.Program | None = None  # the same followed by ck_ll_sum
         self.store_version = -1
         self.ll: torch.Tensor | None = None
         self.ll_cell = 0  # program input cell of program_ll that redirects the [sum, count] pair (0: none)
@@ -59,10 +58,10 @@ class _Binding:
         self.x_last: torch.Tensor | None = None  # ... the batch of the last call (kept alive; read by eager launches)
 
     def destroy(self) -> None:
-        for name in ("program", "program_ll"):
-            if getattr(self, name) is not None:
-                capi.load().ck_program_destroy(getattr(self, name))
-                setattr(self, name, None)
+        for prog in (self.program, self.program_ll):
+            if prog is not None:
+                prog.close()
+        self.program = self.program_ll = None
 
 
 class HipCircuit(_LaunchMixin, _ProfilingMixin):
@@ -449,15 +448,6 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
     def __call__(self, x: torch.Tensor | None = None, *, integrate_vars=None) -> torch.Tensor:
         return self.forward(x, integrate_vars=integrate_vars)
 
-    def __del__(self) -> None:  # pragma: no cover - interpreter teardown order
-        try:
-            for b in self._bindings.values():
-                b.destroy()
-            if self._pprog is not None:
-                capi.load().ck_program_destroy(self._pprog)
-        except Exception:
-            pass
-
     # -- binding ---------------------------------------------------------------------------------
     def _layer_batch(self, l: HipLayer, B: int) -> int:
         return B
@@ -528,8 +518,8 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         bd.program = self._record(bd, with_ll=False)  # the launch list, recorded once
         # a hipGraph keeps the pointers of its capture: long launch lists read the staged copy of the batch.  The list of
         # `log_likelihood_sum` (recorded on first use, with this binding's `direct`) can be one launch longer: decide on that
-        if bd.direct and self.use_graph and capi.load().ck_program_num_ops(bd.program) + 1 > self.graph_min_launches:
-            capi.load().ck_program_destroy(bd.program)
+        if bd.direct and self.use_graph and bd.program.num_ops + 1 > self.graph_min_launches:
+            bd.program.close()
             bd.direct = False
             bd.program = self._record(bd, with_ll=False)
         self._bindings[B] = bd
@@ -571,24 +561,23 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
     def _record(self, bd: _Binding, *, with_ll: bool):
         """Record one forward for this binding; `with_ll` appends the device-side log-likelihood sum
         so that `log_likelihood_sum` replays ONE graph."""
-        prog = C.c_void_p()
-        capi.call("ck_program_begin", C.byref(prog))
-        self._recording = True
-        try:
-            if not self.cache_params:
-                self._enqueue_params(0, at_end=bd.params_at_end)
-            self._enqueue_layers(bd, 0, with_ll=with_ll)
-            if self.validate_inputs and self._int_input and not bd.direct and not self._poison_in_tail():
-                for p, f in self._out_pairs:  # (complex outputs: both halves of every element)
-                    v = bd.views[int(p)][int(f)]
-                    capi.call("ck_poison_outputs", v.data_ptr(), v.numel() * (2 if self._complex else 1), self._bad_input.data_ptr(), 0)
-            if with_ll and not self._tail_fuses_ll():
-                p, f = int(self._out_pairs[0, 0]), int(self._out_pairs[0, 1])
-                capi.call("ck_ll_sum", bd.views[p][f].data_ptr(), bd.B, 1, bd.ll.data_ptr(), 0)
-        finally:
-            self._recording = False
-            capi.call("ck_program_end", prog)
-        return prog
+        def body() -> None:
+            self._recording = True
+            try:
+                if not self.cache_params:
+                    self._enqueue_params(0, at_end=bd.params_at_end)
+                self._enqueue_layers(bd, 0, with_ll=with_ll)
+                if self.validate_inputs and self._int_input and not bd.direct and not self._poison_in_tail():
+                    for p, f in self._out_pairs:  # (complex outputs: both halves of every element)
+                        v = bd.views[int(p)][int(f)]
+                        capi.call("ck_poison_outputs", v.data_ptr(), v.numel() * (2 if self._complex else 1), self._bad_input.data_ptr(), 0)
+                if with_ll and not self._tail_fuses_ll():
+                    p, f = int(self._out_pairs[0, 0]), int(self._out_pairs[0, 1])
+                    capi.call("ck_ll_sum", bd.views[p][f].data_ptr(), bd.B, 1, bd.ll.data_ptr(), 0)
+            finally:
+                self._recording = False
+
+        return capi.Program.record(body)
 
     def _raw_batch_args(self, bd: _Binding) -> tuple[int | None, int]:
         """(x_rows, x_input) of a launch that reads the caller's batch: program input cell 0 while recording, the batch of
@@ -605,16 +594,10 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         if self._pprog is not None and self._pprog_version == self.store.version:
             return self._pprog
         if self._pprog is not None:
-            capi.load().ck_program_destroy(self._pprog)
-            self._pprog = None
-        prog = C.c_void_p()
-        capi.call("ck_program_begin", C.byref(prog))
-        try:
-            self._enqueue_params(0)
-        finally:
-            capi.call("ck_program_end", prog)
-        self._pprog, self._pprog_version, self._pprog_data_version = prog, self.store.version, None
-        return prog
+            self._pprog.close()
+        self._pprog = capi.Program.record(lambda: self._enqueue_params(0))
+        self._pprog_version, self._pprog_data_version = self.store.version, None
+        return self._pprog
 
     def invalidate_parameters(self) -> None:
         """Tell a `cache_params` circuit that parameter values were modified in place behind the
@@ -877,12 +860,11 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             if with_ll and bd.program_ll is None:
                 bd.program_ll = self._record(bd, with_ll=True)
             prog = bd.program_ll if with_ll else bd.program
-            lib = capi.load()
-            as_graph = bool(self.use_graph) and lib.ck_program_num_ops(prog) > self.graph_min_launches
+            as_graph = bool(self.use_graph) and prog.num_ops > self.graph_min_launches
             state = self.store.state() if (self.cache_params or bd.params_at_end) else None
             refresh = self.cache_params and self._pprog_data_version != state
             pprog = self._param_program() if refresh else None
-            p_graph = refresh and bool(self.use_graph) and lib.ck_program_num_ops(pprog) > self.graph_min_launches
+            p_graph = refresh and bool(self.use_graph) and pprog.num_ops > self.graph_min_launches
             if (as_graph or p_graph) and cur.cuda_stream == 0:  # a capture cannot run on the legacy default stream
                 if self._side is None:
                     self._side = torch.cuda.Stream(self.device)
@@ -895,22 +877,22 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
                 if as_graph:
                     raise RuntimeError("a binding that reads the raw batch cannot be replayed as a hipGraph")
                 bd.x_last = xi
-                capi.call("ck_program_set_input", prog, 0, xi.data_ptr())
+                prog.set_input(0, xi.data_ptr())
             if with_ll and bd.ll_cell:  # (an eager replay reads the cell; NULL = the binding's own pair)
                 direct_ll = ll_out is not None and not as_graph
-                capi.call("ck_program_set_input", prog, bd.ll_cell, ll_out.data_ptr() if direct_ll else None)
+                prog.set_input(bd.ll_cell, ll_out.data_ptr() if direct_ll else None)
                 if direct_ll:
                     ll_out = None
             if refresh:
                 self._pprog_data_version = state
-                capi.call("ck_program_launch", pprog, 1 if p_graph else 0, stream)
+                pprog.launch(stream, p_graph)
             if bd.params_at_end:
                 # the launch that ends this forward re-evaluates the parameters for the next one; a store that has changed
                 # since the derived parameters in memory were evaluated gets them evaluated now, on their own
                 if self._params_valid_version != state:
                     self._launch_param_batch(stream)
                 self._params_valid_version = state
-            capi.call("ck_program_launch", prog, 1 if as_graph else 0, stream)
+            prog.launch(stream, as_graph)
             if run is not cur:
                 cur.wait_stream(run)
             if ll_out is not None:  # no launch of this binding takes the destination: one 16-byte copy
@@ -924,7 +906,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         if with_ll and bd.program_ll is None:
             bd.program_ll = self._record(bd, with_ll=True)
         prog = bd.program_ll if with_ll else bd.program
-        return bool(self.use_graph) and capi.load().ck_program_num_ops(prog) > self.graph_min_launches
+        return bool(self.use_graph) and prog.num_ops > self.graph_min_launches
 
     def forward(self, x: torch.Tensor | None = None, *, integrate_vars=None) -> torch.Tensor:
         """Returns ``(B, O, K)`` like ``TorchCircuit.forward`` (``(O, K)`` for an empty-scope circuit).
@@ -1018,7 +1000,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         return sum(l.num_folds * B * l.num_output_units for l in self.layers) * esz
 
     def num_launches(self, B: int) -> int:
-        return int(capi.load().ck_program_num_ops(self._bind(B).program))
+        return self._bind(B).program.num_ops
 
     def num_launches_ll(self, B: int) -> int:
         """Launches of one `log_likelihood_sum` step: the recorded program plus the staging of the batch in front of it
@@ -1027,7 +1009,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         if bd.program_ll is None:
             bd.program_ll = self._record(bd, with_ll=True)
         staging = 0 if bd.direct else int(self._float_input) + int(self._int_input)
-        return int(capi.load().ck_program_num_ops(bd.program_ll)) + (staging if self.plan.num_variables else 0)
+        return bd.program_ll.num_ops + (staging if self.plan.num_variables else 0)
 
     def reads_batch_directly(self, B: int) -> bool:
         return self._bind(B).direct

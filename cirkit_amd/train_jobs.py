@@ -63,8 +63,6 @@ class JobStep:
         self.tr = trainer
         self.c = trainer.circuit
         self._bound: dict[int, dict] = {}
-        self._opt: torch.Tensor | None = None
-        self._opt_key = None
         self._own_state = None  # the store's state after this object's last in-place update (fused optimizer)
         self.why = self._analyse()
 
@@ -403,30 +401,9 @@ class JobStep:
         the optimizer on their tensors' ranges and re-evaluates their parameter graphs at its start)."""
         return [i for i in self.inputs if i not in self.gauss and i not in self.cat]
 
-    def _opt_state(self) -> torch.Tensor:
-        """The DEVICE ck_opt_state of the fused optimizer (created on first use; its constants follow the trainer's)."""
-        tr = self.tr
-        key = (float(tr.lr), tuple(float(b) for b in tr.betas), float(tr.eps), tr.optimizer)
-        if self._opt is None:
-            o = capi.OptState()
-            o.lr, o.b1, o.b2, o.eps, o.bc1, o.bc2 = tr.lr, tr.betas[0], tr.betas[1], tr.eps, 1.0, 1.0
-            o.step, o.skipped, o.skip_now, o.kind = 0, 0, 0, 1 if tr.optimizer == "adam" else 0
-            o.b1d, o.b2d = float(tr.betas[0]), float(tr.betas[1])  # the bias corrections are formed in double (torch.optim.Adam does)
-            self._opt = torch.frombuffer(bytearray(bytes(o)), dtype=torch.uint8).to(self.c.device)
-            self._opt_key = key
-        elif key != self._opt_key:  # (the learning rate was changed between steps: the first 16 bytes)
-            head = torch.tensor([tr.lr, tr.betas[0], tr.betas[1], tr.eps], dtype=torch.float32).view(torch.uint8)
-            self._opt[:16].copy_(head.to(self.c.device))
-            self._opt[40:56].copy_(torch.tensor([tr.betas[0], tr.betas[1]], dtype=torch.float64).view(torch.uint8).to(self.c.device))
-            self._opt_key = key
-        return self._opt
-
     def opt_counters(self) -> tuple[int, int]:
-        """(steps taken, steps dropped) of the fused optimizer (a device read)."""
-        if self._opt is None:
-            return 0, 0
-        v = self._opt[24:32].cpu().view(torch.int32)
-        return int(v[0]), int(v[1])
+        """(steps taken, steps dropped) of the trainer's device clock, which the job epilogues advance (a device read)."""
+        return self.tr.opt_counters()
 
     def bind(self, B: int) -> dict:
         tr, c = self.tr, self.c
@@ -436,7 +413,7 @@ class JobStep:
             return st
         if st is not None:
             for pr in st["prog"].values():
-                capi.load().ck_program_destroy(pr)
+                pr.close()
         dev = c.device
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
@@ -460,19 +437,15 @@ class JobStep:
             pool.extend(addr(x) for x in blocks)
             return off, len(blocks)
 
-        grads, flat_p = tr.grads, tr._flat_param
+        def fold_ptr(t: torch.Tensor | None, fold: int) -> int:
+            return 0 if t is None else t.data_ptr() + fold * (t.numel() // t.shape[0]) * 4
 
         def grad_ptr(theta) -> int:
-            t = grads[theta[0]]
-            return t.data_ptr() + theta[1] * (t.numel() // t.shape[0]) * 4
+            return fold_ptr(tr.grads[theta[0]], theta[1])
 
         def theta_ptrs(theta) -> tuple[int, int, int]:
-            t = c.store[theta[0]]
-            p = t.data_ptr() + theta[1] * (t.numel() // t.shape[0]) * 4
-            off = p - flat_p.data_ptr()
-            m1 = tr._m1.data_ptr() + off if tr._m1 is not None else 0
-            m2 = tr._m2.data_ptr() + off if tr._m2 is not None else 0
-            return p, m1, m2
+            m1, m2 = tr._moments.get(theta[0], (None, None))
+            return fold_ptr(c.store[theta[0]], theta[1]), fold_ptr(m1, theta[1]), fold_ptr(m2, theta[1])
 
         tiles = (B + 31) // 32
         keep: list[torch.Tensor] = [extra]
@@ -748,7 +721,7 @@ class JobStep:
         seed = torch.zeros(B, dtype=torch.float32, device=dev)
         pool_d = torch.from_numpy(np.asarray(pool, dtype=np.uint64).view(np.int64)).to(dev)
         keep.extend([rin_d, ptrs_d, rpart, rtick, seed, pool_d])
-        opt = self._opt_state()
+        opt = tr._opt_state()
 
         def root_args(mode: int):
             ra = capi.RootLaunch()
@@ -766,9 +739,9 @@ class JobStep:
                 ra.theta_c, ra.m1_c, ra.m2_c, ra.c_out = th, m1, m2, lm._w.data_ptr()
             validate = c.validate_inputs and c._int_input
             # mode 1: the circuit's own flag (latched after the step by the trainer); mode 2: `ck_opt_tick` has moved it into
-            # the optimizer state's skip_now (byte 32) by the time the root launch runs
-            ra.opt = opt.data_ptr() if mode == 2 else None
-            ra.bad_flag = (opt.data_ptr() + 32) if mode == 2 else (c._bad_input.data_ptr() if validate else None)
+            # the optimizer state's skip_now by the time the root launch runs
+            ra.opt = opt.ptr if mode == 2 else None
+            ra.bad_flag = opt.skip_now_ptr if mode == 2 else (c._bad_input.data_ptr() if validate else None)
             ra.seed_const, ra.R, ra.B, ra.mode, ra.n_wg, ra.S = 0.0, R, B, mode, n_wg, S_root
             return ra
 
@@ -778,7 +751,7 @@ class JobStep:
         while len(self._bound) >= 4:
             old = self._bound.pop(next(iter(self._bound)))
             for pr in old["prog"].values():
-                capi.load().ck_program_destroy(pr)
+                pr.close()
         self._bound[B] = st
         return st
 
@@ -787,13 +760,7 @@ class JobStep:
         prog = st["prog"].get(mode)
         if prog is None:
             bd = self.c._bind(B)
-            prog = C.c_void_p()
-            capi.call("ck_program_begin", C.byref(prog))
-            try:
-                self._enqueue(bd, st, B, mode, 0)
-            finally:
-                capi.call("ck_program_end", prog)
-            st["prog"][mode] = prog
+            prog = st["prog"][mode] = capi.Program.record(lambda: self._enqueue(bd, st, B, mode, 0))
         return prog
 
     def _enqueue(self, bd, st: dict, B: int, mode: int, stream: int) -> None:
@@ -803,7 +770,7 @@ class JobStep:
         tr, c = self.tr, self.c
         pool = st["pool"].data_ptr()
         blk = B * K
-        opt = self._opt_state().data_ptr() if mode == 2 else None
+        opt = tr._opt_state().ptr if mode == 2 else None
         validate = c.validate_inputs and c._int_input
         if mode == 2:
             capi.call("ck_opt_tick", opt, c._bad_input.data_ptr() if validate else None, tr._bad_seen.data_ptr() if validate else None, stream)
@@ -849,9 +816,9 @@ class JobStep:
             for i in self._uncovered():
                 for name in self._tensors_of(i):
                     t, g = c.store[name], tr.grads[name]
-                    off = t.data_ptr() - tr._flat_param.data_ptr()
-                    capi.call("ck_opt_step_range", t.data_ptr(), g.data_ptr(), None, (tr._m1.data_ptr() + off) if tr._m1 is not None else None,
-                              (tr._m2.data_ptr() + off) if tr._m2 is not None else None, t.numel(), opt, stream)
+                    m1, m2 = tr._moments.get(name, (None, None))
+                    capi.call("ck_opt_step_range", t.data_ptr(), g.data_ptr(), None, None if m1 is None else m1.data_ptr(),
+                              None if m2 is None else m2.data_ptr(), t.numel(), opt, stream)
 
     def _tensors_of(self, i: int) -> list[str]:
         l = self.c.layers[i]
@@ -901,7 +868,7 @@ class JobStep:
         with torch.cuda.device(c.device):
             stream = torch.cuda.current_stream(c.device).cuda_stream
             if mode == 2:
-                self._opt_state()
+                self.tr._opt_state()
                 if self._own_state != c.store.state():
                     # somebody else changed a parameter since this object last derived them: all graphs, once
                     c._enqueue_params(stream)
@@ -911,7 +878,7 @@ class JobStep:
                 st["seed_value"] = -1.0 / gB
             xf, xi = c._prepare_input(x)
             c._stage_input(bd, xf, xi, stream)
-            capi.call("ck_program_launch", prog, 0, stream)
+            prog.launch(stream)
             if mode == 2:
                 c.store.touch()
                 self._own_state = c.store.state()
@@ -930,4 +897,4 @@ class JobStep:
 
     def num_launches(self, B: int, mode: int = 2) -> int:
         st = self.bind(B)
-        return int(capi.load().ck_program_num_ops(self._program(st, B, mode)))
+        return self._program(st, B, mode).num_ops

@@ -32,16 +32,17 @@ from typing import Mapping
 import numpy as np
 import torch
 
-from .distributed import all_reduce_sum as _all_reduce_sum, default_comm as _default_comm, world_size as _world_size
+from .distributed import world_size as _world_size
 from . import _capi as capi
 from .circuit import HipCircuit
 from .layers import (HipCategoricalLayer, HipCPTLayer, HipGaussianLayer, HipHadamardLayer, HipKroneckerLayer, HipSumLayer,
                      HipTuckerLayer)
 from .parameters import TensorStore
 from .plan import Plan
+from .train_state import DeviceOptState, FlatBuffers, TrainerSurface
 
 
-class HipTrainer:
+class HipTrainer(TrainerSurface):
     """Maximum-likelihood training of a plan's parameters: ``loss = -mean_b log p(x_b)``."""
 
     def __init__(
@@ -87,30 +88,15 @@ class HipTrainer:
                 host = {n: (tensors[n].detach().cpu().numpy() if hasattr(tensors[n], "detach") else np.asarray(tensors[n]))
                         for n in self.user_plan.tensors}
                 tensors = padding.pad_tensors(self._pad_info, host)
-        # all parameters live in ONE flat buffer (the store's tensors are views of it, in plan order -- the order of
-        # the flat gradient and moment buffers): the optimizer step is a single launch
-        dev = torch.device(device)
-        names = list(plan.tensors)
-        sizes = [int(np.prod(plan.tensors[n][0])) for n in names]
-        self._flat_param = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-        if isinstance(tensors, TensorStore):
-            src = {n: tensors[n] for n in names}
-        else:
-            src = tensors
-        store = TensorStore(dev)
-        off = 0
-        for n, sz in zip(names, sizes):
-            view = self._flat_param[off : off + sz].view(plan.tensors[n][0])
-            v = src[n]
-            view.copy_(torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach().to(torch.float32))
-            store._t[n] = view
-            off += sz
-        store.version += 1
+        # parameters, gradients and moments: one flat buffer each (cirkit_amd/train_state.py); `grads` are views
+        fb = FlatBuffers(plan.tensors, tensors, device, optimizer)
+        self._flat_param, self._flat_grad, self._m1, self._m2, self._moments = fb.param, fb.grad, fb.m1, fb.m2, fb.moments
+        store, self.grads = fb.store, fb.grads
         self.plan = plan
         self.fused, self._fz = False, None
         self._fuse_optimizer = bool(fuse_optimizer)
-        self._opt: torch.Tensor | None = None  # the DEVICE ck_opt_state of the fused form's optimizer epilogues
-        self._opt_key = None
+        # the DEVICE ck_opt_state of the optimizer epilogues (fused form) or job epilogues (job form: the two exclude each other)
+        self._opt = DeviceOptState(device)
         why = "fused=False" if fused is False else self._setup_fused(plan, store, device)
         if why is not None:
             if fused is True:
@@ -130,21 +116,6 @@ class HipTrainer:
             raise NotImplementedError("training needs a single circuit output")
         if not self.fused:
             self._check_supported()
-        # one flat gradient buffer; per-tensor gradients are views of it (single all-reduce)
-        self._flat_grad = torch.zeros(sum(sizes), dtype=torch.float32, device=self.device)
-        self.grads: dict[str, torch.Tensor] = {}
-        off = 0
-        for n, sz in zip(names, sizes):
-            self.grads[n] = self._flat_grad[off : off + sz].view(plan.tensors[n][0])
-            off += sz
-        self._m1 = torch.zeros_like(self._flat_grad) if optimizer == "adam" else None
-        self._m2 = torch.zeros_like(self._flat_grad) if optimizer == "adam" else None
-        self._moments: dict[str, tuple] = {}
-        if optimizer == "adam":
-            off = 0
-            for n, sz in zip(names, sizes):
-                self._moments[n] = (self._m1[off : off + sz], self._m2[off : off + sz])
-                off += sz
         self._bwd: dict[int, dict] = {}
         # input validation: the circuit's flag is raised by a batch with an out-of-range category; a step on such a batch
         # changes nothing (`step`), the flag is latched into `_bad_seen` -- what `check_inputs()` reports -- and cleared
@@ -423,7 +394,7 @@ class HipTrainer:
         # turns the validation flag of the forward into this step's flag (`step`: what the optimizer launch skips on)
         # (with the optimizer in the epilogues -- `with_opt`, one rank -- it is the optimizer's clock as well: a flagged step is dropped)
         capi.call("ck_fill_latch", fz["dw_sum"].data_ptr(), fz["dw_sum"].numel(), 0.0, c._bad_input.data_ptr(),
-                  self._step_flag.data_ptr(), self._bad_seen.data_ptr(), self._opt_state().data_ptr() if with_opt else None, stream)
+                  self._step_flag.data_ptr(), self._bad_seen.data_ptr(), self._opt_state().ptr if with_opt else None, stream)
         for p in st["need_zero"]:
             if gviews[p] is not None:
                 capi.call("ck_fill_f32", gviews[p].data_ptr(), gviews[p].numel(), 0.0, stream)
@@ -489,7 +460,7 @@ class HipTrainer:
             # the optimizer in the epilogues (one rank): the launch that
             # holds the gradients of the Categorical and dense logits updates them and writes the next forward's table, the
             # launch that differentiates the weight softmaxes updates those logits and writes the next forward's weights
-            state = self._opt_state().data_ptr()  # (its clock of this step: the fill launch at the start of the list)
+            state = self._opt_state().ptr  # (its clock of this step: the fill launch at the start of the list)
             topt = capi.TableOpt()
             topt.state = state
             (m1c, m2c), (m1d, m2d) = self._moments.get(n_cat, (None, None)), self._moments.get(n_dense, (None, None))
@@ -605,23 +576,18 @@ class HipTrainer:
         ``self.grads`` (views of one flat buffer).  Returns the device tensor [sum log p, count] of this shard -- a view
         of the circuit's own buffer, overwritten by the next step (clone it to keep it).
 
-        ``global_batch`` defaults to the number of rows of ALL ranks when torch.distributed is initialised (every rank is
-        assumed to hold as many rows as this one; pass it explicitly otherwise), so that the SUM all-reduce of
-        `all_reduce_grads` yields the gradient of the mean NLL of the global batch."""
+        ``global_batch``: see `TrainerSurface._global_batch`."""
         with torch.cuda.device(self.device):  # every launch below goes to a stream of self.device
             return self._loss_and_grads(x, global_batch)
 
     def _loss_and_grads(self, x: torch.Tensor, global_batch: int | None) -> torch.Tensor:
         self._grads_current = True
-        import torch.distributed as dist
-
-        if global_batch is None and _world_size() > 1:
-            global_batch = int(x.shape[0]) * _world_size()
         B = int(x.shape[0])
+        gB = self._global_batch(B, global_batch)
         if self._jobs is not None:  # one recorded launch list: parameters, forward levels, root, backward levels
-            return self._jobs.loss_and_grads(x, float(global_batch or B))
+            return self._jobs.loss_and_grads(x, gB)
         ll = self._forward(x)
-        self._backward(B, float(global_batch or B), None)
+        self._backward(B, gB, None)
         return ll
 
     def _forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -751,15 +717,6 @@ class HipTrainer:
         return {n: self.circuit.store.export(n) if self._pad_info is None else
                 self._pad_info.unpad(n, self.circuit.store[n].detach().cpu().numpy()) for n in self.user_plan.tensors}
 
-    def all_reduce_grads(self) -> None:
-        """The one gradient exchange of data-parallel training: SUM over ranks of the flat buffer."""
-        import torch.distributed as dist
-
-        # (also at world size 1: the collective is then RCCL's identity, and the same call path is what a 1-GPU box can test)
-        # RCCL through the C ABI (ck_comm_all_reduce_f32, on the launch stream) when a HipComm is set; torch.distributed otherwise
-        if _default_comm() is not None or (dist.is_available() and dist.is_initialized()):
-            _all_reduce_sum(self._flat_grad)
-
     def apply_gradients(self, skip_flag: torch.Tensor | None = None) -> None:
         """The optimizer step on `self.grads`.  `skip_flag`: a device int32; when it is nonzero at launch time the step
         changes nothing (parameters, moments, Adam's step count)."""
@@ -771,22 +728,6 @@ class HipTrainer:
         a Categorical table the epilogue's table job applies to (C % 4 == 0; `_setup_fused` checked C <= 256)."""
         return (self.fused and self._fuse_optimizer and self._pad_info is None and self._jobs is None
                 and self.circuit.layers[self._fz["group"].input_layer].num_categories % 4 == 0)
-
-    def _opt_state(self) -> torch.Tensor:
-        """The DEVICE `ck_opt_state` (constants, clock, dropped steps) of the optimizer epilogues."""
-        key = (float(self.lr), tuple(float(b) for b in self.betas), float(self.eps))
-        if self._opt is None:
-            o = capi.OptState()
-            o.lr, o.b1, o.b2, o.eps, o.bc1, o.bc2 = self.lr, self.betas[0], self.betas[1], self.eps, 1.0, 1.0
-            o.step, o.skipped, o.skip_now, o.kind = 0, 0, 0, 1 if self.optimizer == "adam" else 0
-            o.b1d, o.b2d = float(self.betas[0]), float(self.betas[1])
-            self._opt = torch.frombuffer(bytearray(bytes(o)), dtype=torch.uint8).to(self.device)
-        elif key != self._opt_key:  # (the learning rate was changed between steps: the first 16 bytes)
-            head = torch.tensor([self.lr, self.betas[0], self.betas[1], self.eps], dtype=torch.float32).view(torch.uint8)
-            self._opt[:16].copy_(head.to(self.device))
-            self._opt[40:56].copy_(torch.tensor([self.betas[0], self.betas[1]], dtype=torch.float64).view(torch.uint8).to(self.device))
-        self._opt_key = key
-        return self._opt
 
     def _use_clock(self, which: str) -> None:
         """ONE optimizer clock per trainer: the fused job step counts Adam's steps on the device (`ck_opt_state.step`, not advanced
@@ -820,8 +761,6 @@ class HipTrainer:
     def step(self, x: torch.Tensor, *, global_batch: int | None = None) -> torch.Tensor:
         """One optimisation step on this rank's shard; returns the device tensor [sum log p, count]
         of the shard (before the update)."""
-        import torch.distributed as dist
-
         c = self.circuit
         alone = _world_size() <= 1
         if self._jobs is not None and self._fuse_optimizer and alone:
@@ -829,7 +768,7 @@ class HipTrainer:
             self._use_clock("device")
             self.step_count += 1
             self._grads_current = False
-            return self._jobs.step(x, float(global_batch or int(x.shape[0])))
+            return self._jobs.step(x, self._global_batch(int(x.shape[0]), global_batch))
         if self._fused_opt_ok() and alone:
             # the fused form with the optimizer in its backward epilogues: no optimizer launch, no parameter prologue before
             # the next forward (`grads` still receives every gradient)
@@ -839,47 +778,20 @@ class HipTrainer:
                 self._grads_current = True
                 B = int(x.shape[0])
                 ll = self._forward(x)
-                self._backward(B, float(global_batch or B), None, with_opt=True)
+                self._backward(B, self._global_batch(B, global_batch), None, with_opt=True)
                 c.store.raw_writes += 1
             return ll
         ll = self.loss_and_grads(x, global_batch=global_batch)
+        # the flag a batch with an out-of-range category raised is THIS step's (fused: handed on by the backward's first launch;
+        # layer-wise: latched and cleared after the update); everything stays on the device -- no host synchronisation
         validate = c.validate_inputs and c._int_input
-        # a batch with an out-of-range category (NaN log-likelihood) must not reach the parameters.  The flag it raised is THIS
-        # step's (fused: handed on by the backward's first launch; layer-wise: latched and cleared below), everything stays on
-        # the device -- no host synchronisation: on a single rank the optimizer launch changes nothing at all; with several
-        # ranks the other ranks' gradients are valid and every rank must take the same step, so this rank's are dropped
-        flag = self._step_flag if self.fused else c._bad_input
-        if validate and not alone:
-            with torch.cuda.device(self.device):
-                capi.call("ck_zero_if_flag", self._flat_grad.data_ptr(), self._flat_grad.numel(), flag.data_ptr(),
-                          torch.cuda.current_stream(self.device).cuda_stream)
-        self.all_reduce_grads()
-        self.apply_gradients(flag if (validate and alone) else None)
-        if validate and not self.fused:
-            with torch.cuda.device(self.device):
-                capi.call("ck_latch_flag", c._bad_input.data_ptr(), self._bad_seen.data_ptr(),
-                          torch.cuda.current_stream(self.device).cuda_stream)
+        self._reduce_and_apply((self._step_flag if self.fused else c._bad_input) if validate else None, alone, latch=not self.fused)
         return ll
 
     @property
     def skipped_steps(self) -> int:
         """Steps that changed nothing because their batch held an illegal category (a device read)."""
-        n = int(self._skipped.item())
-        if self._jobs is not None:
-            n += self._jobs.opt_counters()[1]
-        if self._opt is not None:
-            n += int(self._opt[28:32].cpu().view(torch.int32)[0])
-        return n
-
-    def check_inputs(self) -> None:
-        """Raise ``IndexError`` if a batch since the last check held a category out of range (as
-        `TorchCategoricalLayer`'s indexing would have, layers/input.py:399-412).  On a single rank the steps on such
-        batches changed nothing (parameters, moments, Adam's step count); later valid batches train normally."""
-        if int(self._bad_seen.item()) != 0:
-            self._bad_seen.zero_()
-            self.circuit._bad_input.zero_()
-            raise IndexError("a batch held a category outside [0, num_categories) of its variable")
-        self.circuit.check_inputs()
+        return int(self._skipped.item()) + self.opt_counters()[1]
 
 
 class _CircuitFunction(torch.autograd.Function):

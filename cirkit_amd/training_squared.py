@@ -30,13 +30,13 @@ from typing import Mapping
 import numpy as np
 import torch
 
-from .distributed import all_reduce_sum as _all_reduce_sum, default_comm as _default_comm, world_size as _world_size
+from .distributed import world_size as _world_size
 from . import _capi as capi
 from .circuit import HipCircuit
 from .layers import (HipCategoricalLayer, HipConstantValueLayer, HipCPTLayer, HipEmbeddingLayer, HipGaussianLayer, HipHadamardLayer,
                      HipSumLayer, HipTensorDotLayer, HipTuckerLayer)
-from .parameters import TensorStore
 from .plan import Plan
+from .train_state import DeviceOptState, FlatBuffers, TrainerSurface
 
 
 class _PlanBackward:
@@ -688,7 +688,7 @@ class _SignedCircuit:
                       ga + 4 * o, self.grads[self.wname[i]].data_ptr(), l.num_folds, l.arity, B, l.num_output_units, *gather, stream)
 
 
-class HipSquaredTrainer:
+class HipSquaredTrainer(TrainerSurface):
     """Maximum-likelihood training of a squared circuit with real parameters: ``loss = -mean_b (2 Re c(x_b) - Re Z)``
     (the reference's loop for sum-of-squares circuits; c under complex-lse-sum -- or a real circuit under lse-sum --, Z built
     from the plan of c)."""
@@ -705,87 +705,45 @@ class HipSquaredTrainer:
 
             plan_z = squared_partition_plan(plan_c)
         dev = torch.device(device)
-        names = list(plan_c.tensors)
-        sizes = [int(np.prod(plan_c.tensors[n][0])) for n in names]
-        self._flat_param = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-        store = TensorStore(dev)
-        off = 0
-        for n, sz in zip(names, sizes):
+        for n in plan_c.tensors:
             v = tensors[n]
             if np.iscomplexobj(v) or (hasattr(v, "is_complex") and v.is_complex()):
                 raise NotImplementedError("HipSquaredTrainer: complex parameter tensors")
-            view = self._flat_param[off : off + sz].view(plan_c.tensors[n][0])
-            view.copy_(torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach().to(torch.float32))
-            store._t[n] = view
-            off += sz
-        store.version += 1
-        self.plan_c, self.plan_z, self.store = plan_c, plan_z, store
+        # parameters, gradients and moments: one flat buffer each (cirkit_amd/train_state.py): one optimizer launch, one all-reduce
+        fb = FlatBuffers(plan_c.tensors, tensors, dev, optimizer)
+        self._flat_param, self._flat_grad, self._m1, self._m2 = fb.param, fb.grad, fb.m1, fb.m2
+        self.plan_c, self.plan_z, self.store, self.grads = plan_c, plan_z, fb.store, fb.grads
         # (every layer evaluates its own parameter graph -- no batched prologue --: `HipParameter.backward` differentiates what
         #  `HipParameter.evaluate` left behind)
         kw = dict(device=dev, use_graph=False, fuse=False, pad_units=False, signed_real=False, tiled_weights=False, dense_on_table=False,
                   fused_weight_softmax=False, batch_params=False)
-        self.c = HipCircuit(plan_c, store, **kw)
-        self.z = HipCircuit(plan_z, store, **kw)
-        self.device = self.c.device
-        self._flat_grad = torch.zeros(sum(sizes), dtype=torch.float32, device=self.device)
-        self.grads: dict[str, torch.Tensor] = {}
-        off = 0
-        for n, sz in zip(names, sizes):
-            self.grads[n] = self._flat_grad[off : off + sz].view(plan_c.tensors[n][0])
-            off += sz
+        self.c = HipCircuit(plan_c, self.store, **kw)
+        self.z = HipCircuit(plan_z, self.store, **kw)
+        self.circuit, self.device = self.c, self.c.device  # (`circuit`: the one whose batches are validated)
         # Z's launches run beside c's on a second stream: their gradients go to a buffer of their own, added before the optimizer
         self._flat_grad_z = torch.zeros_like(self._flat_grad)
-        grads_z, off = {}, 0
-        for n, sz in zip(names, sizes):
-            grads_z[n] = self._flat_grad_z[off : off + sz].view(plan_c.tensors[n][0])
-            off += sz
-        self._bwd_c, self._bwd_z = _PlanBackward(self.c, self.grads), _PlanBackward(self.z, grads_z)
+        self._bwd_c, self._bwd_z = _PlanBackward(self.c, self.grads), _PlanBackward(self.z, fb.views(self._flat_grad_z))
         # c on signed-log blocks where its layers allow it (`signed`: None = where they do, True = required, False = never)
         sc = _SignedCircuit(self.c, self.grads) if signed is not False else None
         if signed is True and sc.why is not None:
             raise NotImplementedError(f"HipSquaredTrainer(signed=True): {sc.why}")
         self._signed = sc if (sc is not None and sc.why is None) else None
         self.lr, self.optimizer, self.betas, self.eps = lr, optimizer, betas, eps
-        self._m1 = torch.zeros_like(self._flat_grad) if optimizer == "adam" else None
-        self._m2 = torch.zeros_like(self._flat_grad) if optimizer == "adam" else None
         self._bad_seen = torch.zeros(1, dtype=torch.int32, device=self.device)  # latched by `step`, reported by `check_inputs`
         self._ll = torch.zeros(2, dtype=torch.float64, device=self.device)
-        self._opt: torch.Tensor | None = None  # the DEVICE ck_opt_state: constants, clock, dropped steps
-        self._opt_key = None
+        self._opt = DeviceOptState(self.device)  # constants, clock, dropped steps
         self.use_graph = bool(use_graph)
-        self._programs: dict[tuple, tuple] = {}
+        self._programs: dict[tuple, tuple[capi.Program | None, int]] = {}
         self._side: tuple[torch.cuda.Stream, torch.cuda.Stream] | None = None
 
-    def __del__(self):
-        try:
-            for pr, _ in self._programs.values():
-                capi.load().ck_program_destroy(pr)
-        except Exception:
-            pass
-
     # -- the recorded step ----------------------------------------------------------------------------------------------
-    def _opt_state(self) -> torch.Tensor:
-        key = (float(self.lr), tuple(float(b) for b in self.betas), float(self.eps))
-        if self._opt is None:
-            o = capi.OptState()
-            o.lr, o.b1, o.b2, o.eps, o.bc1, o.bc2 = self.lr, self.betas[0], self.betas[1], self.eps, 1.0, 1.0
-            o.step, o.skipped, o.skip_now, o.kind = 0, 0, 0, 1 if self.optimizer == "adam" else 0
-            o.b1d, o.b2d = float(self.betas[0]), float(self.betas[1])  # the bias corrections are formed in double (torch.optim.Adam does)
-            self._opt = torch.frombuffer(bytearray(bytes(o)), dtype=torch.uint8).to(self.device)
-        elif key != self._opt_key:  # (the learning rate was changed between steps: the first 16 bytes)
-            head = torch.tensor([self.lr, self.betas[0], self.betas[1], self.eps], dtype=torch.float32).view(torch.uint8)
-            self._opt[:16].copy_(head.to(self.device))
-            self._opt[40:56].copy_(torch.tensor([self.betas[0], self.betas[1]], dtype=torch.float64).view(torch.uint8).to(self.device))
-        self._opt_key = key
-        return self._opt
-
     def _enqueue_optimizer(self, stream: int, with_z: bool = False) -> None:
         """`with_z`: the optimizer reads c's and Z's gradient buffers and adds them itself (no axpy launch before it; `grads`
         then holds c's part only -- `loss_and_grads` leaves the sum)."""
         p = self._flat_param
         capi.call("ck_opt_step_range", p.data_ptr(), self._flat_grad.data_ptr(), self._flat_grad_z.data_ptr() if with_z else None,
                   None if self._m1 is None else self._m1.data_ptr(), None if self._m2 is None else self._m2.data_ptr(), p.numel(),
-                  self._opt_state().data_ptr(), stream)
+                  self._opt_state().ptr, stream)
 
     def _enqueue(self, part: str, B: int, gB: float, with_optimizer: bool, stream: int) -> None:
         n = self._flat_grad.numel()
@@ -809,7 +767,7 @@ class HipSquaredTrainer:
             c, z = self.c, self.z
             validate = c.validate_inputs and c._int_input
             if with_optimizer:  # a batch with an illegal category drops the step (skip_now)
-                capi.call("ck_opt_tick", self._opt_state().data_ptr(), c._bad_input.data_ptr() if validate else None,
+                capi.call("ck_opt_tick", self._opt_state().ptr, c._bad_input.data_ptr() if validate else None,
                           self._bad_seen.data_ptr() if validate else None, stream)
             yc = self._signed.output(B) if self._signed is not None else c._bind(B).views[int(c._out_pairs[0, 0])][int(c._out_pairs[0, 1])]
             yz = z._bind(1).views[int(z._out_pairs[0, 0])][int(z._out_pairs[0, 1])]
@@ -836,16 +794,11 @@ class HipSquaredTrainer:
                 return
             for k in [k for k in self._programs if k[:4] == key[:4] and k != key]:  # (rebound arenas: their lists are stale)
                 if self._programs[k][0] is not None:
-                    capi.load().ck_program_destroy(self._programs[k][0])
+                    self._programs[k][0].close()
                 del self._programs[k]
-            prog = C.c_void_p()
-            capi.call("ck_program_begin", C.byref(prog))
-            try:
-                self._enqueue(part, B, gB, with_optimizer, run.cuda_stream)
-            finally:
-                capi.call("ck_program_end", prog)
+            prog = capi.Program.record(lambda: self._enqueue(part, B, gB, with_optimizer, run.cuda_stream))
             self._programs[key] = (prog, seen)
-        capi.call("ck_program_launch", prog, 1 if self.use_graph else 0, run.cuda_stream)
+        prog.launch(run.cuda_stream, self.use_graph)
 
     def _launch(self, x: torch.Tensor, B: int, gB: float, with_optimizer: bool) -> None:
         """Forward and backward of c on the caller's stream, forward and backward of Z (a few hundred launches on one row: they
@@ -879,13 +832,6 @@ class HipSquaredTrainer:
         if main is not cur:
             cur.wait_stream(main)
 
-    def _global_batch(self, B: int, global_batch: int | None) -> float:
-        import torch.distributed as dist
-
-        if global_batch is None and _world_size() > 1:
-            global_batch = B * _world_size()
-        return float(global_batch or B)
-
     def loss_and_grads(self, x: torch.Tensor, *, global_batch: int | None = None) -> torch.Tensor:
         """Forward of c on the batch and of Z, then both backward launch lists: the gradients of
         ``-(1 / global_batch) sum_b (2 Re c(x_b)) + (B / global_batch) Re Z`` land in `self.grads`; returns the device tensor
@@ -895,19 +841,12 @@ class HipSquaredTrainer:
             self._launch(x, B, self._global_batch(B, global_batch), False)
             return self._ll
 
-    def all_reduce_grads(self) -> None:
-        import torch.distributed as dist
-
-        # RCCL through the C ABI (ck_comm_all_reduce_f32, on the launch stream) when a HipComm is set; torch.distributed otherwise
-        if _default_comm() is not None or (dist.is_available() and dist.is_initialized()):
-            _all_reduce_sum(self._flat_grad)
-
     def apply_gradients(self, skip_flag: torch.Tensor | None = None) -> None:
         """The optimizer step on `self.grads`.  `skip_flag`: a device int32; nonzero at launch time = the step changes nothing
         (parameters, moments, Adam's step count), the flag is latched into what `check_inputs()` reports and cleared."""
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            capi.call("ck_opt_tick", self._opt_state().data_ptr(), None if skip_flag is None else skip_flag.data_ptr(),
+            capi.call("ck_opt_tick", self._opt_state().ptr, None if skip_flag is None else skip_flag.data_ptr(),
                       None if skip_flag is None else self._bad_seen.data_ptr(), stream)
             self._enqueue_optimizer(stream)
             self.store.touch()
@@ -918,8 +857,6 @@ class HipSquaredTrainer:
         circuit's flag into the step's skip state and the update changes nothing; with several ranks this rank's gradients are
         zeroed before the all-reduce (every rank takes the same step).  The flag is latched into what `check_inputs()` reports
         and cleared -- no host synchronisation, and alone everything after the two forwards is one replayed launch list."""
-        import torch.distributed as dist
-
         c = self.c
         validate = c.validate_inputs and c._int_input
         alone = _world_size() <= 1
@@ -929,23 +866,8 @@ class HipSquaredTrainer:
             if alone:
                 self.store.touch()
                 return self._ll
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if validate:
-                capi.call("ck_zero_if_flag", self._flat_grad.data_ptr(), self._flat_grad.numel(), c._bad_input.data_ptr(), stream)
-        self.all_reduce_grads()
-        self.apply_gradients(None)
-        if validate:
-            with torch.cuda.device(self.device):
-                capi.call("ck_latch_flag", c._bad_input.data_ptr(), self._bad_seen.data_ptr(),
-                          torch.cuda.current_stream(self.device).cuda_stream)
+        self._reduce_and_apply(c._bad_input if validate else None, alone, latch=True)
         return self._ll
-
-    def opt_counters(self) -> tuple[int, int]:
-        """(steps taken, steps dropped) of the optimizer's device clock (a device read)."""
-        if self._opt is None:
-            return 0, 0
-        v = self._opt[24:32].cpu().view(torch.int32)
-        return int(v[0]), int(v[1])
 
     @property
     def step_count(self) -> int:
@@ -954,15 +876,6 @@ class HipSquaredTrainer:
     @property
     def skipped_steps(self) -> int:
         return self.opt_counters()[1]
-
-    def check_inputs(self) -> None:
-        """Raise ``IndexError`` if a batch since the last check held a category out of range (layers/input.py:258-266,
-        399-412 index with it); on a single rank the steps on such batches changed nothing."""
-        if int(self._bad_seen.item()) != 0:
-            self._bad_seen.zero_()
-            self.c._bad_input.zero_()
-            raise IndexError("a batch held a category outside [0, num_categories) of its variable")
-        self.c.check_inputs()
 
     def gradients(self) -> dict[str, np.ndarray]:
         return {n: g.detach().cpu().numpy() for n, g in self.grads.items()}

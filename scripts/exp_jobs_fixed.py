@@ -24,7 +24,7 @@ tr.step(x)
 torch.cuda.synchronize()
 st = js.bind(B)
 pool = st["pool"].data_ptr()
-opt = js._opt_state().data_ptr()
+opt = tr._opt_state().ptr
 stream = torch.cuda.current_stream().cuda_stream
 la = max((l for l in st["launches"] if l[0] == "sum_bwd"), key=lambda l: l[2])
 dt = np.dtype(capi.SUM_JOB_DTYPE)

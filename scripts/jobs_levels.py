@@ -35,7 +35,7 @@ for _ in range(3):
 torch.cuda.synchronize()
 st = js.bind(B)
 MODE = int(os.environ.get("MODE", "2"))  # 2: the optimizer inside the epilogues (what `step` runs on one rank); 1: d theta only
-OPT = js._opt_state().data_ptr() if MODE == 2 else None
+OPT = tr._opt_state().ptr if MODE == 2 else None
 pool = st["pool"].data_ptr()
 blk = B * 64
 stream = torch.cuda.current_stream().cuda_stream

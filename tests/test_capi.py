@@ -77,6 +77,27 @@ def test_program_recording_needs_no_device():
     assert lib.ck_program_destroy(prog) == 0
 
 
+def test_program_type_records_and_closes_once():
+    """`capi.Program`: the same recording as above through the owner of the handle; a body that raises still ends the
+    recording, and a second `close()` is a no-op."""
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+
+    def body():
+        capi.call("ck_param_unary", capi.CK_UNARY_EXP, p, p, 16, 0.0, 1.0, None)
+        capi.call("ck_ll_sum", p, 8, 1, p, None)
+
+    prog = capi.Program.record(body)
+    assert prog.num_ops == 2
+    prog.close()
+    prog.close()
+    with pytest.raises(ValueError):  # (validation while recording: nothing is appended, the error reaches the caller)
+        capi.Program.record(lambda: capi.call("ck_param_unary", 99, p, p, 4, 0.0, 1.0, None))
+    again = capi.Program.record(body)  # (not CK_ERR_STATE: the failed recording was ended)
+    assert again.num_ops == 2
+    again.close()
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(capi, "_lib", None)
     monkeypatch.setattr(capi, "_LIB_PATH", str(tmp_path / "nope.so"))
