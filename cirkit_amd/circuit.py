@@ -961,6 +961,29 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
 
         return sample(self, num_samples, seed=seed, return_choices=return_choices)
 
+    def sample_conditional(self, x: torch.Tensor, sample_vars, *, seed: int | None = None, return_choices: bool = False,
+                           return_log_evidence: bool = False, rows_per_chunk: int | None = None):
+        """Draw the unobserved part of every row of ``x`` (B, D): row n's sampled entries are an exact draw from
+        ``p(x_S | x_O) = c(x_O, x_S) / c(x_O)`` of output fold 0, unit 0, for any circuit `sample` accepts.  The reference
+        conditions on ONE observation by building a new circuit (symbolic/functional.py:75-135 ``evidence``), which its
+        ``SamplingQuery`` then refuses as unnormalised; here every row has its own evidence, in one batch.
+
+        `sample_vars` marks the variables to draw, in the forms ``integrate_vars`` takes (a bool mask ``(B, D)`` / ``(1, D)`` /
+        ``(D,)`` or an iterable of variable ids, with the same errors); an entry of ``x`` holding the marginalisation
+        sentinel (a negative category, NaN) is drawn too, every other entry is evidence and is returned bit for bit.
+        Returns ``(B, D)`` on this device with the dtype rule of `sample`.  `seed` as in `sample`: the draws use the same
+        Philox counters (row n, global fold id), so with every variable sampled they follow ``sample(B, seed=...)`` and
+        they do not depend on `rows_per_chunk`.  `return_choices`: also the ``(F, B)`` int32 choices of every sum-type layer,
+        as `sample` returns them.  `return_log_evidence`: also the ``(B,)`` fp32 ``log c(x_O)`` (= ``self(x,
+        integrate_vars=mask)[:, 0, 0]``).  A row whose evidence has no finite mass draws nothing: its sampled entries keep
+        the sentinel (-1 / NaN) and its choices are -1 (no exception, no synchronisation).  `rows_per_chunk`: rows per
+        evidence forward (None: its activation arena stays <= 2 GiB).  Results are in the order: samples, choices, log
+        evidence (cirkit_amd/sampling.py)."""
+        from .sampling import sample_conditional
+
+        return sample_conditional(self, x, sample_vars, seed=seed, return_choices=return_choices,
+                                  return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
+
     def log_likelihood_sum(self, x: torch.Tensor, out: torch.Tensor | None = None, *, reduce: bool = False) -> torch.Tensor:
         """Device tensor ``[sum_b log p(x_b), B]`` in fp64 -- the two numbers the data-parallel
         all-reduce exchanges (SURVEY.md section 8 e).  Requires a single scalar output.

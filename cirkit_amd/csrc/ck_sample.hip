@@ -4,6 +4,7 @@
 
 #include "ck_internal.h"
 #include "ck_philox.h"
+#include "ck_sample_draw.h"
 
 namespace {
 
@@ -68,25 +69,6 @@ __global__ void __launch_bounds__(kCdfRowsPerBlock * ck::kWave)
   if (bad) atomicOr(flag, bad);
 }
 
-// smallest i with t < cdf[i]: an entry whose own mass is positive (t < T is guaranteed by the caller)
-__device__ __forceinline__ int cdf_search(const float* __restrict__ row, int M, float t) {
-  int lo = 0, hi = M - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (t < row[mid]) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ int draw(const float* __restrict__ row, int M, float u) {
-  const float T = row[M - 1];
-  if (!(T > 0.f)) return 0;  // (a row with no mass is never reached from a root of positive mass)
-  float t = u * T;
-  if (t >= T) t = __int_as_float(__float_as_int(T) - 1);  // the float below T (T > 0)
-  return cdf_search(row, M, t);
-}
-
 // One workgroup owns `S` consecutive samples; sel[g * S + s] = the unit of global fold g on sample s's induced tree, -1 if g
 // is not on it.  Layers are walked from the last to the first; a fold writes the units of its children, which belong to
 // earlier layers, so one barrier per layer orders the walk.
@@ -140,7 +122,7 @@ __global__ void __launch_bounds__(kWalkThreads)
         if (x_float) static_cast<float*>(x)[o] = v;
         continue;  // (a Gaussian layer makes the output fp32: DESIGN.md section 11)
       }
-      const int i = draw(L.cdf + (static_cast<int64_t>(f) * L.Ko + k) * L.M, L.M, ck::philox_uniform(p.x[0]));
+      const int i = ck::cdf_draw(L.cdf + (static_cast<int64_t>(f) * L.Ko + k) * L.M, L.M, ck::philox_uniform(p.x[0]));
       if (L.type == CK_SAMPLE_CATEGORICAL) {
         const int64_t o = n * D + L.scope[f];
         if (x_float) static_cast<float*>(x)[o] = static_cast<float>(i);

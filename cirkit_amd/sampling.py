@@ -12,6 +12,10 @@ gather among those draws -- and refuses circuits whose sum weights are not norma
   call (`ck_sample_walk`); randomness is Philox4x32-10 with counter (sample, global fold id, 0, 0) (cirkit_amd/csrc/ck_philox.h).
 
 On a normalised circuit every partition function is 1 and the distribution is the reference's.
+
+`HipCircuit.sample_conditional` draws the unobserved part of every row from ``p(x_S | x_O)``: the same walk, weighted by the
+per-row unit values of the layer-wise marginal forward of the row's evidence instead of the partition functions, so its CDF
+rows are built on the device per (fold, sample) (`ck_sample_cond_walk`, DESIGN.md section 11 "Conditional sampling").
 """
 
 from __future__ import annotations
@@ -67,6 +71,29 @@ def _choice_map(spec, user_spec) -> np.ndarray:
     if _is_mixing(spec):
         return h.astype(np.int32)
     return np.where(k < ku, h * ku + k, -1).astype(np.int32)
+
+
+_CHUNK_ARENA_BYTES = 2 << 30  # default bound of the evidence forward's activation arena (`sample_conditional`)
+
+
+def chunk_rows(B: int, rows_per_chunk: int | None, arena_bytes_per_row: int) -> list[tuple[int, int]]:
+    """(first row, rows) of each chunk of a `sample_conditional` batch of B rows: `rows_per_chunk` rows each (None: as many as
+    keep the evidence forward's arena <= 2 GiB), the last chunk the remainder.  Two sizes at most: the chunk and the tail."""
+    if rows_per_chunk is None:
+        R = max(1, _CHUNK_ARENA_BYTES // max(1, int(arena_bytes_per_row)))
+    else:
+        R = int(rows_per_chunk)
+        if R <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+    R = min(R, B)
+    return [(r0, min(R, B - r0)) for r0 in range(0, B, R)]
+
+
+def fold_block_offsets(bases, folds, units, B: int) -> np.ndarray:
+    """(total folds) int64 `val_off` of `ck_sample_cond_walk`: the element offset, from the arena base, of global fold g's
+    (B, Ko) block, for layers whose (F, B, Ko) outputs start at element offsets `bases`."""
+    return np.concatenate([int(b) + np.arange(int(f), dtype=np.int64) * int(B) * int(k) for b, f, k in zip(bases, folds, units)]
+                          ).astype(np.int64)
 
 
 class Sampler:
@@ -144,7 +171,10 @@ class Sampler:
                 self.sum_layers.append(j)
             self.layers.append(d)
         self.zero_fill = not covered.all()  # (variables outside every input layer's scope read 0)
+        self.uncovered = torch.from_numpy(np.nonzero(~covered)[0]).to(dev)  # (copied once: a call does not wait on the host)
         self._zc = None
+        self._wtab: tuple | None = None  # (parameter key, device table of the sum-type layers' linear weights)
+        self._val_off: dict[int, tuple[int, torch.Tensor]] = {}  # chunk rows -> (arena address, val_off table)
         self._key = None
         self._table: torch.Tensor | None = None  # the device descriptor table without choices
         self._desc: np.ndarray | None = None
@@ -273,6 +303,92 @@ class Sampler:
                 self._keep = table  # (the launch is asynchronous: the table outlives it until the next call)
         return (x, choices) if return_choices else x
 
+    # -- conditional sampling ---------------------------------------------------------------------------------------
+    def _weight_table(self) -> torch.Tensor:
+        """Device array of one pointer per layer: the (F, Ko, M) linear weights `prepare` evaluated, NULL for the others."""
+        if self._wtab is None or self._wtab[0] != self._key:
+            ptrs = np.array([d["w"].data_ptr() if "w" in d else 0 for d in self.layers], dtype=np.uint64)
+            self._wtab = (self._key, torch.from_numpy(ptrs.view(np.int64)).to(self.device))
+        return self._wtab[1]
+
+    def _val_off_table(self, bd) -> torch.Tensor:
+        """(total_folds) int64: element offset of global fold g's (B, Ko) block from the arena base of binding `bd`."""
+        hit = self._val_off.get(bd.B)
+        if hit is not None and hit[0] == bd.arena.data_ptr():
+            return hit[1]
+        base = bd.arena.data_ptr()
+        off = fold_block_offsets([(v.data_ptr() - base) // v.element_size() for v in bd.views],
+                                 [l.num_folds for l in self.plan.layers], [l.num_output_units for l in self.plan.layers], bd.B)
+        t = torch.from_numpy(off).to(self.device)
+        self._val_off[bd.B] = (base, t)
+        return t
+
+    def sample_conditional(self, x: torch.Tensor, sample_vars, seed: int | None = None, return_choices: bool = False,
+                           return_log_evidence: bool = False, rows_per_chunk: int | None = None):
+        D = self.D
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise ValueError("The input to the circuit should have shape (B, D), where B is the batch size and D "
+                             "is the number of variables the circuit is defined on")
+        if x.shape[1] < D:
+            raise ValueError(f"expected at least {D} variables, found {x.shape[1]}")
+        B = int(x.shape[0])
+        if B <= 0:
+            raise ValueError("empty batch")
+        xm = self.hc._apply_integration_mask(x[:, :D].to(self.device), sample_vars).to(self.dtype).contiguous()  # (its errors first)
+        chunks = chunk_rows(B, rows_per_chunk, self.hc.arena_bytes(1))
+        sizes = {nb for _, nb in chunks}
+        if seed is None:
+            seed = int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64).item())
+        seed = int(seed) & (2**64 - 1)
+        self.prepare()
+        zc = self._z_circuit()
+        for b in [b for b in zc._bindings if b != 1 and b not in sizes]:  # two batch sizes bound: the chunk and the tail
+            zc._bindings.pop(b).destroy()
+            self._val_off.pop(b, None)
+        dev = self.device
+        j_root = int(np.searchsorted(self.fold_off, self.root_fold, side="right") - 1)
+        f_root = self.root_fold - int(self.fold_off[j_root])
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            out = xm.clone()  # (the sentinels mark what is left to draw)
+            logev = torch.empty(B, dtype=torch.float32, device=dev)
+            table, choices = self._table, None
+            if return_choices:
+                desc = self._desc.copy()
+                choices = []
+                for j in self.sum_layers:
+                    c = torch.empty((self.layers[j]["F"], B), dtype=torch.int32, device=dev)
+                    desc[j]["choices"] = c.data_ptr()
+                    choices.append(c)
+                table = torch.from_numpy(desc.view(np.uint8).copy()).pin_memory().to(dev, non_blocking=True)
+            wtab = self._weight_table()
+            for r0, nb in chunks:
+                bd = zc._run(xm[r0 : r0 + nb])
+                # the evidence is range-checked where it is staged, on the private circuit's flag: move a hit to the flag
+                # `hc.check_inputs()` reports (that chunk's outputs are NaN, as `hc(x)`'s would be) and clear this one, so
+                # that later forwards of the private circuit -- `prepare()` included -- are not poisoned by it
+                if self.hc.validate_inputs:
+                    self.hc._bad_input.bitwise_or_(zc._bad_input)
+                zc._bad_input.zero_()
+                logev[r0 : r0 + nb].copy_(bd.views[j_root][f_root, :, 0])
+                capi.call("ck_sample_cond_walk", table.data_ptr(), wtab.data_ptr(), len(self.layers), self.root_fold, 0,
+                          self.total_folds, self.S, bd.arena.data_ptr(), self._val_off_table(bd).data_ptr(), r0, nb, B, D, seed,
+                          xm[r0].data_ptr(), out[r0].data_ptr(), 1 if self.float_out else 0, stream)
+            if self.zero_fill:  # variables outside every input layer's scope: 0, as `sample` writes, in rows with mass
+                u = self.uncovered
+                cols = out[:, u]
+                sent = torch.isnan(cols) if self.float_out else cols < 0
+                out[:, u] = torch.where(sent & torch.isfinite(logev)[:, None], torch.zeros((), dtype=out.dtype, device=dev), cols)
+            if return_choices:
+                self._keep = table
+        res = (out,)
+        if return_choices:
+            res += (choices,)
+        if return_log_evidence:
+            res += (logev,)
+        return res[0] if len(res) == 1 else res
+
+
 
 def sample(hc: "HipCircuit", num_samples: int, *, seed: int | None = None, return_choices: bool = False):
     """`HipCircuit.sample`: see its docstring."""
@@ -280,6 +396,15 @@ def sample(hc: "HipCircuit", num_samples: int, *, seed: int | None = None, retur
     if s is None:
         s = hc._sampler = Sampler(hc)
     return s.sample(num_samples, seed, return_choices)
+
+
+def sample_conditional(hc: "HipCircuit", x: torch.Tensor, sample_vars, *, seed: int | None = None,
+                       return_choices: bool = False, return_log_evidence: bool = False, rows_per_chunk: int | None = None):
+    """`HipCircuit.sample_conditional`: see its docstring."""
+    s = getattr(hc, "_sampler", None)
+    if s is None:
+        s = hc._sampler = Sampler(hc)
+    return s.sample_conditional(x, sample_vars, seed, return_choices, return_log_evidence, rows_per_chunk)
 
 
 class SamplingQuery:

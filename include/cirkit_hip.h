@@ -1136,6 +1136,23 @@ int ck_sample_cdf(const float* w, int64_t w_sf, int64_t w_sk, int64_t w_sm, int 
  * int64 values (x_float = 0) or fp32 (x_float != 0, required with a Gaussian layer); choices as the descriptors say. */
 int ck_sample_walk(const ck_sample_layer* layers, int n_layers, int root_fold, int root_unit, int total_folds, int S,
                    int64_t N, int D, uint64_t seed, void* x, int x_float, void* stream);
+/* Conditional sampling given evidence (ABI 50): rows row0 .. row0 + B - 1 of a batch of N rows each draw their unobserved
+ * variables from p(x_S | x_O) = c(x_O, x_S) / c(x_O).  Replaces the reference's symbolic/functional.py:75-135 `evidence`,
+ * which compiles a new circuit for ONE observation (and which its SamplingQuery then refuses as unnormalised,
+ * layers/inner.py:275-279); here every row carries its own evidence.  vals: the arena base of the layer-wise marginal forward
+ * of the chunk's evidence; val_off (total_folds) the element offset of global fold g's (B, Ko) block of per-row log values
+ * in it.  weights: a DEVICE array of n_layers pointers, the (F, Ko, M) LINEAR weights of each sum / mixing / CP-T / Tucker
+ * layer (NULL for the others).  A sum-type unit on a sample's tree draws entry i with mass w_i exp(v_i), v_i the entry's
+ * child value at the row (CP-T: summed over the inputs, Tucker: v0[a] + v1[b]); entries with w_i <= 0 add 0 and their child
+ * values are not read; the CDF row is built per (fold, sample) by one wave.  Input layers draw from the unconditional CDF
+ * rows / Gaussian parameters of the descriptors, and only where ev (B, D) holds the sentinel (int64: a negative category;
+ * fp32 with x_float != 0: NaN, or <= -1 for a discrete layer); observed entries of x are not written.  A row whose root value
+ * is not finite draws nothing.  x (B, D): the output, holding the evidence on entry.  choices: the descriptors' (F, N)
+ * tensors of the WHOLE batch, written at columns row0 .. row0 + B - 1.  Random numbers as ck_sample_walk, with n = row0 + the
+ * chunk row: the draws do not depend on the chunking. */
+int ck_sample_cond_walk(const ck_sample_layer* layers, const float* const* weights, int n_layers, int root_fold, int root_unit,
+                        int total_folds, int S, const float* vals, const int64_t* val_off, int64_t row0, int64_t B, int64_t N,
+                        int D, uint64_t seed, const void* ev, void* x, int x_float, void* stream);
 
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
