@@ -10,7 +10,7 @@ from typing import Any, Callable
 # CIRKIT_HIP_LIB: a lab build of the same library (scripts/lab_build.sh, scripts/defect_injection.sh); never a different backend
 _LIB_PATH = os.environ.get("CIRKIT_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libcirkit_hip.so")
 
-ABI_VERSION = 50
+ABI_VERSION = 51
 
 CK_SUM_CAT = 0
 CK_SUM_PROD = 1
@@ -311,6 +311,11 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_sample_cdf": [_p, _l, _l, _l, _i, _p, _l, _i, _i, _p, _p, _p],
     "ck_sample_walk": [_p, _i, _i, _i, _i, _i, _l, _i, C.c_uint64, _p, _i, _p],
     "ck_sample_cond_walk": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _l, _l, _l, _i, C.c_uint64, _p, _p, _i, _p],
+    "ck_mpe_input_max": [_i, _p, _l, _l, _l, _i, _i, _p, _p, _p, _l, _i, _p, _p, _p],
+    "ck_mpe_up_input": [_i, _p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _p, _l, _i, _p, _i, _l, _i, _p, _p, _i, _p, _p, _p],
+    "ck_mpe_up_sum": [_i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _i, _l, _p],
+    "ck_mpe_up_product": [_i, _p, _l, _i, _i, _i, _p, _p, _i, _l, _p],
+    "ck_mpe_walk": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l, _l, _l, _i, _p, _p, _i, _p, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],
     "ck_jobs_gauss_bwd": [_p, _i, _p, _i, _p, _p],
     "ck_opt_step_range": [_p, _p, _p, _p, _p, _l, _p, _p],

@@ -984,6 +984,32 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         return sample_conditional(self, x, sample_vars, seed=seed, return_choices=return_choices,
                                   return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
 
+    def mpe(self, x: torch.Tensor, query_vars, *, return_choices: bool = False, return_log_value: bool = False,
+            rows_per_chunk: int | None = None):
+        """Most probable completion of every row of ``x`` (B, D) under max-product, for output fold 0, unit 0 and any
+        circuit `sample` accepts (the same refusals).  The reference has no max semiring and no MAP / MPE query.
+
+        `query_vars` marks the variables to maximise over, in the forms ``integrate_vars`` takes (with the same errors); an
+        entry of ``x`` holding the sentinel (a negative category, NaN) is maximised too, every other entry is evidence and is
+        returned bit for bit.  Upward, a sum / mixing / CP-T / Tucker unit takes ``max_i (log w_i + v_i)`` over its entries
+        with ``w_i > 0``, a product unit adds its children's values, an input unit gives ``log p(x_v)`` where observed and
+        ``max_c log p(c)`` where maximised (a Gaussian: its value at the mean).  Downward, every unit on the row's induced tree
+        takes its argmax entry, the smallest index on ties; a maximised variable takes its unit's argmax category (smallest
+        index on ties) or the Gaussian mean.  On a deterministic circuit this is the exact MPE; on any other it is the
+        max-product approximation, and the returned value is only a LOWER BOUND of ``max_x log c(x_O, x)``.
+
+        Returns ``(B, D)`` on this device with the dtype rule of `sample`.  `return_choices`: also the ``(F, B)`` int32
+        choices of every sum-type layer, numbered as `sample` numbers them, -1 off the row's tree.  `return_log_value`: also
+        the ``(B,)`` fp32 max-product log value of the completion (unnormalised, like ``self(x)``).  A row whose evidence has
+        no finite mass keeps the sentinel in its query entries, gets -1 choices and a value of -inf (no exception, no
+        synchronisation); an out-of-range category is reported by `check_inputs` and its row's value is NaN, nothing written.
+        `rows_per_chunk`: rows per upward pass (None: its arena stays <= 2 GiB); results do not depend on it.  Results are in
+        the order: completion, choices, log value (cirkit_amd/mpe.py)."""
+        from .mpe import mpe
+
+        return mpe(self, x, query_vars, return_choices=return_choices, return_log_value=return_log_value,
+                   rows_per_chunk=rows_per_chunk)
+
     def log_likelihood_sum(self, x: torch.Tensor, out: torch.Tensor | None = None, *, reduce: bool = False) -> torch.Tensor:
         """Device tensor ``[sum_b log p(x_b), B]`` in fp64 -- the two numbers the data-parallel
         all-reduce exchanges (SURVEY.md section 8 e).  Requires a single scalar output.

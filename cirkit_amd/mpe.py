@@ -1,0 +1,195 @@
+"""Most probable explanation on the GPU: `HipCircuit.mpe` ("Most probable explanation").
+
+Given per-row evidence ``x_O``, the completion of the other variables that maximises the circuit under max-product: the
+upward pass evaluates every unit in the max-product ("Viterbi") semiring -- a sum-type unit takes ``max_i (log w_i + v_i)``
+over its entries with ``w_i > 0``, a product unit adds its children's values, an input unit gives ``log p(x_v)`` where
+``x_v`` is observed and ``max_c log p(c)`` where it is maximised -- and the walk follows, top down, the argmax entry of every
+unit on the row's induced tree (smallest index on ties).  On a deterministic circuit this is the exact MPE; otherwise it is
+the usual max-product approximation and its value a lower bound of ``max_x log c(x_O, x)``.
+
+The reference has no max semiring and no MAP / MPE query.  This module reuses the circuit's `Sampler`: its structure,
+descriptor table, choice maps and `prepare()`d weights; the log weights and the input layers' maxima are built here, per
+parameter state, on the first `mpe` call.  Kernels: cirkit_amd/csrc/ck_mpe.hip.
+"""
+
+from __future__ import annotations
+
+from typing import TYPE_CHECKING
+
+import numpy as np
+import torch
+
+from . import _capi as capi
+from .parameters import HipParameter
+from .sampling import Sampler, chunk_rows, fold_block_offsets
+
+if TYPE_CHECKING:  # pragma: no cover
+    from .circuit import HipCircuit
+
+_ALIGN = 64  # elements: every layer's (F, B, Ko) block of the arena starts on a 256-byte boundary
+
+
+class MPEState:
+    """The MPE state of one `HipCircuit`, next to its `Sampler`: the per-parameter-state tables and the upward arenas."""
+
+    def __init__(self, sampler: Sampler) -> None:
+        self.s = sampler
+        self.layers: list[dict] = [{} for _ in sampler.layers]
+        for t, d in zip(self.layers, sampler.layers):
+            if d["kind"] == capi.CK_SAMPLE_GAUSSIAN and "log_partition" in d["spec"].params:
+                t["lp"] = HipParameter(d["spec"].params["log_partition"], sampler.store)
+        self._key = None
+        self._logw_tab: torch.Tensor | None = None
+        self._amax_tab: torch.Tensor | None = None
+        self._arenas: dict[int, tuple[torch.Tensor, torch.Tensor, list[int]]] = {}  # rows -> (arena, val_off, bases)
+        sizes = [d["F"] * d["Ko"] for d in sampler.layers]
+        self.sizes_per_row = sizes
+        self.bytes_per_row = 4 * int(sum(sizes))
+
+    # -- once per parameter state ------------------------------------------------------------------------------------
+    def tables(self) -> None:
+        """Log weights of the sum-type layers and the maxima of the input layers for the store's current values."""
+        s = self.s
+        s.prepare()
+        if self._key == s._key:
+            return
+        dev = s.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            logw = np.zeros(len(s.layers), dtype=np.uint64)
+            amax = np.zeros(len(s.layers), dtype=np.uint64)
+            for j, (d, t) in enumerate(zip(s.layers, self.layers)):
+                F, Ko, M, kind = d["F"], d["Ko"], d["M"], d["kind"]
+                if "w" in d:  # sum / mixing / CP-T / Tucker: (F, Ko, M) linear weights evaluated by prepare()
+                    w = d["w"]
+                    t["lw"] = torch.where(w > 0, torch.log(w), torch.full((), float("-inf"), device=dev)).contiguous()
+                    logw[j] = t["lw"].data_ptr()
+                    continue
+                if kind not in (capi.CK_SAMPLE_CATEGORICAL, capi.CK_SAMPLE_GAUSSIAN):
+                    continue
+                t["vmax"] = torch.empty((F, Ko), dtype=torch.float32, device=dev)
+                t["amax"] = torch.empty((F, Ko), dtype=torch.int32, device=dev)
+                if kind == capi.CK_SAMPLE_GAUSSIAN:
+                    t["lp_v"] = t["lp"].evaluate(stream).reshape(F, Ko).contiguous().clone() if "lp" in t else None
+                    t["src"] = (None, 0, 0, 0, 0, 0)
+                    lp = t["lp_v"].data_ptr() if t["lp_v"] is not None else None
+                    capi.call("ck_mpe_input_max", kind, None, 0, 0, 0, 0, 0, d["mean_v"].data_ptr(), d["stddev_v"].data_ptr(),
+                              lp, F, Ko, t["vmax"].data_ptr(), t["amax"].data_ptr(), stream)
+                    continue
+                tab = d["tab"]  # prepare()'s table: Binomial (F, T + 2, K) log-pmf, Categorical (F, K, C) probs or logits
+                if d["spec"].type == "binomial":
+                    t["src"] = (tab, (M + 1) * Ko, 1, Ko, 1, M)
+                else:
+                    t["src"] = (tab, Ko * M, M, 1, 1 if d["is_logits"] else 0, M)
+                _, sf, sk, sc, t_log, C = t["src"]
+                capi.call("ck_mpe_input_max", kind, tab.data_ptr(), sf, sk, sc, t_log, C, None, None, None, F, Ko,
+                          t["vmax"].data_ptr(), t["amax"].data_ptr(), stream)
+                amax[j] = t["amax"].data_ptr()
+            self._logw_tab = torch.from_numpy(logw.view(np.int64)).to(dev)
+            self._amax_tab = torch.from_numpy(amax.view(np.int64)).to(dev)
+        self._key = s._key
+
+    # -- per chunk size ----------------------------------------------------------------------------------------------
+    def _arena(self, R: int) -> tuple[torch.Tensor, torch.Tensor, list[int]]:
+        hit = self._arenas.get(R)
+        if hit is None:
+            bases, total = [], 0
+            for n in self.sizes_per_row:
+                bases.append(total)
+                total += -(-n * R // _ALIGN) * _ALIGN
+            arena = torch.empty(total, dtype=torch.float32, device=self.s.device)
+            off = fold_block_offsets(bases, [d["F"] for d in self.s.layers], [d["Ko"] for d in self.s.layers], R)
+            hit = self._arenas[R] = (arena, torch.from_numpy(off).to(self.s.device), bases)
+        return hit
+
+    def _upward(self, xm: torch.Tensor, R: int, flag: torch.Tensor | None, bad: torch.Tensor, stream: int):
+        s = self.s
+        arena, val_off, _ = self._arena(R)
+        vals, vo = arena.data_ptr(), val_off.data_ptr()
+        x_float = 1 if s.float_out else 0
+        for j, (d, t) in enumerate(zip(s.layers, self.layers)):
+            F, H, Ki, Ko, M, kind, g0 = d["F"], d["H"], d["Ki"], d["Ko"], d["M"], d["kind"], int(s.fold_off[j])
+            if kind == capi.CK_SAMPLE_GAUSSIAN:
+                lp = t["lp_v"].data_ptr() if t["lp_v"] is not None else None
+                capi.call("ck_mpe_up_input", kind, d["scope"].data_ptr(), None, 0, 0, 0, 0, 0, d["mean_v"].data_ptr(),
+                          d["stddev_v"].data_ptr(), lp, t["vmax"].data_ptr(), F, Ko, xm.data_ptr(), x_float, R, s.D, vals, vo,
+                          g0, None if flag is None else flag.data_ptr(), bad.data_ptr(), stream)
+            elif kind == capi.CK_SAMPLE_CATEGORICAL:
+                tab, sf, sk, sc, t_log, C = t["src"]
+                capi.call("ck_mpe_up_input", kind, d["scope"].data_ptr(), tab.data_ptr(), sf, sk, sc, t_log, C, None, None, None,
+                          t["vmax"].data_ptr(), F, Ko, xm.data_ptr(), x_float, R, s.D, vals, vo, g0,
+                          None if flag is None else flag.data_ptr(), bad.data_ptr(), stream)
+            elif kind in (capi.CK_SAMPLE_HADAMARD, capi.CK_SAMPLE_KRONECKER):
+                capi.call("ck_mpe_up_product", kind, d["child"].data_ptr(), F, H, Ki, Ko, vals, vo, g0, R, stream)
+            else:
+                capi.call("ck_mpe_up_sum", kind, d["child"].data_ptr(), t["lw"].data_ptr(), F, H, Ki, Ko, M, vals, vo, g0, R,
+                          stream)
+        return arena, val_off
+
+    # -- once per call ------------------------------------------------------------------------------------------------
+    def mpe(self, x: torch.Tensor, query_vars, return_choices: bool = False, return_log_value: bool = False,
+            rows_per_chunk: int | None = None):
+        s = self.s
+        hc = s.hc
+        D = s.D
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise ValueError("The input to the circuit should have shape (B, D), where B is the batch size and D "
+                             "is the number of variables the circuit is defined on")
+        if x.shape[1] < D:
+            raise ValueError(f"expected at least {D} variables, found {x.shape[1]}")
+        B = int(x.shape[0])
+        if B <= 0:
+            raise ValueError("empty batch")
+        xm = hc._apply_integration_mask(x[:, :D].to(s.device), query_vars).to(s.dtype).contiguous()  # (its errors first)
+        chunks = chunk_rows(B, rows_per_chunk, self.bytes_per_row)
+        sizes = {nb for _, nb in chunks}
+        self.tables()
+        for r in [r for r in self._arenas if r not in sizes]:  # two arenas at most: the chunk and the tail
+            del self._arenas[r]
+        dev = s.device
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            out = xm.clone()  # (the sentinels mark what is left to fill)
+            logv = torch.empty(B, dtype=torch.float32, device=dev)
+            bad = torch.zeros(B, dtype=torch.int32, device=dev)
+            flag = hc._bad_input if hc.validate_inputs else None
+            table, choices = s._table, None
+            if return_choices:
+                desc = s._desc.copy()
+                choices = []
+                for j in s.sum_layers:
+                    c = torch.empty((s.layers[j]["F"], B), dtype=torch.int32, device=dev)
+                    desc[j]["choices"] = c.data_ptr()
+                    choices.append(c)
+                table = torch.from_numpy(desc.view(np.uint8).copy()).pin_memory().to(dev, non_blocking=True)
+            for r0, nb in chunks:
+                xc = xm[r0 : r0 + nb]
+                arena, val_off = self._upward(xc, nb, flag, bad[r0:], stream)
+                capi.call("ck_mpe_walk", table.data_ptr(), self._logw_tab.data_ptr(), self._amax_tab.data_ptr(), len(s.layers),
+                          s.root_fold, 0, s.total_folds, s.S, arena.data_ptr(), val_off.data_ptr(), bad.data_ptr(), r0, nb, B,
+                          D, xc.data_ptr(), out[r0].data_ptr(), 1 if s.float_out else 0, logv.data_ptr(), stream)
+            if s.zero_fill:  # variables outside every input layer's scope: 0, as `sample` writes, in rows with a completion
+                u = s.uncovered
+                cols = out[:, u]
+                sent = torch.isnan(cols) if s.float_out else cols < 0
+                out[:, u] = torch.where(sent & torch.isfinite(logv)[:, None], torch.zeros((), dtype=out.dtype, device=dev), cols)
+            if return_choices:
+                self._keep = table  # (the launches are asynchronous: the table outlives them until the next call)
+        res = (out,)
+        if return_choices:
+            res += (choices,)
+        if return_log_value:
+            res += (logv,)
+        return res[0] if len(res) == 1 else res
+
+
+def mpe(hc: "HipCircuit", x: torch.Tensor, query_vars, *, return_choices: bool = False, return_log_value: bool = False,
+        rows_per_chunk: int | None = None):
+    """`HipCircuit.mpe`: see its docstring."""
+    s = getattr(hc, "_sampler", None)
+    if s is None:
+        s = hc._sampler = Sampler(hc)
+    m = getattr(s, "_mpe", None)
+    if m is None:
+        m = s._mpe = MPEState(s)
+    return m.mpe(x, query_vars, return_choices, return_log_value, rows_per_chunk)

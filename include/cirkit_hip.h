@@ -1154,6 +1154,49 @@ int ck_sample_cond_walk(const ck_sample_layer* layers, const float* const* weigh
                         int total_folds, int S, const float* vals, const int64_t* val_off, int64_t row0, int64_t B, int64_t N,
                         int D, uint64_t seed, const void* ev, void* x, int x_float, void* stream);
 
+/* ---- most probable explanation (ABI 51) --------------------------------------------------------
+ * The max-product ("Viterbi") completion of every row: the variables where ev (B, D) holds the sentinel take the values of
+ * argmax_x c(x_O, x) under max-product, evidence entries are kept.  The reference has no counterpart: its semirings are
+ * sum-product, lse-sum and complex-lse-sum (cirkit/backend/torch/semiring.py) and its queries IntegrateQuery and
+ * SamplingQuery (queries.py).  Descriptors, unit numbering and choices are those of the sampling walk (ck_sample_layer).
+ * vals / val_off: an arena holding one (F, B, Ko) block per layer and the element offset of global fold g's (B, Ko) block,
+ * as ck_sample_cond_walk reads them; the upward launches write it, one per layer in plan order, and the walk reads it. */
+/* Per (fold, unit) of an input layer: vmax the largest log value over the categories, amax its SMALLEST index (type
+ * CK_SAMPLE_CATEGORICAL: the table read at tab + f sf + k sk + c sc, log-probabilities when t_log, else probabilities), or
+ * the Gaussian's log density at its mean plus log_partition (F, K) when not NULL (type CK_SAMPLE_GAUSSIAN, amax 0). */
+int ck_mpe_input_max(int type, const float* tab, int64_t sf, int64_t sk, int64_t sc, int t_log, int C, const float* mean,
+                     const float* stddev, const float* log_partition, int64_t F, int K, float* vmax, int32_t* amax,
+                     void* stream);
+/* Upward values of an input layer of global folds fold_off .. fold_off + F - 1 for the B rows of ev: log p(x) of an observed
+ * entry (table lookup, or the Gaussian's log density), vmax where ev holds the sentinel (int64: negative; fp32 with
+ * x_float != 0: NaN, or <= -1 for a discrete layer, which truncates the value).  An observed category outside 0 .. C - 1
+ * sets *flag |= 1 (flag may be NULL) and bad[n] = 1; its value is NaN. */
+int ck_mpe_up_input(int type, const int64_t* scope, const float* tab, int64_t sf, int64_t sk, int64_t sc, int t_log, int C,
+                    const float* mean, const float* stddev, const float* log_partition, const float* vmax, int64_t F, int K,
+                    const void* ev, int x_float, int64_t B, int D, float* vals, const int64_t* val_off, int fold_off,
+                    int32_t* flag, int32_t* bad, void* stream);
+/* Upward values of a sum / mixing (CK_SAMPLE_SUM, mixing as its block-diagonal (K, H K) weight), CP-T or Tucker (arity 2)
+ * layer: unit k of fold f at row n is max_i (lw[f, k, i] + v_i), v_i the entry's child value (ck_mpe_entry.h), lw (F, Ko, M)
+ * log weights with -inf for w <= 0.  Entries are taken two per v_max3_f32; a NaN entry is skipped. */
+int ck_mpe_up_sum(int type, const int32_t* child, const float* lw, int64_t F, int H, int Ki, int Ko, int M, float* vals,
+                  const int64_t* val_off, int fold_off, int64_t B, void* stream);
+/* Upward values of a Hadamard (unit k of every input) or Kronecker (the digits of k in base Ki, input 0 most significant)
+ * layer: the sum of the children's values. */
+int ck_mpe_up_product(int type, const int32_t* child, int64_t F, int H, int Ki, int Ko, float* vals, const int64_t* val_off,
+                      int fold_off, int64_t B, void* stream);
+/* The argmax walk of rows row0 .. row0 + B - 1 of a batch of N rows, S rows per workgroup as ck_sample_cond_walk.  logw: a
+ * DEVICE array of n_layers pointers, the (F, Ko, M) log weights of each sum-type layer (NULL for the others); amax: a DEVICE
+ * array of n_layers pointers, the (F, Ko) argmax categories of each Categorical / Binomial layer (NULL for the others).
+ * A sum-type unit on a row's tree takes the smallest entry index whose value equals the maximum; a maximised input entry
+ * takes its unit's argmax category or the Gaussian mean; observed entries of x are not written.  bad (N), logv (N) and the
+ * descriptors' (F, N) choices are indexed by the row of the whole batch: logv[n] is the root value (NaN where bad[n] != 0);
+ * a row whose root value is not finite, or with bad[n] != 0, takes nothing and gets -1 choices.  ev, x (B, D): the chunk's
+ * masked evidence and the output, holding the evidence on entry.  No randomness: results do not depend on the chunking. */
+int ck_mpe_walk(const ck_sample_layer* layers, const float* const* logw, const int32_t* const* amax, int n_layers,
+                int root_fold, int root_unit, int total_folds, int S, const float* vals, const int64_t* val_off,
+                const int32_t* bad, int64_t row0, int64_t B, int64_t N, int D, const void* ev, void* x, int x_float,
+                float* logv, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
