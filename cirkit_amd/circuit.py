@@ -16,6 +16,7 @@ with ~10 ATen launches per layer.
 
 from __future__ import annotations
 
+import itertools
 import os
 from typing import Mapping
 
@@ -38,7 +39,12 @@ _ALIGN = 64  # arena alignment of every layer block, in activation elements (>= 
 class _Binding:
     """Everything that depends on the batch size: arena, offset tables, recorded program."""
 
+    _serials = itertools.count(1)
+
     def __init__(self) -> None:
+        # never repeats: what a launch list recorded elsewhere over this binding's buffers is keyed on (a rebuilt binding can get
+        # its arena back at the same address while its staging copies, offset tables and [sum, count] pair have moved)
+        self.serial = next(_Binding._serials)
         self.B = 0
         self.arena: torch.Tensor | None = None
         self.views: list[torch.Tensor] = []

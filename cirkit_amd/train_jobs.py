@@ -409,10 +409,10 @@ class JobStep:
         tr, c = self.tr, self.c
         bd = c._bind(B)
         st = self._bound.get(B)
-        if st is not None and st["arena_ptr"] == bd.arena.data_ptr() and st["store_version"] == c.store.version:
+        if st is not None and st["serial"] == bd.serial and st["store_version"] == c.store.version:
             return st
-        if st is not None:
-            for pr in st["prog"].values():
+        if st is not None:  # (a rebuilt circuit binding: the recorded lists point at its old staging copies and [sum, count] pair)
+            for pr in self._bound.pop(B)["prog"].values():
                 pr.close()
         dev = c.device
         with torch.cuda.device(dev):
@@ -745,7 +745,7 @@ class JobStep:
             ra.seed_const, ra.R, ra.B, ra.mode, ra.n_wg, ra.S = 0.0, R, B, mode, n_wg, S_root
             return ra
 
-        st = {"arena_ptr": bd.arena.data_ptr(), "store_version": c.store.version, "keep": keep, "launches": launches,
+        st = {"serial": bd.serial, "store_version": c.store.version, "keep": keep, "launches": launches,
               "root": {1: root_args(1), 2: root_args(2)}, "pool": pool_d, "seed": seed, "seed_value": None, "extra": extra, "x0": x0,
               "prog": {}, "dT": {}}
         while len(self._bound) >= 4:

@@ -24,6 +24,7 @@ read by exactly one consumer (trees: what `squared_partition_plan` and the regio
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 from typing import Mapping
 
@@ -37,6 +38,10 @@ from .layers import (HipCategoricalLayer, HipConstantValueLayer, HipCPTLayer, Hi
                      HipSumLayer, HipTensorDotLayer, HipTuckerLayer)
 from .plan import Plan
 from .train_state import DeviceOptState, FlatBuffers, TrainerSurface
+
+# serial numbers of the per-batch-size states of c and Z (never repeated): the recorded launch lists of `HipSquaredTrainer` point at
+# their buffers and are keyed on them -- a rebuilt state can get its arena back at the old address while its other buffers moved
+_state_serials = itertools.count(1)
 
 
 class _PlanBackward:
@@ -84,7 +89,7 @@ class _PlanBackward:
     def _bind(self, B: int) -> dict:
         bd = self.c._bind(B)
         st = self._bound.get(B)
-        if st is not None and st["arena_ptr"] == bd.arena.data_ptr():
+        if st is not None and st["binding"] == bd.serial:
             return st
         dev = bd.arena.device
         cplx = self.cplx
@@ -132,7 +137,8 @@ class _PlanBackward:
                 if not l.log_space:
                     sc["dv"] = f32(F, K)
             scratch[i] = sc
-        st = {"arena_ptr": bd.arena.data_ptr(), "garena": garena, "gviews": gviews, "scratch": scratch, "pool": None}
+        st = {"binding": bd.serial, "serial": next(_state_serials), "garena": garena, "gviews": gviews, "scratch": scratch, "pool": None}
+        self._bound.pop(B, None)
         while len(self._bound) >= 4:
             self._bound.pop(next(iter(self._bound)))
         self._bound[B] = st
@@ -215,10 +221,10 @@ class _PlanBackward:
         e = 2 if cplx else 1
         esz = 4 * e
         po, fo = int(c._out_pairs[0, 0]), int(c._out_pairs[0, 1])
-        if st.get("seed_key") != float(seed_real):  # (the output layer's gradient is read, never written: once per binding and seed)
-            capi.call("ck_fill_f32", gviews[po].data_ptr(), gviews[po].numel() * e, 0.0, stream)
-            capi.call("ck_fill_strided_f32", gviews[po][fo].data_ptr(), B, e, float(seed_real), stream)  # (Re = seed, Im = 0)
-            st["seed_key"] = float(seed_real)
+        # the output layer's gradient: filled on every run, so a recorded list carries the seed of its own (B, global batch) key --
+        # lists of several keys share this block (c at one B with two global batches; Z, whose B = 1, under any B / global batch)
+        capi.call("ck_fill_f32", gviews[po].data_ptr(), gviews[po].numel() * e, 0.0, stream)
+        capi.call("ck_fill_strided_f32", gviews[po][fo].data_ptr(), B, e, float(seed_real), stream)  # (Re = seed, Im = 0)
         ga, aa = garena.data_ptr(), bd.arena.data_ptr()
         pool = self._weight_pool(st)
         if not pool_zeroed:
@@ -491,6 +497,7 @@ class _SignedCircuit:
                 n += c.layers[i].num_folds * Bp * 32  # (a 1 .. 4 unit layer: rows of Ko floats at the start of its block)
         po, fo = int(c._out_pairs[0, 0]), int(c._out_pairs[0, 1])
         st = {
+            "serial": next(_state_serials),
             "arena": torch.zeros(max(n, 32), dtype=torch.float32, device=dev),
             "signs": torch.zeros(max(n // 32, 1), dtype=torch.int32, device=dev),
             "garena": torch.zeros(max(n, 32), dtype=torch.float32, device=dev),
@@ -665,11 +672,10 @@ class _SignedCircuit:
         c, st = self.c, self.bind(B)
         a, sg, ga = st["arena"].data_ptr(), st["signs"].data_ptr(), st["garena"].data_ptr()
         po, fo = int(c._out_pairs[0, 0]), int(c._out_pairs[0, 1])
-        if st.get("seed_key") != float(seed):  # (nobody writes this block: filled once per binding and seed, outside the recorded lists)
-            if c.layers[po].num_folds > 1:
-                capi.call("ck_fill_f32", st["seed"].data_ptr(), st["seed"].numel(), 0.0, stream)
-            capi.call("ck_fill_f32", st["seed"].data_ptr() + 4 * fo * B, B, float(seed), stream)
-            st["seed_key"] = float(seed)
+        # (filled on every run, inside the recorded list: the lists of one binding at two global batches share this block)
+        if c.layers[po].num_folds > 1:
+            capi.call("ck_fill_f32", st["seed"].data_ptr(), st["seed"].numel(), 0.0, stream)
+        capi.call("ck_fill_f32", st["seed"].data_ptr() + 4 * fo * B, B, float(seed), stream)
         for i in reversed(list(self.kind)):
             l, k = c.layers[i], self.kind[i]
             if k == "emb":
@@ -784,15 +790,17 @@ class HipSquaredTrainer(TrainerSurface):
         (alone) the optimizer ("mid": the clock and the pair, as soon as both forwards are there) -- per (batch size, global batch): the first two
         calls run eagerly (they size the scratch of the parameter graphs), the third records, later ones replay (as a hipGraph
         when `use_graph`)."""
-        c_arena = self._signed.bind(B)["arena"] if self._signed is not None else self.c._bind(B).arena
-        key = (part, B, float(gB), bool(with_optimizer), c_arena.data_ptr(), self.z._bind(1).arena.data_ptr())
+        # (the lists point at the buffers of c's and Z's states at this batch size -- and, through them, of the circuits' bindings --:
+        #  keyed on their serial numbers, never on an address a rebuilt state can get back)
+        c_state = self._signed.bind(B) if self._signed is not None else self._bwd_c._bind(B)
+        key = (part, B, float(gB), bool(with_optimizer), c_state["serial"], self._bwd_z._bind(1)["serial"])
         prog, seen = self._programs.get(key, (None, 0))
         if prog is None:
             if seen < 2:
                 self._enqueue(part, B, gB, with_optimizer, run.cuda_stream)
                 self._programs[key] = (None, seen + 1)
                 return
-            for k in [k for k in self._programs if k[:4] == key[:4] and k != key]:  # (rebound arenas: their lists are stale)
+            for k in [k for k in self._programs if k[:4] == key[:4] and k != key]:  # (rebuilt states: their lists are stale)
                 if self._programs[k][0] is not None:
                     self._programs[k][0].close()
                 del self._programs[k]
