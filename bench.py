@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: log-likelihood evaluations / second of the folded log-space forward.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
 
 Workload (BASELINE.json configs[1]; configs[2] at N=8): 784-variable QuadTree-2 circuit,
 Categorical-256 inputs, CP sum layers, K=32, fp32, batch 4096 PER GPU (weak scaling), synthetic
@@ -15,7 +15,10 @@ timed region is one round of exactly K steps between barrier + synchronize (`--r
 is reported); `--settle` untimed steps precede every timed region, because the device keeps speeding up over its first
 ~50 ms of work -- `timing` lists every round.  `--dump-outputs DIR` writes what the last timed step returned (.npy).
 
-Prints ONE JSON line on rank 0 (contract in the task description), with
+A plain run sets up, warms up, times its steps, writes its outputs and prints ONE JSON line on rank 0: the headline fields,
+`config`, `timing`, `distributed`, `check` (mean LL of the last step) and `roofline.forward` (the step by algorithmic bytes,
+from the timed region itself).  `--full` also runs everything measured beside the headline figure (each part can still be
+skipped by its `--no-*` switch), and the line then carries
   roofline     -- the dominant kernel (by HIP-event time per launch, measured here): the contraction flops it EXECUTES
                   against the dense fp32-input MFMA peak (157.3 TFLOP/s), or its measured HBM bytes against 8 TB/s,
                   whichever binds; `traffic` / `mfma_busy_frac` from three short rocprofv3 counter passes run by this
@@ -24,7 +27,9 @@ Prints ONE JSON line on rank 0 (contract in the task description), with
                   algorithmic bytes (SURVEY.md section 8 d); `roofline.algorithmic` = the same convention per launch;
   check        -- mean LL of the last step and the max relative error of 64 rows against the CPU oracle;
   cpu_baseline -- the CPU oracle (op-for-op port of the reference's torch-CPU path) timed on the
-                  host cores of this box on a bounded sample (rank 0, N = 1 only); host core count and CPU model stated.
+                  host cores on a bounded sample (rank 0, at any N); host core count and CPU model stated;
+  variants     -- the same circuit cached / with its parameters at the start / on bf16 pieces / on two streams (N = 1);
+  other_configs -- BASELINE configs 4 and 5, the notebook Tucker configuration and four training steps (N = 1).
 """
 
 from __future__ import annotations
@@ -79,7 +84,8 @@ def bench_summary(result: dict) -> dict:
 
     roof = result.get("roofline") or {}
     s = {
-        "cfg2_fwd": {"ms": round(float(result["ms_per_step"]), 4), "mfma": (round(float(roof["frac"]), 3) if roof.get("frac") is not None else None)},
+        "cfg2_fwd": {"ms": round(float(result["ms_per_step"]), 4),
+                     "mfma": (round(float(roof["frac"]), 3) if roof.get("frac") is not None and roof.get("bound") == "mfma" else None)},
         "cfg4_fwd": pick(oc.get("config4"), "ms_per_forward"),
         "cfg5_fwd": pick(oc.get("config5"), "ms_per_forward"),
         "cfg5_Z": ({"ms": round(float(oc["config5"]["ms_partition_function"]), 4)} if "config5" in oc else None),
@@ -538,6 +544,10 @@ def main() -> None:
     ap.add_argument("--no-graph", action="store_true", help="never replay as a hipGraph (only lists of more than 64 launches are by default)")
     ap.add_argument("--fuse", type=int, default=-1, help="-1: full leaf fusion (default), 0: layer-wise, n: n CP-T levels")
     ap.add_argument("--contraction", default="f32", choices=["f32"], help="K=32 sum layers: exact fp32 MFMA (the only form)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel breakdown and live rocprofv3 "
+                         "counter passes behind `roofline`, the CPU oracle (`cpu_baseline`, `check.max_rel_err_vs_oracle`), "
+                         "`variants` and `other_configs`.  Off by default; the --no-* switches below skip parts of it")
     ap.add_argument("--no-variants", action="store_true", help="skip the secondary measurements (cached parameters, parameters at the start, two streams)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short measurements of BASELINE configs 4 and 5 (never part of `value`)")
@@ -570,6 +580,8 @@ def main() -> None:
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-steps", type=int, default=12, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure and nothing that takes runs of its own
+        args.no_variants = args.no_other_configs = args.no_cpu_baseline = args.no_kernel_breakdown = args.no_live_pmc = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as invoked by hand / by the driver: become the launcher -- one rank per GPU under

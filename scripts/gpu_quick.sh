@@ -8,11 +8,10 @@ if [ -n "$K" ]; then
   grep -v "^  File\|^Extension modules" gpurun_out/pytest.log | head -60
   tail -5 gpurun_out/pytest.log
 fi
-python bench.py --no-variants --no-other-configs --no-cpu-baseline "$@" > gpurun_out/bq.json 2> gpurun_out/bq.err
-tail -c 400 gpurun_out/bq.err
-python - <<'PY'
-import json
-d = json.load(open("gpurun_out/bq.json"))
+LINE=$(python bench.py --full --no-variants --no-other-configs --no-cpu-baseline "$@" | tail -1)
+python - "$LINE" <<'PY'
+import json, sys
+d = json.loads(sys.argv[1])
 print("value", round(d["value"]), "ms_per_step", round(d["ms_per_step"], 5), "launches", d["config"]["launches_per_step"],
       "raw", d["config"].get("leaf_reads_raw_batch"))
 print({k: round(1e3 * v["ms_per_step"], 2) for k, v in d["roofline"].get("kernels", {}).items()})

@@ -4,8 +4,8 @@
 #     bash scripts/profile_round.sh r02 [tag]
 #
 # Writes into gpurun_out/<round>/ (scratch; copy what is to be judged into profiles/):
-#   <round>_<tag>_bench.json      the line printed by `python bench.py` (all defaults)
-#   <round>_<tag>_bench.txt       kernel trace of `bench.py --no-cpu-baseline --no-other-configs --no-variants --no-live-pmc`
+#   <round>_<tag>_bench.json      the line printed by `python bench.py --full` (all other defaults)
+#   <round>_<tag>_bench.txt       kernel trace of `bench.py --full --no-cpu-baseline --no-other-configs --no-variants --no-live-pmc`
 #                                 + one PMC pass per counter (FETCH_SIZE, WRITE_SIZE, SQ_VALU_MFMA_BUSY_CYCLES, SQ_BUSY_CYCLES)
 #   traffic_<tag>.json            scripts/make_traffic_json.py entry of the FETCH/WRITE passes
 # Counters are collected in their own runs, with --kernel-trace only (never with a sys/hip/hsa trace).
@@ -16,10 +16,10 @@ OUT=gpurun_out/$ROUND
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 PY=python
-QUIET="--no-cpu-baseline --no-other-configs --no-variants --no-live-pmc"
+QUIET="--full --no-cpu-baseline --no-other-configs --no-variants --no-live-pmc"
 PMCARGS="--steps 10 --warmup 2 --rounds 1 --no-cpu-baseline --no-kernel-breakdown --no-variants --no-other-configs --no-live-pmc"
 
-$PY bench.py > "$OUT/${ROUND}_${TAG}_bench.json" 2> "$OUT/${ROUND}_${TAG}_bench.err"
+$PY bench.py --full > "$OUT/${ROUND}_${TAG}_bench.json" 2> "$OUT/${ROUND}_${TAG}_bench.err"
 tail -1 "$OUT/${ROUND}_${TAG}_bench.json"
 
 rocprofv3 --kernel-trace --stats -d "$OUT/trace_$TAG" -o trace -- $PY bench.py $QUIET > "$OUT/trace_$TAG.log" 2>&1

@@ -108,7 +108,7 @@ def test_bench_four_ranks_carry_baseline_config_3_batch(hip_device):
     # (the N > 1 line is as complete as the N = 1 line -- rank 0 times the CPU oracle, checks 64 rows against it
     #  and fills `roofline` from its own instrumented pass while the other ranks wait at the closing barrier)
     args = [a for a in BENCH_ARGS if a not in ("--no-cpu-baseline", "--no-kernel-breakdown")]
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--batch", "8192", *args]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--batch", "8192", "--full", *args]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     d = _one_json_line(out)
     assert d["config"]["global_batch"] == 32768
@@ -127,7 +127,7 @@ def test_bench_two_ranks_with_live_counter_passes(hip_device):
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     args = [a for a in BENCH_ARGS if a not in ("--no-kernel-breakdown", "--no-live-pmc")]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29619", os.path.join(ROOT, "bench.py"), "--gpus", "2", *args]
+           "--master-port", "29619", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", *args]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     d = _one_json_line(out)
     _check_two_ranks(d, hip_device)
@@ -222,12 +222,12 @@ def test_trainer_gradient_all_reduce_through_rccl(hip_device, tmp_path):
 
 
 def test_bench_line_carries_the_contract(hip_device):
-    """`python bench.py` (N = 1, short): ONE JSON line with the fields the driver reads -- metric / value / unit / n_gpus / steps /
+    """`python bench.py --full` (N = 1, short): ONE JSON line with the fields the driver reads -- metric / value / unit / n_gpus / steps /
     warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload -- plus `roofline` (dominant
     kernel: bound, achieved, peak, unit, frac, traffic) and `cpu_baseline` (value, unit, cores, kind, sample); value = rows / time."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "BENCH_DIST_BACKEND")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--settle", "20", "--rounds", "2",
-           "--no-variants", "--no-other-configs", "--no-live-pmc"]
+           "--full", "--no-variants", "--no-other-configs", "--no-live-pmc"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _one_json_line(out)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -264,3 +264,27 @@ def test_bench_steps_are_the_timed_steps_and_outputs_are_dumped(hip_device, tmp_
     assert pair[1] == B and d["check"]["mean_ll"] == pair[0] / pair[1]
     tot = _expected_last_step(hip_device, 1, rounds=1)
     assert abs(pair[0] - tot[0].item()) <= 1e-9 * abs(tot[0].item())
+
+
+def test_plain_bench_line_is_lean(hip_device, tmp_path):
+    """`python bench.py` without `--full`: the headline fields and the outputs of the timed steps, and none of the measurements
+    that take runs of their own (CPU oracle, per-kernel pass, counter passes, variants, other configurations)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "BENCH_DIST_BACKEND")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(STEPS), "--warmup", str(WARMUP),
+           "--settle", "0", "--batches", str(NB), "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    d = _one_json_line(out)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "check"):
+        assert k in d, k
+    assert d["steps"] == STEPS and d["warmup"] == WARMUP and d["steps_timed_total"] == STEPS
+    assert d["unit"] == "evals/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - B / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("cpu_baseline", "other_configs"):
+        assert k not in d, k
+    assert not d.get("variants") and "max_rel_err_vs_oracle" not in d["check"]
+    r = d["roofline"]
+    assert r["kernel"] == "forward program" and "kernels" not in r and r["forward"]["avg_ms"] > 0
+    assert d["summary"]["cfg2_fwd"]["mfma"] is None  # (the algorithmic-bytes fraction is no MFMA figure)
+    pair = np.load(tmp_path / "out" / "ll_sum_count.npy")
+    tot = _expected_last_step(hip_device, 1, rounds=1)
+    assert pair[1] == B and abs(pair[0] - tot[0].item()) <= 1e-9 * abs(tot[0].item())
