@@ -4,8 +4,7 @@
 // is observed and max_c log p(c) where it is maximised.  The walk picks the smallest entry index among the maxima.
 #include <math.h>
 
-#include "ck_internal.h"
-#include "ck_mpe_entry.h"
+#include "ck_walk.h"
 
 namespace {
 
@@ -13,8 +12,6 @@ constexpr int kUpThreads = 256;
 constexpr int kRM = 4;   // rows of a thread's register micro-tile
 constexpr int kKM = 4;   // units of a thread's register micro-tile
 constexpr int kMC = 16;  // entries staged in LDS per step
-constexpr int kWalkThreads = 1024;  // 16 waves, as the conditional walk
-constexpr int kWalkWaves = kWalkThreads / ck::kWave;
 
 // ---- per-parameter-state input tables ------------------------------------------------------------------------------
 // Per (fold, unit): the largest log value over the categories and its smallest index (a Categorical / Binomial table read at
@@ -62,21 +59,15 @@ __global__ void __launch_bounds__(256)
   const int64_t n = rest % B, f = rest / B;
   const int64_t o = f * K + k;
   const int64_t e_at = n * D + scope[f];
-  float v;
-  if (type == CK_SAMPLE_GAUSSIAN) {
-    const float x = static_cast<const float*>(ev)[e_at];
-    v = isnan(x) ? vmax[o] : ck::mpe_gauss(x, mean[o], stddev[o], lz, o);
+  float v, x = 0.f;
+  int64_t c = 0;
+  if (!ck::observed(ev, e_at, x_float, type == CK_SAMPLE_GAUSSIAN, x, c)) {
+    v = vmax[o];
+  } else if (type == CK_SAMPLE_GAUSSIAN) {
+    v = ck::mpe_gauss(x, mean[o], stddev[o], lz, o);
   } else {
-    int64_t c;
-    if (x_float) {
-      const float x = static_cast<const float*>(ev)[e_at];
-      c = !(x > -1.f) ? -1 : (x >= static_cast<float>(C) ? C : static_cast<int64_t>(x));
-    } else {
-      c = static_cast<const int64_t*>(ev)[e_at];
-    }
-    if (c < 0) {
-      v = vmax[o];
-    } else if (c >= C) {
+    if (x_float) c = x >= static_cast<float>(C) ? C : static_cast<int64_t>(x);
+    if (c >= C) {
       v = NAN;
       if (k == 0) {
         bad[n] = 1;
@@ -122,7 +113,7 @@ __global__ void __launch_bounds__(kUpThreads)
     for (int t = threadIdx.x; t < TR * kMC; t += kUpThreads) {
       const int m = t % kMC, r = t / kMC;
       float e = 0.f;  // (padding entries: 0 under a log weight of -inf)
-      if (m0 + m < M && n0 + r < B) e = ck::mpe_entry(type, ch, H, Ki, vals, val_off, n0 + r, m0 + m);
+      if (m0 + m < M && n0 + r < B) e = ck::entry_value(type, ch, H, Ki, vals, val_off, n0 + r, m0 + m);
       sEf[m * EP + r] = e;
     }
     for (int t = threadIdx.x; t < TK * kMC; t += kUpThreads) {
@@ -181,121 +172,50 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---- argmax walk ---------------------------------------------------------------------------------------------------
-// One workgroup owns S consecutive rows of the chunk; sel[g * S + s] is the unit of global fold g on row s's tree (-1: off
-// the tree), as in the conditional walk (ck_sample_cond.hip).  A sum-type unit on a tree is one wave: 64 entries at a time
-// through the shared entry helper, a wave max, and the first lane of the ballot of the entries equal to it.
-__global__ void __launch_bounds__(kWalkThreads)
-    mpe_walk_kernel(const ck_sample_layer* __restrict__ layers, const float* const* __restrict__ logw,
-                    const int32_t* const* __restrict__ amax, int n_layers, int root_fold, int root_unit, int total_folds, int S,
-                    const float* __restrict__ vals, const int64_t* __restrict__ val_off, const int32_t* __restrict__ bad,
-                    int64_t row0, int64_t B, int64_t N, int D, const void* __restrict__ ev, void* __restrict__ x, int x_float,
-                    float* __restrict__ logv) {
-  extern __shared__ int16_t sel[];
-  const int64_t b0 = static_cast<int64_t>(blockIdx.x) * S;
-  const int ns = static_cast<int>(B - b0 < S ? B - b0 : S);
-  const int lane = threadIdx.x & (ck::kWave - 1);
-  const int wave = threadIdx.x / ck::kWave;
-  for (int i = threadIdx.x; i < total_folds * S; i += blockDim.x) sel[i] = -1;
-  int root_ko = 0;
-  for (int j = 0; j < n_layers; ++j) {
-    if (root_fold >= layers[j].fold_off && root_fold < layers[j].fold_off + layers[j].F) root_ko = layers[j].Ko;
-  }
-  __syncthreads();
-  for (int s = threadIdx.x; s < ns; s += blockDim.x) {  // rows without finite mass, and rows with bad evidence, stay empty
-    const int64_t n = row0 + b0 + s;
-    const float r = vals[val_off[root_fold] + (b0 + s) * root_ko + root_unit];
+// The walk policy of MPE (ck::evidence_walk_kernel): rows without finite mass, and rows with bad evidence, stay empty, and
+// logv[n] gets the root value (NaN where bad[n]); a sum-type unit on a tree is one wave: 64 entries at a time through the
+// shared entry helper, a wave max, and the first lane of the ballot of the entries equal to it; an unobserved input takes
+// its unit's argmax category or the Gaussian mean.
+struct MpeArgmax {
+  const int32_t* const* amax;
+  const int32_t* bad;
+  float* logv;
+
+  __device__ bool root(int64_t n, float r) const {
     const bool b = bad[n] != 0;
     logv[n] = b ? NAN : r;
-    if (!b && isfinite(r)) sel[root_fold * S + s] = static_cast<int16_t>(root_unit);
+    return !b && isfinite(r);
   }
-  __syncthreads();
-  for (int li = n_layers - 1; li >= 0; --li) {
-    const ck_sample_layer& L = layers[li];
-    if (L.type == CK_SAMPLE_SUM || L.type == CK_SAMPLE_CPT || L.type == CK_SAMPLE_TUCKER) {
-      const float* __restrict__ W = logw[li];
-      for (int it = wave; it < L.F * ns; it += kWalkWaves) {  // (wave-uniform)
-        const int f = it / ns, s = it % ns;
-        const int64_t nl = b0 + s, n = row0 + nl;
-        const int k = sel[(L.fold_off + f) * S + s];
-        const int32_t* ch = L.child + static_cast<int64_t>(f) * L.H;
-        int choice = -1;
-        if (k >= 0 && k < L.Ko) {
-          const float* wr = W + (static_cast<int64_t>(f) * L.Ko + k) * L.M;
-          float best = -INFINITY;
-          for (int m0 = 0; m0 < L.M; m0 += ck::kWave) {
-            const int i = m0 + lane;
-            float v = -INFINITY;
-            if (i < L.M) {
-              const float lwi = wr[i];
-              if (lwi != -INFINITY) v = ck::mpe_term(lwi, ck::mpe_entry(L.type, ch, L.H, L.Ki, vals, val_off, nl, i));
-              if (isnan(v)) v = -INFINITY;
-            }
-            const float cm = ck::wave_max(v);
-            if (cm > best) {  // strict: an earlier block keeps a tie
-              best = cm;
-              choice = m0 + __ffsll(static_cast<unsigned long long>(__ballot(v == cm))) - 1;
-            }
-          }
-        }
-        if (lane == 0) {
-          if (choice >= 0) {
-            if (L.type == CK_SAMPLE_SUM) {
-              sel[ch[choice / L.Ki] * S + s] = static_cast<int16_t>(choice % L.Ki);
-            } else if (L.type == CK_SAMPLE_CPT) {
-              for (int h = 0; h < L.H; ++h) sel[ch[h] * S + s] = static_cast<int16_t>(choice);
-            } else {
-              sel[ch[0] * S + s] = static_cast<int16_t>(choice / L.Ki);
-              sel[ch[1] * S + s] = static_cast<int16_t>(choice % L.Ki);
-            }
-          }
-          if (L.choices != nullptr)
-            L.choices[static_cast<int64_t>(f) * N + n] = choice < 0 ? -1 : (L.cmap != nullptr ? L.cmap[choice] : choice);
-        }
+
+  __device__ int choose(const ck_sample_layer& L, const float* __restrict__ wr, const int32_t* __restrict__ ch,
+                        const float* __restrict__ vals, const int64_t* __restrict__ val_off, int64_t nl, int64_t, int,
+                        int lane) const {
+    int choice = -1;
+    float best = -INFINITY;
+    for (int m0 = 0; m0 < L.M; m0 += ck::kWave) {
+      const int i = m0 + lane;
+      float v = -INFINITY;
+      if (i < L.M) {
+        const float lwi = wr[i];
+        if (lwi != -INFINITY) v = ck::mpe_term(lwi, ck::entry_value(L.type, ch, L.H, L.Ki, vals, val_off, nl, i));
+        if (isnan(v)) v = -INFINITY;
       }
-      __syncthreads();
-      continue;
+      const float cm = ck::wave_max(v);
+      if (cm > best) {  // strict: an earlier block keeps a tie
+        best = cm;
+        choice = m0 + __ffsll(static_cast<unsigned long long>(__ballot(v == cm))) - 1;
+      }
     }
-    const int items = L.F * ns;
-    const bool input = L.type == CK_SAMPLE_CATEGORICAL || L.type == CK_SAMPLE_GAUSSIAN;
-    for (int it = threadIdx.x; it < items; it += blockDim.x) {
-      const int f = input ? it % L.F : it / ns;
-      const int s = input ? it / L.F : it % ns;
-      const int64_t nl = b0 + s;
-      const int k = sel[(L.fold_off + f) * S + s];
-      if (k < 0 || k >= L.Ko) continue;
-      const int32_t* ch = L.child + static_cast<int64_t>(f) * L.H;
-      if (L.type == CK_SAMPLE_HADAMARD) {
-        for (int h = 0; h < L.H; ++h) sel[ch[h] * S + s] = static_cast<int16_t>(k);
-        continue;
-      }
-      if (L.type == CK_SAMPLE_KRONECKER) {
-        int r = k;
-        for (int h = L.H - 1; h >= 0; --h) {
-          sel[ch[h] * S + s] = static_cast<int16_t>(r % L.Ki);
-          r /= L.Ki;
-        }
-        continue;
-      }
-      // input layers write only maximised entries (the output starts as a copy of the masked evidence)
-      const int64_t o = nl * D + L.scope[f];
-      if (x_float) {
-        const float e = static_cast<const float*>(ev)[o];
-        if (L.type == CK_SAMPLE_GAUSSIAN ? !isnan(e) : e > -1.f) continue;
-      } else if (static_cast<const int64_t*>(ev)[o] >= 0) {
-        continue;
-      }
-      const int64_t u = static_cast<int64_t>(f) * L.Ko + k;
-      if (L.type == CK_SAMPLE_GAUSSIAN) {
-        if (x_float) static_cast<float*>(x)[o] = L.mean[u];
-        continue;
-      }
-      const int c = amax[li][u];
-      if (x_float) static_cast<float*>(x)[o] = static_cast<float>(c);
-      else static_cast<int64_t*>(x)[o] = c;
-    }
-    __syncthreads();
+    return choice;
   }
-}
+
+  __device__ void fill(const ck_sample_layer& L, int li, int f, int k, int64_t, int, void* __restrict__ x, int x_float,
+                       int64_t o) const {
+    const int64_t u = static_cast<int64_t>(f) * L.Ko + k;
+    if (L.type == CK_SAMPLE_GAUSSIAN) ck::store_value(x, x_float, o, L.mean[u]);
+    else ck::store_category(x, x_float, o, amax[li][u]);
+  }
+};
 
 int64_t blocks_of(int64_t items, int threads) { return (items + threads - 1) / threads; }
 
@@ -391,23 +311,7 @@ int ck_mpe_walk(const ck_sample_layer* layers, const float* const* logw, const i
                 int root_fold, int root_unit, int total_folds, int S, const float* vals, const int64_t* val_off,
                 const int32_t* bad, int64_t row0, int64_t B, int64_t N, int D, const void* ev, void* x, int x_float,
                 float* logv, void* stream) {
-  CK_REQUIRE(layers != nullptr && logw != nullptr && amax != nullptr && vals != nullptr && val_off != nullptr &&
-                 bad != nullptr && ev != nullptr && x != nullptr && logv != nullptr,
-             "ck_mpe_walk: null pointer");
-  CK_REQUIRE(n_layers > 0 && total_folds > 0 && B > 0 && D > 0 && S > 0, "ck_mpe_walk: non-positive size");
-  CK_REQUIRE(row0 >= 0 && row0 + B <= N, "ck_mpe_walk: rows %lld .. %lld outside the %lld rows of the batch",
-             static_cast<long long>(row0), static_cast<long long>(row0 + B), static_cast<long long>(N));
-  CK_REQUIRE(root_fold >= 0 && root_fold < total_folds && root_unit >= 0 && root_unit < 32768, "ck_mpe_walk: root out of range");
-  const int64_t lds = static_cast<int64_t>(total_folds) * S * 2;
-  CK_REQUIRE(lds <= CK_SAMPLE_MAX_LDS, "ck_mpe_walk: %d folds x %d rows exceed the LDS budget", total_folds, S);
-  const int64_t blocks = (B + S - 1) / S;
-  CK_REQUIRE(blocks <= 0x7fffffff, "ck_mpe_walk: too many rows");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(mpe_walk_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kWalkThreads), static_cast<size_t>(lds),
-                           s, layers, logw, amax, n_layers, root_fold, root_unit, total_folds, S, vals, val_off, bad, row0, B, N,
-                           D, ev, x, x_float, logv);
-        return hipGetLastError();
-      },
-      stream);
+  CK_REQUIRE(amax != nullptr && bad != nullptr && logv != nullptr, "ck_mpe_walk: null pointer");
+  return ck::evidence_walk("ck_mpe_walk", layers, logw, n_layers, root_fold, root_unit, total_folds, S, vals, val_off, row0,
+                           B, N, D, ev, x, x_float, MpeArgmax{amax, bad, logv}, stream);
 }

@@ -3,8 +3,7 @@
 #include <math.h>
 
 #include "ck_internal.h"
-#include "ck_philox.h"
-#include "ck_sample_draw.h"
+#include "ck_walk.h"
 
 namespace {
 
@@ -69,76 +68,35 @@ __global__ void __launch_bounds__(kCdfRowsPerBlock * ck::kWave)
   if (bad) atomicOr(flag, bad);
 }
 
-// One workgroup owns `S` consecutive samples; sel[g * S + s] = the unit of global fold g on sample s's induced tree, -1 if g
-// is not on it.  Layers are walked from the last to the first; a fold writes the units of its children, which belong to
-// earlier layers, so one barrier per layer orders the walk.
+// One workgroup owns `S` consecutive samples (the sel table and layer order of ck_walk.h); every item is one thread, a draw
+// from a CDF row prepared once per parameter state.
 __global__ void __launch_bounds__(kWalkThreads)
     sample_walk_kernel(const ck_sample_layer* __restrict__ layers, int n_layers, int root_fold, int root_unit, int total_folds,
                        int S, int64_t N, int D, uint32_t key0, uint32_t key1, void* __restrict__ x, int x_float) {
   extern __shared__ int16_t sel[];
   const int64_t n0 = static_cast<int64_t>(blockIdx.x) * S;
   const int ns = static_cast<int>(N - n0 < S ? N - n0 : S);
-  for (int i = threadIdx.x; i < total_folds * S; i += blockDim.x) sel[i] = -1;
+  ck::walk_init(sel, total_folds, S, layers, n_layers, root_fold);
   __syncthreads();
   for (int s = threadIdx.x; s < ns; s += blockDim.x) sel[root_fold * S + s] = static_cast<int16_t>(root_unit);
   __syncthreads();
   for (int li = n_layers - 1; li >= 0; --li) {
     const ck_sample_layer L = layers[li];
-    const int items = L.F * ns;
-    const bool input = L.type == CK_SAMPLE_CATEGORICAL || L.type == CK_SAMPLE_GAUSSIAN;
-    for (int it = threadIdx.x; it < items; it += blockDim.x) {
-      // inner layers: consecutive threads = consecutive samples of one fold (one CDF row region, coalesced `choices`);
-      // input layers: consecutive threads = consecutive folds of one sample (neighbouring variables of one output row)
-      const int f = input ? it % L.F : it / ns;
-      const int s = input ? it / L.F : it % ns;
+    ck::walk_items(L, sel, S, ns, [&](int f, int s, int g, int k) {
       const int64_t n = n0 + s;
-      const int g = L.fold_off + f;
-      const int k = sel[g * S + s];
-      const bool on = k >= 0 && k < L.Ko;
-      if (!on) {
-        if (L.choices != nullptr) L.choices[static_cast<int64_t>(f) * N + n] = -1;
-        continue;
+      if (k < 0) {
+        ck::walk_record(L, f, N, n, -1);
+        return;
       }
-      const int32_t* ch = L.child + static_cast<int64_t>(f) * L.H;
-      if (L.type == CK_SAMPLE_HADAMARD) {
-        for (int h = 0; h < L.H; ++h) sel[ch[h] * S + s] = static_cast<int16_t>(k);
-        continue;
-      }
-      if (L.type == CK_SAMPLE_KRONECKER) {  // unit k = (u_0, ..., u_{H-1}) in base Ki, input 0 most significant
-        int r = k;
-        for (int h = L.H - 1; h >= 0; --h) {
-          sel[ch[h] * S + s] = static_cast<int16_t>(r % L.Ki);
-          r /= L.Ki;
-        }
-        continue;
-      }
-      const ck::Philox4 p = ck::philox4x32_10(static_cast<uint32_t>(n), static_cast<uint32_t>(g), 0u, 0u, key0, key1);
-      if (L.type == CK_SAMPLE_GAUSSIAN) {
-        const float u1 = static_cast<float>((p.x[0] >> 8) + 1u) * 5.9604644775390625e-8f;
-        const float u2 = ck::philox_uniform(p.x[1]);
-        const float z = sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
-        const int64_t o = n * D + L.scope[f];
-        const float v = L.mean[static_cast<int64_t>(f) * L.Ko + k] + L.stddev[static_cast<int64_t>(f) * L.Ko + k] * z;
-        if (x_float) static_cast<float*>(x)[o] = v;
-        continue;  // (a Gaussian layer makes the output fp32: DESIGN.md section 11)
+      const ck::Philox4 p = ck::walk_philox(n, g, key0, key1);
+      if (ck::is_input(L.type)) {
+        ck::draw_input(L, f, k, p, x, x_float, n * D + L.scope[f]);
+        return;
       }
       const int i = ck::cdf_draw(L.cdf + (static_cast<int64_t>(f) * L.Ko + k) * L.M, L.M, ck::philox_uniform(p.x[0]));
-      if (L.type == CK_SAMPLE_CATEGORICAL) {
-        const int64_t o = n * D + L.scope[f];
-        if (x_float) static_cast<float*>(x)[o] = static_cast<float>(i);
-        else static_cast<int64_t*>(x)[o] = i;
-        continue;
-      }
-      if (L.choices != nullptr) L.choices[static_cast<int64_t>(f) * N + n] = L.cmap != nullptr ? L.cmap[i] : i;
-      if (L.type == CK_SAMPLE_SUM) {
-        sel[ch[i / L.Ki] * S + s] = static_cast<int16_t>(i % L.Ki);
-      } else if (L.type == CK_SAMPLE_CPT) {
-        for (int h = 0; h < L.H; ++h) sel[ch[h] * S + s] = static_cast<int16_t>(i);
-      } else {  // CK_SAMPLE_TUCKER, arity 2
-        sel[ch[0] * S + s] = static_cast<int16_t>(i / L.Ki);
-        sel[ch[1] * S + s] = static_cast<int16_t>(i % L.Ki);
-      }
-    }
+      ck::walk_record(L, f, N, n, i);
+      ck::walk_child(L, L.child + static_cast<int64_t>(f) * L.H, sel, S, s, i);
+    });
     __syncthreads();
   }
 }
@@ -164,19 +122,14 @@ int ck_sample_cdf(const float* w, int64_t w_sf, int64_t w_sk, int64_t w_sm, int 
 int ck_sample_walk(const ck_sample_layer* layers, int n_layers, int root_fold, int root_unit, int total_folds, int S,
                    int64_t N, int D, uint64_t seed, void* x, int x_float, void* stream) {
   CK_REQUIRE(layers != nullptr && x != nullptr, "ck_sample_walk: null pointer");
-  CK_REQUIRE(n_layers > 0 && total_folds > 0 && N > 0 && D > 0 && S > 0, "ck_sample_walk: non-positive size");
-  CK_REQUIRE(root_fold >= 0 && root_fold < total_folds && root_unit >= 0 && root_unit < 32768,
-             "ck_sample_walk: root out of range");
-  const int64_t lds = static_cast<int64_t>(total_folds) * S * 2;
-  CK_REQUIRE(lds <= CK_SAMPLE_MAX_LDS, "ck_sample_walk: %d folds x %d samples exceed the LDS budget", total_folds, S);
-  const int64_t blocks = (N + S - 1) / S;
-  CK_REQUIRE(blocks <= 0x7fffffff, "ck_sample_walk: too many samples");
+  size_t lds;
+  unsigned blocks;
+  if (int st = ck::walk_grid("ck_sample_walk", n_layers, root_fold, root_unit, total_folds, S, N, D, lds, blocks)) return st;
   const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
   return ck::dispatch(
       [=](hipStream_t s) {
-        hipLaunchKernelGGL(sample_walk_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kWalkThreads),
-                           static_cast<size_t>(lds), s, layers, n_layers, root_fold, root_unit, total_folds, S, N, D, k0, k1,
-                           x, x_float);
+        hipLaunchKernelGGL(sample_walk_kernel, dim3(blocks), dim3(kWalkThreads), lds, s, layers, n_layers, root_fold,
+                           root_unit, total_folds, S, N, D, k0, k1, x, x_float);
         return hipGetLastError();
       },
       stream);

@@ -16,12 +16,11 @@ from __future__ import annotations
 
 from typing import TYPE_CHECKING
 
-import numpy as np
 import torch
 
 from . import _capi as capi
 from .parameters import HipParameter
-from .sampling import Sampler, chunk_rows, fold_block_offsets
+from .sampling import Sampler, chunk_rows, fold_block_offsets, pack, ptr_table, sampler
 
 if TYPE_CHECKING:  # pragma: no cover
     from .circuit import HipCircuit
@@ -30,19 +29,19 @@ _ALIGN = 64  # elements: every layer's (F, B, Ko) block of the arena starts on a
 
 
 class MPEState:
-    """The MPE state of one `HipCircuit`, next to its `Sampler`: the per-parameter-state tables and the upward arenas."""
+    """The MPE state of one `HipCircuit`, next to its `Sampler`: the per-parameter-state tables (kept in the sampler's
+    layer dicts: ``lw``, ``vmax``, ``amax``, ``src``, ``lp``), their device pointer tables and the upward arenas."""
 
-    def __init__(self, sampler: Sampler) -> None:
-        self.s = sampler
-        self.layers: list[dict] = [{} for _ in sampler.layers]
-        for t, d in zip(self.layers, sampler.layers):
+    def __init__(self, s: Sampler) -> None:
+        self.s = s
+        for d in s.layers:
             if d["kind"] == capi.CK_SAMPLE_GAUSSIAN and "log_partition" in d["spec"].params:
-                t["lp"] = HipParameter(d["spec"].params["log_partition"], sampler.store)
+                d["lp"] = HipParameter(d["spec"].params["log_partition"], s.store)
         self._key = None
         self._logw_tab: torch.Tensor | None = None
         self._amax_tab: torch.Tensor | None = None
         self._arenas: dict[int, tuple[torch.Tensor, torch.Tensor, list[int]]] = {}  # rows -> (arena, val_off, bases)
-        sizes = [d["F"] * d["Ko"] for d in sampler.layers]
+        sizes = [d["F"] * d["Ko"] for d in s.layers]
         self.sizes_per_row = sizes
         self.bytes_per_row = 4 * int(sum(sizes))
 
@@ -56,37 +55,29 @@ class MPEState:
         dev = s.device
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            logw = np.zeros(len(s.layers), dtype=np.uint64)
-            amax = np.zeros(len(s.layers), dtype=np.uint64)
-            for j, (d, t) in enumerate(zip(s.layers, self.layers)):
+            for d in s.layers:
                 F, Ko, M, kind = d["F"], d["Ko"], d["M"], d["kind"]
                 if "w" in d:  # sum / mixing / CP-T / Tucker: (F, Ko, M) linear weights evaluated by prepare()
                     w = d["w"]
-                    t["lw"] = torch.where(w > 0, torch.log(w), torch.full((), float("-inf"), device=dev)).contiguous()
-                    logw[j] = t["lw"].data_ptr()
+                    d["lw"] = torch.where(w > 0, torch.log(w), torch.full((), float("-inf"), device=dev)).contiguous()
                     continue
                 if kind not in (capi.CK_SAMPLE_CATEGORICAL, capi.CK_SAMPLE_GAUSSIAN):
                     continue
-                t["vmax"] = torch.empty((F, Ko), dtype=torch.float32, device=dev)
-                t["amax"] = torch.empty((F, Ko), dtype=torch.int32, device=dev)
+                d["vmax"] = torch.empty((F, Ko), dtype=torch.float32, device=dev)
+                d["amax"] = torch.empty((F, Ko), dtype=torch.int32, device=dev)
+                # src: the (tab, sf, sk, sc, t_log, C, mean, stddev, log_partition) arguments of both input launches
                 if kind == capi.CK_SAMPLE_GAUSSIAN:
-                    t["lp_v"] = t["lp"].evaluate(stream).reshape(F, Ko).contiguous().clone() if "lp" in t else None
-                    t["src"] = (None, 0, 0, 0, 0, 0)
-                    lp = t["lp_v"].data_ptr() if t["lp_v"] is not None else None
-                    capi.call("ck_mpe_input_max", kind, None, 0, 0, 0, 0, 0, d["mean_v"].data_ptr(), d["stddev_v"].data_ptr(),
-                              lp, F, Ko, t["vmax"].data_ptr(), t["amax"].data_ptr(), stream)
-                    continue
-                tab = d["tab"]  # prepare()'s table: Binomial (F, T + 2, K) log-pmf, Categorical (F, K, C) probs or logits
-                if d["spec"].type == "binomial":
-                    t["src"] = (tab, (M + 1) * Ko, 1, Ko, 1, M)
-                else:
-                    t["src"] = (tab, Ko * M, M, 1, 1 if d["is_logits"] else 0, M)
-                _, sf, sk, sc, t_log, C = t["src"]
-                capi.call("ck_mpe_input_max", kind, tab.data_ptr(), sf, sk, sc, t_log, C, None, None, None, F, Ko,
-                          t["vmax"].data_ptr(), t["amax"].data_ptr(), stream)
-                amax[j] = t["amax"].data_ptr()
-            self._logw_tab = torch.from_numpy(logw.view(np.int64)).to(dev)
-            self._amax_tab = torch.from_numpy(amax.view(np.int64)).to(dev)
+                    d["lp_v"] = d["lp"].evaluate(stream).reshape(F, Ko).contiguous().clone() if "lp" in d else None
+                    lp = d["lp_v"].data_ptr() if d["lp_v"] is not None else None
+                    d["src"] = (None, 0, 0, 0, 0, 0, d["mean_v"].data_ptr(), d["stddev_v"].data_ptr(), lp)
+                elif d["spec"].type == "binomial":  # prepare()'s (F, T + 2, K) log-pmf table
+                    d["src"] = (d["tab"].data_ptr(), (M + 1) * Ko, 1, Ko, 1, M, None, None, None)
+                else:  # prepare()'s (F, K, C) table of probabilities or logits
+                    d["src"] = (d["tab"].data_ptr(), Ko * M, M, 1, 1 if d["is_logits"] else 0, M, None, None, None)
+                capi.call("ck_mpe_input_max", kind, *d["src"], F, Ko, d["vmax"].data_ptr(), d["amax"].data_ptr(), stream)
+            self._logw_tab = ptr_table([d.get("lw") for d in s.layers], dev)
+            self._amax_tab = ptr_table([d.get("amax") if d["kind"] == capi.CK_SAMPLE_CATEGORICAL else None for d in s.layers],
+                                       dev)
         self._key = s._key
 
     # -- per chunk size ----------------------------------------------------------------------------------------------
@@ -107,22 +98,15 @@ class MPEState:
         arena, val_off, _ = self._arena(R)
         vals, vo = arena.data_ptr(), val_off.data_ptr()
         x_float = 1 if s.float_out else 0
-        for j, (d, t) in enumerate(zip(s.layers, self.layers)):
+        for j, d in enumerate(s.layers):
             F, H, Ki, Ko, M, kind, g0 = d["F"], d["H"], d["Ki"], d["Ko"], d["M"], d["kind"], int(s.fold_off[j])
-            if kind == capi.CK_SAMPLE_GAUSSIAN:
-                lp = t["lp_v"].data_ptr() if t["lp_v"] is not None else None
-                capi.call("ck_mpe_up_input", kind, d["scope"].data_ptr(), None, 0, 0, 0, 0, 0, d["mean_v"].data_ptr(),
-                          d["stddev_v"].data_ptr(), lp, t["vmax"].data_ptr(), F, Ko, xm.data_ptr(), x_float, R, s.D, vals, vo,
-                          g0, None if flag is None else flag.data_ptr(), bad.data_ptr(), stream)
-            elif kind == capi.CK_SAMPLE_CATEGORICAL:
-                tab, sf, sk, sc, t_log, C = t["src"]
-                capi.call("ck_mpe_up_input", kind, d["scope"].data_ptr(), tab.data_ptr(), sf, sk, sc, t_log, C, None, None, None,
-                          t["vmax"].data_ptr(), F, Ko, xm.data_ptr(), x_float, R, s.D, vals, vo, g0,
-                          None if flag is None else flag.data_ptr(), bad.data_ptr(), stream)
+            if kind in (capi.CK_SAMPLE_CATEGORICAL, capi.CK_SAMPLE_GAUSSIAN):
+                capi.call("ck_mpe_up_input", kind, d["scope"].data_ptr(), *d["src"], d["vmax"].data_ptr(), F, Ko, xm.data_ptr(),
+                          x_float, R, s.D, vals, vo, g0, None if flag is None else flag.data_ptr(), bad.data_ptr(), stream)
             elif kind in (capi.CK_SAMPLE_HADAMARD, capi.CK_SAMPLE_KRONECKER):
                 capi.call("ck_mpe_up_product", kind, d["child"].data_ptr(), F, H, Ki, Ko, vals, vo, g0, R, stream)
             else:
-                capi.call("ck_mpe_up_sum", kind, d["child"].data_ptr(), t["lw"].data_ptr(), F, H, Ki, Ko, M, vals, vo, g0, R,
+                capi.call("ck_mpe_up_sum", kind, d["child"].data_ptr(), d["lw"].data_ptr(), F, H, Ki, Ko, M, vals, vo, g0, R,
                           stream)
         return arena, val_off
 
@@ -131,16 +115,8 @@ class MPEState:
             rows_per_chunk: int | None = None):
         s = self.s
         hc = s.hc
-        D = s.D
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise ValueError("The input to the circuit should have shape (B, D), where B is the batch size and D "
-                             "is the number of variables the circuit is defined on")
-        if x.shape[1] < D:
-            raise ValueError(f"expected at least {D} variables, found {x.shape[1]}")
-        B = int(x.shape[0])
-        if B <= 0:
-            raise ValueError("empty batch")
-        xm = hc._apply_integration_mask(x[:, :D].to(s.device), query_vars).to(s.dtype).contiguous()  # (its errors first)
+        xm = s.evidence_batch(x, query_vars)
+        B = int(xm.shape[0])
         chunks = chunk_rows(B, rows_per_chunk, self.bytes_per_row)
         sizes = {nb for _, nb in chunks}
         self.tables()
@@ -153,43 +129,21 @@ class MPEState:
             logv = torch.empty(B, dtype=torch.float32, device=dev)
             bad = torch.zeros(B, dtype=torch.int32, device=dev)
             flag = hc._bad_input if hc.validate_inputs else None
-            table, choices = s._table, None
-            if return_choices:
-                desc = s._desc.copy()
-                choices = []
-                for j in s.sum_layers:
-                    c = torch.empty((s.layers[j]["F"], B), dtype=torch.int32, device=dev)
-                    desc[j]["choices"] = c.data_ptr()
-                    choices.append(c)
-                table = torch.from_numpy(desc.view(np.uint8).copy()).pin_memory().to(dev, non_blocking=True)
+            table, choices = s.choice_table(B) if return_choices else (s._table, None)
             for r0, nb in chunks:
                 xc = xm[r0 : r0 + nb]
                 arena, val_off = self._upward(xc, nb, flag, bad[r0:], stream)
                 capi.call("ck_mpe_walk", table.data_ptr(), self._logw_tab.data_ptr(), self._amax_tab.data_ptr(), len(s.layers),
                           s.root_fold, 0, s.total_folds, s.S, arena.data_ptr(), val_off.data_ptr(), bad.data_ptr(), r0, nb, B,
-                          D, xc.data_ptr(), out[r0].data_ptr(), 1 if s.float_out else 0, logv.data_ptr(), stream)
-            if s.zero_fill:  # variables outside every input layer's scope: 0, as `sample` writes, in rows with a completion
-                u = s.uncovered
-                cols = out[:, u]
-                sent = torch.isnan(cols) if s.float_out else cols < 0
-                out[:, u] = torch.where(sent & torch.isfinite(logv)[:, None], torch.zeros((), dtype=out.dtype, device=dev), cols)
-            if return_choices:
-                self._keep = table  # (the launches are asynchronous: the table outlives them until the next call)
-        res = (out,)
-        if return_choices:
-            res += (choices,)
-        if return_log_value:
-            res += (logv,)
-        return res[0] if len(res) == 1 else res
+                          s.D, xc.data_ptr(), out[r0].data_ptr(), 1 if s.float_out else 0, logv.data_ptr(), stream)
+            s.fill_uncovered(out, logv)
+        return pack(out, choices, logv if return_log_value else None)
 
 
 def mpe(hc: "HipCircuit", x: torch.Tensor, query_vars, *, return_choices: bool = False, return_log_value: bool = False,
         rows_per_chunk: int | None = None):
     """`HipCircuit.mpe`: see its docstring."""
-    s = getattr(hc, "_sampler", None)
-    if s is None:
-        s = hc._sampler = Sampler(hc)
-    m = getattr(s, "_mpe", None)
-    if m is None:
-        m = s._mpe = MPEState(s)
-    return m.mpe(x, query_vars, return_choices, return_log_value, rows_per_chunk)
+    s = sampler(hc)
+    if s._mpe is None:
+        s._mpe = MPEState(s)
+    return s._mpe.mpe(x, query_vars, return_choices, return_log_value, rows_per_chunk)

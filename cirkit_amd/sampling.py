@@ -119,7 +119,8 @@ class Sampler:
         if max(units) >= 32768:
             raise NotImplementedError("sampling layers of 32768 units or more")
         out = resolve_fold_index(plan.output, folds).reshape(-1, 2)
-        self.root_fold = int(self.fold_off[out[0, 0]] + out[0, 1])
+        self.root_layer, self.root_f = int(out[0, 0]), int(out[0, 1])  # (layer, fold) of the root unit
+        self.root_fold = int(self.fold_off[self.root_layer] + self.root_f)
         self.float_out = any(l.type == "gaussian" for l in plan.layers)
         self.dtype = torch.float32 if self.float_out else torch.int64
         dev = self.device
@@ -128,6 +129,7 @@ class Sampler:
         self.sum_layers: list[int] = []
         # (the log partition function of unit k of fold f of layer p sits at zoff[p] + f Ko_p + k of the flattened layer outputs)
         zoff = np.concatenate([[0], np.cumsum([f * k for f, k in zip(folds, units)])]).astype(np.int64)
+        self.root_z = int(zoff[self.root_layer] + self.root_f * units[self.root_layer])
         for j, (s, us) in enumerate(zip(plan.layers, user.layers)):
             d: dict = {"spec": s, "F": s.num_folds, "H": s.arity, "Ki": s.num_input_units, "Ko": s.num_output_units}
             if s.inputs is None:
@@ -178,6 +180,7 @@ class Sampler:
         self._key = None
         self._table: torch.Tensor | None = None  # the device descriptor table without choices
         self._desc: np.ndarray | None = None
+        self._mpe = None  # the `MPEState` (cirkit_amd/mpe.py), built by the first `mpe` call
 
     # -- once per parameter state ------------------------------------------------------------------------------------
     def _z_circuit(self):
@@ -254,7 +257,7 @@ class Sampler:
                               flag.data_ptr(), stream)
                     e["cmap"] = d["cmap"].data_ptr()
                 e["cdf"] = cdf.data_ptr()
-            root = zflat[self.root_fold_z()]
+            root = zflat[self.root_z]
             check = torch.stack([flag.to(torch.float32)[0], root]).cpu()  # one read per parameter state
         bad, logz = int(check[0]), float(check[1])
         if bad & 1:
@@ -267,48 +270,62 @@ class Sampler:
         self._table = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
         self._key = key
 
-    def root_fold_z(self) -> int:
-        """Index of the root unit (output fold 0, unit 0) in the flattened layer outputs."""
-        j = int(np.searchsorted(self.fold_off, self.root_fold, side="right") - 1)
-        f = self.root_fold - int(self.fold_off[j])
-        units = [l.num_output_units for l in self.plan.layers]
-        return int(sum(l.num_folds * k for l, k in zip(self.plan.layers[:j], units[:j])) + f * units[j])
-
     # -- once per call ------------------------------------------------------------------------------------------------
     def sample(self, num_samples: int, seed: int | None = None, return_choices: bool = False):
         N = int(num_samples)
         if N <= 0:
             raise ValueError("num_samples must be positive")
-        if seed is None:  # torch's default CPU generator: torch.manual_seed reproduces the samples
-            seed = int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64).item())
-        seed = int(seed) & (2**64 - 1)
+        seed = _seed(seed)
         self.prepare()
         dev = self.device
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             alloc = torch.zeros if self.zero_fill else torch.empty
             x = alloc((N, self.D), dtype=self.dtype, device=dev)
-            table, choices = self._table, None
-            if return_choices:
-                desc = self._desc.copy()
-                choices = []
-                for j in self.sum_layers:
-                    c = torch.empty((self.layers[j]["F"], N), dtype=torch.int32, device=dev)
-                    desc[j]["choices"] = c.data_ptr()
-                    choices.append(c)
-                table = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+            table, choices = self.choice_table(N) if return_choices else (self._table, None)
             capi.call("ck_sample_walk", table.data_ptr(), len(self.layers), self.root_fold, 0, self.total_folds, self.S, N,
                       self.D, seed, x.data_ptr(), 1 if self.float_out else 0, stream)
-            if return_choices:
-                self._keep = table  # (the launch is asynchronous: the table outlives it until the next call)
-        return (x, choices) if return_choices else x
+        return pack(x, choices, None)
+
+    # -- shared by the evidence queries: `sample_conditional` and `mpe` (cirkit_amd/mpe.py) ----------------------------
+    def evidence_batch(self, x: torch.Tensor, vars_) -> torch.Tensor:
+        """The (B, D) batch `x` with the variables `vars_` marks set to the sentinel, on the device in the output dtype.
+        Raises before anything is prepared or launched."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise ValueError("The input to the circuit should have shape (B, D), where B is the batch size and D "
+                             "is the number of variables the circuit is defined on")
+        if x.shape[1] < self.D:
+            raise ValueError(f"expected at least {self.D} variables, found {x.shape[1]}")
+        if x.shape[0] <= 0:
+            raise ValueError("empty batch")
+        return self.hc._apply_integration_mask(x[:, :self.D].to(self.device), vars_).to(self.dtype).contiguous()
+
+    def choice_table(self, N: int) -> tuple[torch.Tensor, list[torch.Tensor]]:
+        """The device descriptor table with an (F, N) int32 choices tensor for every sum-type layer, and those tensors.
+        The table is kept until the next call: the walk that reads it is asynchronous."""
+        desc = self._desc.copy()
+        choices = []
+        for j in self.sum_layers:
+            c = torch.empty((self.layers[j]["F"], N), dtype=torch.int32, device=self.device)
+            desc[j]["choices"] = c.data_ptr()
+            choices.append(c)
+        self._keep = torch.from_numpy(desc.view(np.uint8).copy()).pin_memory().to(self.device, non_blocking=True)
+        return self._keep, choices
+
+    def fill_uncovered(self, out: torch.Tensor, root_value: torch.Tensor) -> None:
+        """Variables outside every input layer's scope read 0, as `sample` writes, in the rows whose root value is finite."""
+        if self.zero_fill:
+            u = self.uncovered
+            cols = out[:, u]
+            sent = torch.isnan(cols) if self.float_out else cols < 0
+            zero = torch.zeros((), dtype=out.dtype, device=out.device)
+            out[:, u] = torch.where(sent & torch.isfinite(root_value)[:, None], zero, cols)
 
     # -- conditional sampling ---------------------------------------------------------------------------------------
     def _weight_table(self) -> torch.Tensor:
         """Device array of one pointer per layer: the (F, Ko, M) linear weights `prepare` evaluated, NULL for the others."""
         if self._wtab is None or self._wtab[0] != self._key:
-            ptrs = np.array([d["w"].data_ptr() if "w" in d else 0 for d in self.layers], dtype=np.uint64)
-            self._wtab = (self._key, torch.from_numpy(ptrs.view(np.int64)).to(self.device))
+            self._wtab = (self._key, ptr_table([d.get("w") for d in self.layers], self.device))
         return self._wtab[1]
 
     def _val_off_table(self, bd) -> torch.Tensor:
@@ -325,42 +342,22 @@ class Sampler:
 
     def sample_conditional(self, x: torch.Tensor, sample_vars, seed: int | None = None, return_choices: bool = False,
                            return_log_evidence: bool = False, rows_per_chunk: int | None = None):
-        D = self.D
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise ValueError("The input to the circuit should have shape (B, D), where B is the batch size and D "
-                             "is the number of variables the circuit is defined on")
-        if x.shape[1] < D:
-            raise ValueError(f"expected at least {D} variables, found {x.shape[1]}")
-        B = int(x.shape[0])
-        if B <= 0:
-            raise ValueError("empty batch")
-        xm = self.hc._apply_integration_mask(x[:, :D].to(self.device), sample_vars).to(self.dtype).contiguous()  # (its errors first)
+        xm = self.evidence_batch(x, sample_vars)
+        B = int(xm.shape[0])
         chunks = chunk_rows(B, rows_per_chunk, self.hc.arena_bytes(1))
         sizes = {nb for _, nb in chunks}
-        if seed is None:
-            seed = int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64).item())
-        seed = int(seed) & (2**64 - 1)
+        seed = _seed(seed)
         self.prepare()
         zc = self._z_circuit()
         for b in [b for b in zc._bindings if b != 1 and b not in sizes]:  # two batch sizes bound: the chunk and the tail
             zc._bindings.pop(b).destroy()
             self._val_off.pop(b, None)
         dev = self.device
-        j_root = int(np.searchsorted(self.fold_off, self.root_fold, side="right") - 1)
-        f_root = self.root_fold - int(self.fold_off[j_root])
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             out = xm.clone()  # (the sentinels mark what is left to draw)
             logev = torch.empty(B, dtype=torch.float32, device=dev)
-            table, choices = self._table, None
-            if return_choices:
-                desc = self._desc.copy()
-                choices = []
-                for j in self.sum_layers:
-                    c = torch.empty((self.layers[j]["F"], B), dtype=torch.int32, device=dev)
-                    desc[j]["choices"] = c.data_ptr()
-                    choices.append(c)
-                table = torch.from_numpy(desc.view(np.uint8).copy()).pin_memory().to(dev, non_blocking=True)
+            table, choices = self.choice_table(B) if return_choices else (self._table, None)
             wtab = self._weight_table()
             for r0, nb in chunks:
                 bd = zc._run(xm[r0 : r0 + nb])
@@ -370,41 +367,50 @@ class Sampler:
                 if self.hc.validate_inputs:
                     self.hc._bad_input.bitwise_or_(zc._bad_input)
                 zc._bad_input.zero_()
-                logev[r0 : r0 + nb].copy_(bd.views[j_root][f_root, :, 0])
+                logev[r0 : r0 + nb].copy_(bd.views[self.root_layer][self.root_f, :, 0])
                 capi.call("ck_sample_cond_walk", table.data_ptr(), wtab.data_ptr(), len(self.layers), self.root_fold, 0,
-                          self.total_folds, self.S, bd.arena.data_ptr(), self._val_off_table(bd).data_ptr(), r0, nb, B, D, seed,
-                          xm[r0].data_ptr(), out[r0].data_ptr(), 1 if self.float_out else 0, stream)
-            if self.zero_fill:  # variables outside every input layer's scope: 0, as `sample` writes, in rows with mass
-                u = self.uncovered
-                cols = out[:, u]
-                sent = torch.isnan(cols) if self.float_out else cols < 0
-                out[:, u] = torch.where(sent & torch.isfinite(logev)[:, None], torch.zeros((), dtype=out.dtype, device=dev), cols)
-            if return_choices:
-                self._keep = table
-        res = (out,)
-        if return_choices:
-            res += (choices,)
-        if return_log_evidence:
-            res += (logev,)
-        return res[0] if len(res) == 1 else res
+                          self.total_folds, self.S, bd.arena.data_ptr(), self._val_off_table(bd).data_ptr(), r0, nb, B,
+                          self.D, seed, xm[r0].data_ptr(), out[r0].data_ptr(), 1 if self.float_out else 0, stream)
+            self.fill_uncovered(out, logev)
+        return pack(out, choices, logev if return_log_evidence else None)
 
+
+def _seed(seed: int | None) -> int:
+    """The walk's 64-bit Philox key; None draws it from torch's default CPU generator (torch.manual_seed reproduces it)."""
+    if seed is None:
+        seed = int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64).item())
+    return int(seed) & (2**64 - 1)
+
+
+def ptr_table(tensors, device) -> torch.Tensor:
+    """A device array of one pointer per layer: each tensor's address, NULL for None."""
+    ptrs = np.array([0 if t is None else t.data_ptr() for t in tensors], dtype=np.uint64)
+    return torch.from_numpy(ptrs.view(np.int64)).to(device)
+
+
+def pack(out: torch.Tensor, choices: list | None, value: torch.Tensor | None):
+    """A query's result: the output, then the choices and the per-row value where they were asked for."""
+    res = (out,) + ((choices,) if choices is not None else ()) + ((value,) if value is not None else ())
+    return res[0] if len(res) == 1 else res
+
+
+def sampler(hc: "HipCircuit") -> Sampler:
+    """The circuit's `Sampler`, built on first use."""
+    s = getattr(hc, "_sampler", None)
+    if s is None:
+        s = hc._sampler = Sampler(hc)
+    return s
 
 
 def sample(hc: "HipCircuit", num_samples: int, *, seed: int | None = None, return_choices: bool = False):
     """`HipCircuit.sample`: see its docstring."""
-    s = getattr(hc, "_sampler", None)
-    if s is None:
-        s = hc._sampler = Sampler(hc)
-    return s.sample(num_samples, seed, return_choices)
+    return sampler(hc).sample(num_samples, seed, return_choices)
 
 
 def sample_conditional(hc: "HipCircuit", x: torch.Tensor, sample_vars, *, seed: int | None = None,
                        return_choices: bool = False, return_log_evidence: bool = False, rows_per_chunk: int | None = None):
     """`HipCircuit.sample_conditional`: see its docstring."""
-    s = getattr(hc, "_sampler", None)
-    if s is None:
-        s = hc._sampler = Sampler(hc)
-    return s.sample_conditional(x, sample_vars, seed, return_choices, return_log_evidence, rows_per_chunk)
+    return sampler(hc).sample_conditional(x, sample_vars, seed, return_choices, return_log_evidence, rows_per_chunk)
 
 
 class SamplingQuery:

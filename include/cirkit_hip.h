@@ -1176,7 +1176,7 @@ int ck_mpe_up_input(int type, const int64_t* scope, const float* tab, int64_t sf
                     const void* ev, int x_float, int64_t B, int D, float* vals, const int64_t* val_off, int fold_off,
                     int32_t* flag, int32_t* bad, void* stream);
 /* Upward values of a sum / mixing (CK_SAMPLE_SUM, mixing as its block-diagonal (K, H K) weight), CP-T or Tucker (arity 2)
- * layer: unit k of fold f at row n is max_i (lw[f, k, i] + v_i), v_i the entry's child value (ck_mpe_entry.h), lw (F, Ko, M)
+ * layer: unit k of fold f at row n is max_i (lw[f, k, i] + v_i), v_i the entry's child value (ck_walk.h), lw (F, Ko, M)
  * log weights with -inf for w <= 0.  Entries are taken two per v_max3_f32; a NaN entry is skipped. */
 int ck_mpe_up_sum(int type, const int32_t* child, const float* lw, int64_t F, int H, int Ki, int Ko, int M, float* vals,
                   const int64_t* val_off, int fold_off, int64_t B, void* stream);
