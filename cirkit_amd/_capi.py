@@ -316,6 +316,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_mpe_up_sum": [_i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _i, _l, _p],
     "ck_mpe_up_product": [_i, _p, _l, _i, _i, _i, _p, _p, _i, _l, _p],
     "ck_mpe_walk": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l, _l, _l, _i, _p, _p, _i, _p, _p],
+    "ck_flow_down_sum": [_i, _i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p, _i, _l, _p, _p],
+    "ck_flow_segment_add": [_p, _p, _p, _p, _p, _p, _p, _l, _i, _l, _p],
+    "ck_flow_down_product": [_i, _p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _l, _p],
+    "ck_flow_check_evidence": [_p, _i, _p, _l, _i, _p, _p, _p, _p],
+    "ck_flow_leaf_categorical": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _p],
+    "ck_flow_leaf_gaussian": [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],
     "ck_jobs_gauss_bwd": [_p, _i, _p, _i, _p, _p],
     "ck_opt_step_range": [_p, _p, _p, _p, _p, _l, _p, _p],

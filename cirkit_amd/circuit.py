@@ -1016,6 +1016,34 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         return mpe(self, x, query_vars, return_choices=return_choices, return_log_value=return_log_value,
                    rows_per_chunk=rows_per_chunk)
 
+    def posterior_marginals(self, x: torch.Tensor, query_vars, *, return_log_evidence: bool = False,
+                            rows_per_chunk: int | None = None):
+        """All single-variable posteriors of every row of ``x`` (B, D) at once: ``p[n, q, c] = p(X_{v_q} = c | x_O of row n)``
+        for output fold 0, unit 0 of any circuit `sample` accepts (the same refusals), exactly, in one evidence forward and
+        one top-down flow pass.  The reference has no such query.
+
+        `query_vars`: an iterable of variable ids or a ``(D,)`` / ``(1, D)`` bool mask (the errors of ``integrate_vars``; a
+        ``(B, D)`` mask with B > 1 is a ``ValueError``: the output would be ragged; a mask is read on the host).  ``Q`` is the
+        number of query variables, in ascending variable order.  A query variable's own entry of ``x`` is ignored; every
+        other entry holding the sentinel (a negative category, NaN) is integrated out, the rest is the evidence ``x_O``.  A
+        query variable no input layer covers is a ``ValueError``, a query set mixing discrete and Gaussian variables a
+        ``NotImplementedError``, both before anything is prepared or launched.
+
+        Returns ``(B, Q, C)`` fp32 on this device, allocated whole: ``B * Q * C * 4`` bytes (1.6 GB for 4096 rows, 392
+        variables of 256 states).  Discrete query variables: ``C`` is the largest state count among them, entries past a
+        variable's own state count are 0.  Gaussian query variables: ``C = 2``, the mean and the variance of the posterior
+        mixture ``sum_k f_k N(mean_k, stddev_k^2)`` over the variable's input units, weighted by their flows ``f_k``.  The
+        output is not renormalised: a row sums to 1 up to rounding.  `return_log_evidence`: also the ``(B,)`` fp32
+        ``log c(x_O)``.  A row whose evidence has no finite mass is NaN with a log evidence of -inf (no exception, no
+        synchronisation); an out-of-range observed category is reported by `check_inputs` and makes that row alone NaN (log
+        evidence included), whatever `rows_per_chunk` is: `mpe`'s behaviour.
+        `rows_per_chunk`: rows per evidence forward and flow pass (None: the value arena plus the flow arena and its
+        message buffer stay <= 2 GiB); results do not depend on it, bit for bit (cirkit_amd/posterior.py, DESIGN.md
+        section 11)."""
+        from .posterior import posterior_marginals
+
+        return posterior_marginals(self, x, query_vars, return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
+
     def log_likelihood_sum(self, x: torch.Tensor, out: torch.Tensor | None = None, *, reduce: bool = False) -> torch.Tensor:
         """Device tensor ``[sum_b log p(x_b), B]`` in fp64 -- the two numbers the data-parallel
         all-reduce exchanges (SURVEY.md section 8 e).  Requires a single scalar output.

@@ -1197,6 +1197,60 @@ int ck_mpe_walk(const ck_sample_layer* layers, const float* const* logw, const i
                 const int32_t* bad, int64_t row0, int64_t B, int64_t N, int D, const void* ev, void* x, int x_float,
                 float* logv, void* stream);
 
+/* ---- posterior marginals ("Posterior marginals"; additive, ABI 51) ---------------------------------
+ * All single-variable posteriors p(X_v = c | x_O) of every row in one evidence forward and one top-down FLOW pass: the flow
+ * of unit u is f(u) = d log c(x_O) / d log u in LINEAR space, f(root) = 1, and the posterior of v is the flow reaching the
+ * input units over v spread over their own distributions.  The reference has no such query (queries.py: IntegrateQuery and
+ * SamplingQuery only); its autograd computes the same derivative.  vals / val_off: the layer-wise marginal forward of the
+ * chunk's evidence, as ck_sample_cond_walk reads it; flow: an fp32 arena of the same layout (global fold g's (B, Ko) block at
+ * val_off[g]), the root block set by the caller.  Layers are sent down last to first.  No float atomics: results are bit
+ * for bit the same from call to call and for any chunking of the rows. */
+/* The contraction of a sum / mixing (CK_SAMPLE_SUM; diag != 0: mixing, its (K, H K) weight read on the block diagonals only),
+ * CP-T or Tucker (arity 2) layer of global folds fold_off .. fold_off + F - 1.  Per fold and row: lg_k = log f_k - v_k over
+ * the units with f_k > 0 and finite v_k (the others drop out), m = max_k lg_k, T_i = sum_k w[f, k, i] exp(lg_k - m) with w
+ * (F, Ko, M) LINEAR weights, and entry i receives exp(m + e_i + log T_i), exactly 0 where T_i = 0; e_i is the entry's child
+ * value (ck_walk.h).  Written to msg as (B, Ki) MESSAGE blocks, block s at s B Ki: sum / mixing slot f H + i / Ki unit
+ * i % Ki; CP-T slot f unit i (every input receives it); Tucker slot 2 f unit a the sum over b, slot 2 f + 1 unit b the sum
+ * over a.  Sum and CP-T layers of 32 / 64 output units and a multiple of 32 input units run on v_mfma_f32_32x32x2_f32,
+ * everything else on a plain VALU path. */
+int ck_flow_down_sum(int type, int diag, const int32_t* child, const float* w, int64_t F, int H, int Ki, int Ko, int M,
+                     const float* vals, const float* flow, const int64_t* val_off, int fold_off, int64_t B, float* msg,
+                     void* stream);
+/* Every child fold of a sum-type layer adds the messages of its consumers: child c (global fold cfold[c]) adds the slots
+ * items[cstart[c]] .. items[cstart[c + 1] - 1] of msg in list order to its (B, Ki) flow block; cfirst[c] != 0 (no later
+ * layer consumes the child): the sum is stored instead, so the arena needs no clearing. */
+int ck_flow_segment_add(const float* msg, const int32_t* cstart, const int32_t* cfold, const int32_t* cfirst,
+                        const int32_t* items, float* flow, const int64_t* val_off, int64_t n_child, int Ki, int64_t B,
+                        void* stream);
+/* The same for a product layer, read from the flow arena itself.  Hadamard: items are the consumers' global folds, unit k
+ * of the child receives f_k of each.  Kronecker: items are pairs (consumer global fold, input position h), unit i receives
+ * the sum of f over the outputs whose digit h in base Ki (input 0 most significant) is i, in ascending output order. */
+int ck_flow_down_product(int type, const int32_t* cstart, const int32_t* cfold, const int32_t* cfirst, const int32_t* items,
+                         float* flow, const int64_t* val_off, int64_t n_child, int H, int Ki, int Ko, int64_t B,
+                         void* stream);
+/* The range check of a chunk of masked evidence ev (B, D) -- int64, or fp32 with x_float != 0 -- before its evidence forward:
+ * states (D) int32 is the number of states the discrete input layers index each variable with (0: none does).  clean (B, D),
+ * same type, gets the evidence with every out-of-range observed category replaced by 0, so that one bad cell does not turn
+ * the forward of the other rows into NaN; bad[n] = 1 and *flag |= 1 (flag may be NULL) for a row that held one.  This is
+ * ck_mpe_up_input's rule, row by row. */
+int ck_flow_check_evidence(const void* ev, int x_float, const int32_t* states, int64_t B, int D, void* clean, int32_t* bad,
+                           int32_t* flag, void* stream);
+/* out (B, Q, Cout): out[n, q, c] = sum over the input folds of query variable q and their units k of f_k ntab[k, c].
+ * entries: four int64 per input fold (global fold, units K, states C, element offset of its (K, C) block of NORMALISED
+ * table rows in ntab), those of variable q at qstart[q] .. qstart[q + 1] - 1; states c >= C read 0.  A row whose root value
+ * (unit 0 of global fold root_fold, of root_ko units) is not finite, or with bad[n] != 0, is NaN.  logev (B), when not NULL,
+ * gets the root value, NaN where bad[n] != 0.  K_uniform: 32 / 64 when every entry has that many units
+ * (v_mfma_f32_32x32x2_f32 tiles of 32 rows x 32 states), 0 otherwise (plain VALU path). */
+int ck_flow_leaf_categorical(const int64_t* entries, const int32_t* qstart, int Q, int Cout, int K_uniform, const float* ntab,
+                             const float* flow, const float* vals, const int64_t* val_off, int root_fold, int root_ko,
+                             const int32_t* bad, int64_t B, float* out, float* logev, void* stream);
+/* out (B, Q, 2): the mean S1 and the variance S2 - S1^2 of the mixture sum_k f_k N(mean_k, stddev_k^2) over the units of
+ * the input folds of query variable q, S1 = sum f_k mean_k, S2 = sum f_k (stddev_k^2 + mean_k^2); the entries' offsets
+ * index mean / stddev.  Rows without a finite root value, or with bad[n] != 0, are NaN; logev as above. */
+int ck_flow_leaf_gaussian(const int64_t* entries, const int32_t* qstart, int Q, const float* mean, const float* stddev,
+                          const float* flow, const float* vals, const int64_t* val_off, int root_fold, int root_ko,
+                          const int32_t* bad, int64_t B, float* out, float* logev, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
