@@ -247,6 +247,7 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_tail16_lse_fwd": [_p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p],
     "ck_param_softmax": [_p, _p, _l, _i, _l, _i, _p],
     "ck_param_softmax_batch": [C.POINTER(SoftmaxJob), _i, _p],
+    "ck_param_table_job_fits": [_i, _i, _i],
     "ck_param_unary": [_i, _p, _p, _l, _f, _f, _p],
     "ck_param_gather_folds": [_p, _p, _p, _l, _l, _p],
     "ck_param_conj": [_p, _p, _l, _p],
@@ -391,6 +392,12 @@ def call(name: str, *args: Any) -> None:
     """Call an entry point and raise on a non-zero status.  ValueError on CK_ERR_INVALID mirrors the
     reference's shape errors (e.g. TorchSumLayer.__init__, layers/inner.py:237-242)."""
     check(getattr(load(), name)(*args), name)
+
+
+def table_job_fits(kind: int, num_categories: int, num_units: int) -> bool:
+    """Whether `ck_param_softmax_batch` takes a table job (kind 1, 4 or 5) of this size -- the launcher's own LDS bound
+    (`ck_param_table_job_fits`), so that what the host registers is what the launch accepts."""
+    return bool(load().ck_param_table_job_fits(int(kind), int(num_categories), int(num_units)))
 
 
 class Program:

@@ -339,8 +339,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             busy = self._virtual | set(self._group_of_root) | set(self._tail)
             cand = find_table_dense(plan, self.layers, self._children, busy)
             def fits(d: int, c: int) -> bool:  # one fold's (K, C) block + statistics + weights in LDS
-                K, Cn = self.layers[d].num_output_units, self.layers[c].num_categories
-                return (K * (Cn + 1) + 2 * K + K * K) * 4 <= 160 * 1024
+                return capi.table_job_fits(4, self.layers[c].num_categories, self.layers[d].num_output_units)
 
             self._tdense = {d: c for d, c in cand.items()
                             if self.layers[c].probs is not None and self.layers[c].probs.softmax_source() is not None

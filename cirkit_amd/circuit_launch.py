@@ -346,6 +346,8 @@ class _LaunchMixin:
             if src is None or wsrc is None or cat.num_output_units != 32 or tuple(wsrc.shape[1:]) != (32, 32):
                 continue
             Cn = cat.num_categories
+            if not capi.table_job_fits(5 if self.linear_levels else 4, Cn, 32):
+                continue  # (the launch would refuse it: the table and the dense weights go through their own jobs)
             leaf = self._children[g.dense_layer][:, 0, 1].astype(np.int64)
             idx = None if np.array_equal(leaf, np.arange(len(leaf))) else torch.from_numpy(leaf).to(self.device)
             dst = torch.empty((dl.num_folds, Cn + 1, 32), dtype=torch.float32, device=self.device)

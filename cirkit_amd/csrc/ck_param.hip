@@ -1292,6 +1292,17 @@ __global__ void __launch_bounds__(256) softmax_long_rows_kernel(const float* __r
   }
 }
 
+// LDS bytes of one workgroup of a table job (kinds 1, 4, 5): a fold's (k, len) block at a row stride of up to len + 4,
+// the two statistics rows, for kinds 4 / 5 the (k, k) dense weights; kind 1's rows form keeps it transposed, [len][k + 1].
+// The one place this is written down: the launcher refuses what exceeds kTableJobMaxLds, and the host asks
+// ck_param_table_job_fits before it registers such a job.
+constexpr size_t kTableJobMaxLds = 160 * 1024;
+size_t table_job_lds(int kind, int64_t len, int64_t k) {
+  size_t need = (static_cast<size_t>(k) * (len + 4) + 2 * k + (kind >= 4 ? k * k : 0)) * sizeof(float);
+  if (kind == 1) need = std::max(need, static_cast<size_t>(len) * (k + 1) * sizeof(float));
+  return need;
+}
+
 bool long_row_job(const ck_softmax_job& j) {
   return j.kind == 0 && j.len >= 512 && j.len <= 4096 && j.len % 4 == 0 && ck::aligned16(j.in) && ck::aligned16(j.out);
 }
@@ -1568,9 +1579,8 @@ int ck_param_softmax_batch(const ck_softmax_job* jobs, int njobs, void* stream) 
           blocks += static_cast<int>((j.rows + 16 * kPW - 1) / (16 * kPW));
         } else {
           CK_REQUIRE(j.k > 0, "ck_param_softmax_batch: job %d needs k > 0", idx);
-          size_t need = (static_cast<size_t>(j.k) * (j.len + 4) + 2 * j.k + (j.kind >= 4 ? j.k * j.k : 0)) * sizeof(float);  // (row stride up to len + 4)
-          if (j.kind == 1) need = std::max(need, static_cast<size_t>(j.len) * (j.k + 1) * sizeof(float));  // (transposed: [len][k + 1])
-          if (need > 160 * 1024)
+          const size_t need = table_job_lds(j.kind, j.len, j.k);
+          if (need > kTableJobMaxLds)
             return ck::fail(CK_ERR_UNSUPPORTED, "ck_param_softmax_batch: C*K=%d too large for the table job", j.len * j.k);
           lds = std::max(lds, need);
           blocks += static_cast<int>(j.rows);
@@ -1597,6 +1607,11 @@ int ck_param_softmax_batch(const ck_softmax_job* jobs, int njobs, void* stream) 
     }
   }
   return CK_OK;
+}
+
+int ck_param_table_job_fits(int kind, int len, int k) {
+  if (!(kind == 1 || kind == 4 || kind == 5) || len <= 0 || k <= 0) return 0;
+  return table_job_lds(kind, len, k) <= kTableJobMaxLds ? 1 : 0;
 }
 
 int ck_param_binomial_table(const float* p, int is_logits, float* table, int64_t F, int K, int total_count, void* stream) {

@@ -486,6 +486,10 @@ typedef struct ck_softmax_job {
   float* out2;        /* kind 5: (rows, C+1) log scale of each table row */
 } ck_softmax_job;
 int ck_param_softmax_batch(const ck_softmax_job* jobs, int njobs, void* stream);
+/* 1 if ck_param_softmax_batch takes a table job of this kind (1, 4 or 5) with `len` categories and `k` units -- one fold's
+ * block fits a workgroup's LDS -- and 0 if it would return CK_ERR_UNSUPPORTED (or the kind is no table job).  The launcher
+ * applies the same bound; whoever registers such jobs asks here instead of restating it.  Host only, no status. */
+int ck_param_table_job_fits(int kind, int len, int k);
 /* TorchBinomialLayer.log_unnormalized_likelihood (input.py:530-541) as a table: table (F, total_count + 2, K) --
  * row c = log-pmf of the value c for every unit, the last row the layer's integral (0); p (F, K) probabilities or logits.
  * ck_categorical_fwd then gathers row x[b] exactly as for a Categorical layer with total_count + 1 categories. */
