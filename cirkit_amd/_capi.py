@@ -323,6 +323,10 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_flow_check_evidence": [_p, _i, _p, _l, _i, _p, _p, _p, _p],
     "ck_flow_leaf_categorical": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _p],
     "ck_flow_leaf_gaussian": [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _p],
+    "ck_stats_edge_sum": [_i, _i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p, _i, _p, _l, _p, _p, _l, _p],
+    "ck_stats_leaf_categorical": [_p, _p, _l, _i, _i, _p, _i, _i, _p, _p, _i, _p, _l, _p, _p],
+    "ck_stats_leaf_gaussian": [_p, _p, _p, _l, _i, _p, _i, _p, _p, _i, _p, _l, _p, _p],
+    "ck_stats_unit_sum": [_p, _p, _p, _p, _l, _p, _l, _p, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],
     "ck_jobs_gauss_bwd": [_p, _i, _p, _i, _p, _p],
     "ck_opt_step_range": [_p, _p, _p, _p, _p, _l, _p, _p],

@@ -1043,6 +1043,32 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
 
         return posterior_marginals(self, x, query_vars, return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
 
+    def expected_statistics(self, x: torch.Tensor, missing_vars=None, *, rows_per_chunk: int | None = None):
+        """The expected sufficient statistics of every parameter under ``p(. | x_O)``, summed over the rows of ``x`` (B, D):
+        the E-step of EM, for any circuit `sample` accepts (the same refusals).  The reference has no such query.
+
+        `missing_vars`: an iterable of variable ids or a ``(D,)`` / ``(1, D)`` bool mask, integrated out for every row (the
+        errors of ``query_vars``, raised before anything is copied, prepared or launched); an entry of ``x`` holding the
+        sentinel (a negative category, NaN) is integrated out for its row alone; None with no sentinels is complete data.
+
+        Returns an `ExpectedStatistics` (cirkit_amd/expected.py), fp32 on this device, indexed by the user plan's layer
+        index: ``edge[j]`` (F, Ko, M), the shape of the layer's weight, for every sum-type layer -- ``N[f, k, i] = sum_n f_k
+        w[k, i] exp(e_i - v_k)`` with ``v``, ``e``, ``f`` the unit values, entry values and flows of `posterior_marginals`,
+        exactly 0 where ``w <= 0``; ``leaf[j]`` (F, K, C) for every Categorical / Binomial layer -- ``f_k`` at the observed
+        state, ``f_k`` times the unit's normalised table row where the variable is missing -- and (F, K, 3) = ``(sum f_k,
+        sum f_k m1, sum f_k m2)`` for every Gaussian layer, ``(m1, m2) = (x, x^2)`` observed and ``(mean_k, stddev_k^2 +
+        mean_k^2)`` missing; ``unit[j]`` (F, Ko) = ``sum_n f_k`` for every layer; ``log_evidence`` (B,); ``rows``, the
+        number of live rows, a 0-d int64 tensor (no synchronisation).  Only LIVE rows count: a row whose evidence has no
+        finite mass contributes nothing, and neither does one with an out-of-range observed category, which `check_inputs`
+        reports and whose log evidence is NaN.  ``st.normalised(pseudocount)`` gives the closed-form M-step targets; nothing
+        is written into the parameter store, and applying them through a plan's parameter graphs is the caller's business.
+        `rows_per_chunk`: rows per evidence forward and flow pass (None: as `posterior_marginals`).  No float atomics:
+        results are bit-identical from call to call for the same `rows_per_chunk`; chunks are added in order, so another
+        chunking may differ in rounding (`log_evidence` and `rows` do not)."""
+        from .expected import expected_statistics
+
+        return expected_statistics(self, x, missing_vars, rows_per_chunk=rows_per_chunk)
+
     def log_likelihood_sum(self, x: torch.Tensor, out: torch.Tensor | None = None, *, reduce: bool = False) -> torch.Tensor:
         """Device tensor ``[sum_b log p(x_b), B]`` in fp64 -- the two numbers the data-parallel
         all-reduce exchanges (SURVEY.md section 8 e).  Requires a single scalar output.

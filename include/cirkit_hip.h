@@ -1255,6 +1255,41 @@ int ck_flow_leaf_gaussian(const int64_t* entries, const int32_t* qstart, int Q, 
                           const float* flow, const float* vals, const int64_t* val_off, int root_fold, int root_ko,
                           const int32_t* bad, int64_t B, float* out, float* logev, void* stream);
 
+/* ---- expected statistics ("Expected statistics"; additive, ABI 51) -----------------------------------
+ * The flow pass above reduced OVER THE ROWS of a chunk: the expected sufficient statistics of every parameter under
+ * p(. | x_O), the E-step of EM.  vals / flow / val_off as above, after the chunk's flow pass.  live (B) int32: rows with
+ * live[n] == 0 (evidence out of range, root value not finite) contribute nothing.  Every entry point ADDS its sums to its
+ * output, so the caller zeroes the accumulators once and sends the chunks in order.  No float atomics: every sum has a fixed
+ * order that depends on the sizes alone, results are bit for bit the same from call to call. */
+/* edge (F, Ko, M) += N[f, k, i] = sum over the live rows of f_k w[f, k, i] exp(e_i - v_k) for a sum / mixing (diag != 0: block
+ * diagonals only, the rest stays untouched), CP-T or Tucker (arity 2) layer of global folds fold_off .. fold_off + F - 1;
+ * w (F, Ko, M) LINEAR weights, an entry with w <= 0 adds exactly 0, a unit with f_k = 0 or a v_k that is not finite drops out.
+ * Every term is a[n, k] w[k, i] g[n, i] with a = f_k exp(-v_k - m), g = exp(e_i + m) and m the row's max of log f_k - v_k, so
+ * nothing is exponentiated unshifted; a row with an entry whose e_i + m >= 40 takes f_k exp(e_i - v_k) in fp64 instead.  Sum
+ * and CP-T layers of 32 / 64 output units and a multiple of 32 input units accumulate 32 units x 32 entries tiles over row
+ * pairs on v_mfma_f32_32x32x2_f32, everything else takes a plain VALU path.  Launches of fewer than 1024 tiles (of 1024
+ * accumulators) split the rows into S = min(ceil(1024 / tiles), ceil(B / 64)) slices, write partial tiles to scratch and add
+ * them in slice order in a second launch: scratch needs tiles S 1024 floats then (at most 2^21), it may be NULL otherwise. */
+int ck_stats_edge_sum(int type, int diag, const int32_t* child, const float* w, int64_t F, int H, int Ki, int Ko, int M,
+                      const float* vals, const float* flow, const int64_t* val_off, int fold_off, const int32_t* live,
+                      int64_t B, float* edge, float* scratch, int64_t scratch_floats, void* stream);
+/* leaf (F, K, C) += per unit of a Categorical / Binomial layer of global folds fold_off .. the flows of the live rows by
+ * state: f_k at the state a row observes, f_k ntab[f, k, c] at every state where the row misses the variable (ntab (F, K, C)
+ * NORMALISED table rows).  scope (F) int64 the folds' variables; ev (B, D) the chunk's masked evidence, int64 or fp32
+ * (x_float != 0) with the sentinels of ck_flow_check_evidence.  A histogram in LDS, filled in row order. */
+int ck_stats_leaf_categorical(const int64_t* scope, const float* ntab, int64_t F, int K, int C, const void* ev, int x_float,
+                              int D, const float* flow, const int64_t* val_off, int fold_off, const int32_t* live, int64_t B,
+                              float* leaf, void* stream);
+/* leaf (F, K, 3) += (sum f_k, sum f_k m1, sum f_k m2) per unit of a Gaussian layer over the live rows, (m1, m2) = (x, x^2)
+ * where the row observes the variable and (mean_k, stddev_k^2 + mean_k^2) where it is missing (NaN); ev (B, D) fp32. */
+int ck_stats_leaf_gaussian(const int64_t* scope, const float* mean, const float* stddev, int64_t F, int K, const float* ev, int D,
+                           const float* flow, const int64_t* val_off, int fold_off, const int32_t* live, int64_t B, float* leaf,
+                           void* stream);
+/* unit[unit_off[g] + k] += the sum of f_k over the live rows, for every global fold g (fold_ko[g] units) of the arena: one
+ * launch per chunk. */
+int ck_stats_unit_sum(const float* flow, const int64_t* val_off, const int32_t* fold_ko, const int64_t* unit_off,
+                      int64_t total_folds, const int32_t* live, int64_t B, float* unit, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
