@@ -45,6 +45,18 @@ class SoftmaxJob(C.Structure):
     ]
 
 
+class EMJob(C.Structure):
+    """ck_em_job of include/cirkit_hip.h."""
+
+    _fields_ = [
+        ("raw", C.c_void_p), ("raw2", C.c_void_p), ("stats", C.c_void_p), ("support", C.c_void_p),
+        ("rows", C.c_int64),
+        ("len", C.c_int32), ("kind", C.c_int32), ("k", C.c_int32), ("raw_log", C.c_int32),
+        ("lo", C.c_float), ("hi", C.c_float),
+        ("block_begin", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class EinsumDesc(C.Structure):
     """ck_einsum_desc of include/cirkit_hip.h."""
 
@@ -181,6 +193,7 @@ SAMPLE_LAYER_DTYPE = [("type", "<i4"), ("F", "<i4"), ("H", "<i4"), ("Ki", "<i4")
                       ("mean", "<u8"), ("stddev", "<u8")]
 CK_SAMPLE_CATEGORICAL, CK_SAMPLE_GAUSSIAN, CK_SAMPLE_SUM, CK_SAMPLE_CPT, CK_SAMPLE_TUCKER, CK_SAMPLE_HADAMARD, CK_SAMPLE_KRONECKER = range(7)
 CK_SAMPLE_MAX_LDS = 65536
+CK_EM_ROW_SOFTMAX, CK_EM_ROW_LINEAR, CK_EM_MIXING, CK_EM_GAUSSIAN, CK_EM_BINOMIAL = range(5)
 NSUM_JOB_DTYPE = [("out", "<u8"), ("in_off", "<i4"), ("n_in", "<i4")]
 CAT_JOB_DTYPE = [("x", "<u8"), ("theta", "<u8"), ("table", "<u8"), ("dtheta", "<u8"), ("theta_out", "<u8"), ("m1", "<u8"), ("m2", "<u8"),
                  ("table_out", "<u8"), ("g_off", "<i4"), ("n_g", "<i4"), ("mode", "<i4"), ("reserved", "<i4")]
@@ -327,6 +340,8 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_stats_leaf_categorical": [_p, _p, _l, _i, _i, _p, _i, _i, _p, _p, _i, _p, _l, _p, _p],
     "ck_stats_leaf_gaussian": [_p, _p, _p, _l, _i, _p, _i, _p, _p, _i, _p, _l, _p, _p],
     "ck_stats_unit_sum": [_p, _p, _p, _p, _l, _p, _l, _p, _p],
+    "ck_em_job_blocks": [_i, _l, _i],
+    "ck_em_update": [_p, _p, _i, _f, _f, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],
     "ck_jobs_gauss_bwd": [_p, _i, _p, _i, _p, _p],
     "ck_opt_step_range": [_p, _p, _p, _p, _p, _l, _p, _p],

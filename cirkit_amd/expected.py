@@ -158,7 +158,10 @@ class ExpectedState:
                                device=dev) for j, d in enumerate(s.layers) if "scope" in d}
         return edge, leaf, torch.zeros(int(self.unit_at[-1]), dtype=torch.float32, device=dev)
 
-    def expected_statistics(self, x: torch.Tensor, missing_vars, rows_per_chunk: int | None) -> ExpectedStatistics:
+    def device_statistics(self, x: torch.Tensor, missing_vars, rows_per_chunk: int | None, into: tuple | None = None):
+        """The sums of a batch in the DEVICE plan's shapes, nothing sliced: ``(edge, leaf, unit, log_evidence, rows)``.  With
+        `into` = an earlier (edge, leaf, unit) the batch is ADDED to those accumulators, in call order (`HipEMTrainer`'s
+        running sums over several batches); otherwise they start at zero."""
         ps, s = self.ps, self.ps.s
         ids = [] if missing_vars is None else query_ids(missing_vars, s.D)  # (refusals first: nothing copied or launched)
         if rows_per_chunk is not None and int(rows_per_chunk) <= 0:
@@ -168,10 +171,9 @@ class ExpectedState:
         chunks = ps.chunks_of(B, rows_per_chunk)
         ps.tables()
         dev = s.device
-        user = s.hc.user_plan.layers
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            edge, leaf, unit = self.accumulators()
+            edge, leaf, unit = self.accumulators() if into is None else into
             logev = torch.empty(B, dtype=torch.float32, device=dev)
             bad = torch.zeros(B, dtype=torch.int32, device=dev)
             rows = torch.zeros((), dtype=torch.int64, device=dev)
@@ -188,6 +190,13 @@ class ExpectedState:
                 self.unit_sums(bd, flow, live, unit, stream)
                 self.edge_sums(bd, flow, live, edge, stream)
                 self.leaf_sums(bd, flow, xc, live, leaf, stream)
+        return edge, leaf, unit, logev, rows
+
+    def expected_statistics(self, x: torch.Tensor, missing_vars, rows_per_chunk: int | None) -> ExpectedStatistics:
+        ps, s = self.ps, self.ps.s
+        edge, leaf, unit, logev, rows = self.device_statistics(x, missing_vars, rows_per_chunk)
+        user = s.hc.user_plan.layers
+        with torch.cuda.device(s.device):
             # back to the user plan's unit counts (a padded unit carries no flow, a padded entry has weight 0)
             res = ExpectedStatistics({}, {}, [], logev, rows, kinds=[l.type for l in user])
             for j, (d, us) in enumerate(zip(s.layers, user)):

@@ -1290,6 +1290,38 @@ int ck_stats_leaf_gaussian(const int64_t* scope, const float* mean, const float*
 int ck_stats_unit_sum(const float* flow, const int64_t* val_off, const int32_t* fold_ko, const int64_t* unit_off,
                       int64_t total_folds, const int32_t* live, int64_t B, float* unit, void* stream);
 
+/* ---- EM training ("EM training"; additive, ABI 51) ---------------------------------------------------
+ * The M-step of a whole circuit as one launch over a job table: every job inverts one parameter graph in closed form on the
+ * batch-summed statistics of the entry points above and updates the RAW tensor of the store in place, row by row. */
+#define CK_EM_ROW_SOFTMAX 0 /* tensor -> softmax(last axis): rows x len logits, statistics rows x len                        */
+#define CK_EM_ROW_LINEAR 1  /* tensor: a linear weight row (raw_log = 0) or Categorical logits (raw_log = 1)                  */
+#define CK_EM_MIXING 2      /* tensor [-> softmax] -> mixing_weight: raw (F, k, len), statistics (F, k, len k) read at h k + unit */
+#define CK_EM_GAUSSIAN 3    /* raw the means, raw2 the stddev's pre-image under scaled_sigmoid(lo, hi); statistics rows x 3  */
+#define CK_EM_BINOMIAL 4    /* raw the pre-image of probs under sigmoid, one per row; statistics rows x (total_count + 1)    */
+typedef struct ck_em_job {
+  float* raw;           /* the raw tensor, updated in place */
+  float* raw2;          /* CK_EM_GAUSSIAN: the stddev's raw tensor; NULL otherwise */
+  const float* stats;   /* the statistics block behind it, in the device plan's shapes */
+  const float* support; /* the linear weights in the layout of stats, > 0 marks the support the pseudocount goes to; NULL: the
+                           support is read off the row itself (a logit above -inf, a linear entry above 0) */
+  int64_t rows;         /* rows (units for CK_EM_GAUSSIAN / CK_EM_BINOMIAL) */
+  int32_t len;          /* entries of a raw row (mixing: H); CK_EM_GAUSSIAN 3, CK_EM_BINOMIAL total_count + 1 */
+  int32_t kind;
+  int32_t k;            /* CK_EM_MIXING: units per fold */
+  int32_t raw_log;      /* row kinds: the raw row holds logarithms (read through a softmax, written as log theta) */
+  float lo, hi;         /* CK_EM_GAUSSIAN: vmin and vmax of the scaled sigmoid */
+  int32_t block_begin;  /* first workgroup of the job: the running sum of ck_em_job_blocks over the jobs before it */
+  int32_t reserved;
+} ck_em_job;
+/* Workgroups of one job (rows of up to 256 entries: one wave per row, four rows per workgroup; longer rows: one workgroup per
+ * row; CK_EM_GAUSSIAN: one thread per unit); -1 with a message for a kind or size that is none. */
+int ck_em_job_blocks(int kind, int64_t rows, int len);
+/* theta = (1 - step_size) theta_old + step_size theta_hat for every job, theta_hat from n = N + pseudocount [support]; `jobs`
+ * the host copy of the table (validated before anything is launched: -1 and a message), `device_jobs` the same bytes in device
+ * memory, read by the launch.  A row whose statistics sum to 0 keeps its raw values bit for bit; sums in a fixed order, no
+ * float atomics; s = (sigma - lo) / (hi - lo) and p are clamped into [2^-24, 1 - 2^-24] before log s - log1p(-s). */
+int ck_em_update(const ck_em_job* jobs, const ck_em_job* device_jobs, int njobs, float step_size, float pseudocount, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
