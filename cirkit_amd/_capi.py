@@ -336,6 +336,12 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_flow_check_evidence": [_p, _i, _p, _l, _i, _p, _p, _p, _p],
     "ck_flow_leaf_categorical": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _p],
     "ck_flow_leaf_gaussian": [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _p],
+    "ck_loo_down_sum": [_i, _i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p, _i, _l, _p, _p],
+    "ck_loo_segment_lse": [_p, _p, _p, _p, _p, _p, _p, _l, _i, _l, _p],
+    "ck_loo_down_product": [_i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _l, _i, _i, _i, _l, _p],
+    "ck_loo_leaf_categorical": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _l, _p, _p],
+    "ck_loo_leaf_gaussian": [_p, _p, _i, _p, _p, _p, _p, _p, _l, _p, _p],
+    "ck_loo_log_probs": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _l, _p, _p],
     "ck_stats_edge_sum": [_i, _i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p, _i, _p, _l, _p, _p, _l, _p],
     "ck_stats_leaf_categorical": [_p, _p, _l, _i, _i, _p, _i, _i, _p, _p, _i, _p, _l, _p, _p],
     "ck_stats_leaf_gaussian": [_p, _p, _p, _l, _i, _p, _i, _p, _p, _i, _p, _l, _p, _p],

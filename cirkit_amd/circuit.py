@@ -1043,6 +1043,42 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
 
         return posterior_marginals(self, x, query_vars, return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
 
+    def leave_one_out(self, x: torch.Tensor, query_vars=None, missing_vars=None, *, rows_per_chunk: int | None = None):
+        """The leave-one-out conditionals of every row of ``x`` (B, D) at once: ``p[n, q, c] = p(X_{v_q} = c | x_{O \\ {v_q}}
+        of row n)``, the distribution of each query variable given everything ELSE the row observes, for output fold 0,
+        unit 0 of any circuit `sample` accepts (the same refusals), in one evidence forward and one top-down derivative pass.
+        The reference has no such query.
+
+        `query_vars`: as in `posterior_marginals` (ids, a range, a ``(D,)`` / ``(1, D)`` bool mask); None: every variable in
+        the scope of an input layer.  `missing_vars`: as in `sample_conditional` (ids or a ``(D,)`` / ``(1, D)`` / ``(B, D)``
+        bool mask), integrated out, as is every entry holding the sentinel (a negative category, NaN).  A query variable may
+        be observed or missing; for a missing one the result is the posterior marginal ``p(X_v = c | x_O)``.  The result does
+        not depend on the query variable's own value.  Refused before anything is allocated or launched: a query variable
+        no input layer covers (``ValueError``), a query set mixing discrete and Gaussian variables
+        (``NotImplementedError``), an empty batch.
+
+        Returns ``(B, Q, C)`` fp32 on this device.  Discrete variables: ``C`` the largest state count among them, NORMALISED
+        over the states (unlike `posterior_marginals`), entries past a variable's own state count exactly 0.  Gaussian
+        variables: ``C = 2``, the mean and the variance of the mixture of the variable's input units weighted by
+        ``softmax_k`` of their log derivatives.  A (row, variable) whose leave-one-out mass is 0 is NaN; a row whose own
+        evidence has no mass but whose evidence without ``v`` has gets a proper distribution.  An out-of-range observed
+        category is reported by `check_inputs` and makes that row alone NaN, whatever `rows_per_chunk` is.
+        `rows_per_chunk`: rows per pass (None: the value arena, the derivative arena and the messages stay <= 2 GiB); results
+        do not depend on it, bit for bit (cirkit_amd/leave_one_out.py)."""
+        from .leave_one_out import leave_one_out
+
+        return leave_one_out(self, x, query_vars, missing_vars, rows_per_chunk=rows_per_chunk)
+
+    def conditional_log_probs(self, x: torch.Tensor, missing_vars=None, *, rows_per_chunk: int | None = None):
+        """``(B, D)`` fp32: ``log p(x_v | x_{O \\ {v}})`` of every observed entry of ``x`` (a log density for a Gaussian
+        variable), exactly 0 where the row misses the variable (or no input layer covers it), so that ``.sum(1)`` is the
+        row's pseudo-log-likelihood.  The pass of `leave_one_out` without its ``(B, Q, C)`` buffer; discrete and Gaussian
+        variables may be mixed.  NaN where the leave-one-out mass of the (row, variable) is 0, -inf where only the observed
+        value has no mass; out-of-range evidence as in `leave_one_out`."""
+        from .leave_one_out import conditional_log_probs
+
+        return conditional_log_probs(self, x, missing_vars, rows_per_chunk=rows_per_chunk)
+
     def expected_statistics(self, x: torch.Tensor, missing_vars=None, *, rows_per_chunk: int | None = None):
         """The expected sufficient statistics of every parameter under ``p(. | x_O)``, summed over the rows of ``x`` (B, D):
         the E-step of EM, for any circuit `sample` accepts (the same refusals).  The reference has no such query.

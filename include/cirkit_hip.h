@@ -1255,6 +1255,58 @@ int ck_flow_leaf_gaussian(const int64_t* entries, const int32_t* qstart, int Q, 
                           const float* flow, const float* vals, const int64_t* val_off, int root_fold, int root_ko,
                           const int32_t* bad, int64_t B, float* out, float* logev, void* stream);
 
+/* ---- leave-one-out conditionals ("Leave-one-out conditionals"; additive, ABI 51) ---------------------
+ * p(X_v = c | x_{O \ v}) for every variable v of every row in one evidence forward and one top-down DERIVATIVE pass:
+ * D(u) = log (dc(x_O) / du) in LOG space, 0 at the root unit, -inf where the derivative is 0 (Darwiche's differential reading:
+ * the derivative with respect to an input unit over v is the circuit with v taken out).  Unlike the flow above nothing
+ * divides by a value or multiplies by the child's own value, so units that give the observed state probability 0 keep their
+ * term.  vals / val_off as above; der: an fp32 arena of the same layout, -inf everywhere but 0 at the root unit on entry.
+ * Layers are sent down last to first.  No float atomics: results are bit for bit the same from call to call and for any
+ * chunking of the rows. */
+/* The contraction of a sum / mixing (diag != 0), CP-T or Tucker (arity 2) layer, the arguments of ck_flow_down_sum.  Per fold
+ * and row: m = max_k D_k over the finite D_k, T_i = sum_k w[f, k, i] exp(D_k - m), base_i = m + log T_i (-inf where
+ * T_i = 0).  Written to msg as (B, Ki) MESSAGE blocks, block s at s B Ki: sum / mixing slot f H + i / Ki unit i % Ki holds
+ * base_i; CP-T slot f H + h unit i holds base_i plus the values of the inputs h' != h at unit i, added in input order;
+ * Tucker slot 2 f unit a holds lse_b(base_(a, b) + v_1[b]), slot 2 f + 1 unit b holds lse_a(base_(a, b) + v_0[a]).  Sum and
+ * CP-T layers of 32 / 64 output units and a multiple of 32 input units run on v_mfma_f32_32x32x2_f32 (the lane layout of
+ * ck_flow_down_sum), everything else on a plain VALU path. */
+int ck_loo_down_sum(int type, int diag, const int32_t* child, const float* w, int64_t F, int H, int Ki, int Ko, int M,
+                    const float* vals, const float* der, const int64_t* val_off, int fold_off, int64_t B, float* msg,
+                    void* stream);
+/* Every child fold of a sum-type layer combines the messages of its consumers: child c (global fold cfold[c]) takes
+ * logaddexp over the slots items[cstart[c]] .. items[cstart[c + 1] - 1] of msg, in list order, into its (B, Ki) block of der;
+ * cfirst[c] != 0 (no later layer consumes the child): the result is stored, otherwise combined with what the block holds. */
+int ck_loo_segment_lse(const float* msg, const int32_t* cstart, const int32_t* cfold, const int32_t* cfirst,
+                       const int32_t* items, float* der, const int64_t* val_off, int64_t n_child, int Ki, int64_t B,
+                       void* stream);
+/* The same for a product layer of global folds layer_fold .., read from der itself; child (F, H) its global child folds,
+ * items pairs (consumer global fold g, input position h).  Hadamard: unit k receives D_g[k] plus the values of the consumer's
+ * inputs h' != h at unit k.  Kronecker: unit i receives the log-sum-exp over the outputs o whose digit h in base Ki (input 0
+ * most significant) is i, in ascending order, of D_g[o] plus the values of the inputs h' != h at their digits of o. */
+int ck_loo_down_product(int type, const int32_t* cstart, const int32_t* cfold, const int32_t* cfirst, const int32_t* items,
+                        const int32_t* child, int layer_fold, const float* vals, float* der, const int64_t* val_off,
+                        int64_t n_child, int H, int Ki, int Ko, int64_t B, void* stream);
+/* out (B, Q, Cout): out[n, q, c] = a_c / sum_c' a_c' with a_c = sum over the input folds of query variable q and their units
+ * k of exp(D_k + log Z_k - shift) ntab[k, c]: normalised over c before its single store.  entries: five int64 per input fold
+ * (global fold, units K, states C, element offset of its (K, C) block of NORMALISED table rows in ntab, element offset of its
+ * K log normalisers in lz; log Z_k = -inf drops the unit), those of variable q at qstart[q] .. qstart[q + 1] - 1; states
+ * c >= C read 0.  A (row, variable) without mass is NaN, and so is a row with bad[n] != 0.  max_units: the largest number of
+ * units over one query variable (LDS: 4 max_units floats per workgroup). */
+int ck_loo_leaf_categorical(const int64_t* entries, const int32_t* qstart, int Q, int Cout, int max_units, const float* ntab,
+                            const float* lz, const float* der, const int64_t* val_off, const int32_t* bad, int64_t B,
+                            float* out, void* stream);
+/* out (B, Q, 2): the mean S1 and the variance S2 - S1^2 of the mixture sum_k pi_k N(mean_k, stddev_k^2), pi = softmax_k(D_k)
+ * over the units of the input folds of query variable q; the entries' offsets index mean / stddev.  NaN as above. */
+int ck_loo_leaf_gaussian(const int64_t* entries, const int32_t* qstart, int Q, const float* mean, const float* stddev,
+                         const float* der, const int64_t* val_off, const int32_t* bad, int64_t B, float* out, void* stream);
+/* out (B, D): log p(x_v | x_{O \ v}) = lse_k(D_k + v_k) - lse_k(D_k + log Z_k) over the input units of variable v (entries
+ * vstart[v] .. vstart[v + 1] - 1), both sums shifted by max_k D_k.  Exactly 0 where the row misses v (ev (B, D): the chunk's
+ * masked evidence, int64 or fp32 with x_float != 0; vkind[v] == 2 marks a Gaussian variable) or no input layer covers v; NaN
+ * where the leave-one-out mass is 0 or bad[n] != 0; -inf where only the observed value has no mass. */
+int ck_loo_log_probs(const int64_t* entries, const int32_t* vstart, const int32_t* vkind, int D, const float* lz,
+                     const float* der, const float* vals, const int64_t* val_off, const void* ev, int x_float,
+                     const int32_t* bad, int64_t B, float* out, void* stream);
+
 /* ---- expected statistics ("Expected statistics"; additive, ABI 51) -----------------------------------
  * The flow pass above reduced OVER THE ROWS of a chunk: the expected sufficient statistics of every parameter under
  * p(. | x_O), the E-step of EM.  vals / flow / val_off as above, after the chunk's flow pass.  live (B) int32: rows with
