@@ -1,48 +1,24 @@
 // Posterior marginals ("Posterior marginals"): the top-down FLOW pass behind
 // `HipCircuit.posterior_marginals`.  With v the per-row log values of the layer-wise marginal forward of the evidence, the
 // flow of a unit is f(u) = d log c(x_O) / d log u, in LINEAR space, f(root) = 1.  Flows live in an fp32 arena laid out as the
-// value arena (global fold g's (B, Ko) block at val_off[g]).  A layer is sent down in two launches, neither with a float
-// atomic: the contraction writes one (B, Ki) MESSAGE block per (fold, input slot) into a scratch buffer, then every child
-// fold adds the messages of its consumers in list order (CSR), so results are bit-identical from call to call.
+// value arena (global fold g's (B, Ko) block at val_off[g]).  The pass itself -- contraction, message blocks, segment add --
+// is ck_down.h's, instantiated with FlowPass below; this file adds the Kronecker kernel and the leaves.
 #include <math.h>
 
-#include "ck_walk.h"
+#include "ck_down.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / ck::kWave;
-constexpr int kMaxLds = 48 * 1024;
+using ck::blocks_of;
+using ck::f32x16;
+using ck::kThreads;
+using ck::kWaves;
 
-// log f - v of a unit that carries flow; a unit with f = 0 (or NaN), or with v = -inf (or not finite), drops out.  Only the
-// row maximum m is taken from it, and m is only a shift (the same fp32 value on both sides): the fast logarithm will do.
-__device__ __forceinline__ float flow_lg(float f, float v) {
-  return (f > 0.f && v > -INFINITY && v < INFINITY) ? __logf(f) - v : -INFINITY;
-}
-// x exp(a + b) to ~2e-7 relative, whatever the size of a and b: the sum is taken exactly as hi + lo (Knuth's two-sum), so
-// that its rounding -- |a + b| 2^-24, 4e-5 where observed pixels put the values near -700 -- does not reach the exponential:
-// x exp(hi) (1 + lo).  A plain fp32 sum of the log-space terms put ~3e-7 of relative error into every flow of every layer;
-// fp64 exp / log, tried first, cost 5.9 ms of flow pass at config 2, 4096 rows.  Where exp(hi) alone
-// would overflow (the product is still <= 1: a unit or an entry with hardly any flow) the fp64 expression is used.
-__device__ __forceinline__ float scaled_exp(float x, float a, float b) {
-  const float hi = a + b;
-  const float t = hi - a;
-  const float lo = (a - (hi - t)) + (b - t);
-  if (__builtin_expect(!(hi < 80.f), 0))
-    return static_cast<float>(static_cast<double>(x) * exp(static_cast<double>(a) + static_cast<double>(b)));
-  const float e = x * expf(hi);
-  return fmaf(e, lo, e);
-}
-// f exp(-v - m), 0 for a dropped unit (m = -inf only when every unit dropped)
-__device__ __forceinline__ float flow_a(float f, float v, float m) {
-  return (f > 0.f && v > -INFINITY && v < INFINITY) ? scaled_exp(f, -v, -m) : 0.f;
-}
 // T exp(m + e) with nothing exponentiated unshifted; T = 0 gives exactly 0, e = -inf gives 0.
 __device__ __forceinline__ float flow_out(float T, float m, float e) {
   if (!(T > 0.f)) return 0.f;
   if (e == -INFINITY) return 0.f;
-  return scaled_exp(T, m, e);
+  return ck::scaled_exp(T, m, e);
 }
 
 // Where the flow of entry i of fold f at row n goes: sum / mixing slot f H + i / Ki unit i % Ki; CP-T slot f unit i.
@@ -52,147 +28,33 @@ __device__ __forceinline__ int64_t msg_index(int type, int64_t f, int H, int Ki,
   return (slot * B + n) * Ki + unit;
 }
 
-// ---- the contraction, plain VALU path: any layer type, any unit counts ---------------------------------------------
-// A workgroup owns one fold and TR rows.  LDS: sa[TR][Ko] = exp(lg - m), sm[TR] = m, and for Tucker sf[TR][M] entry flows.
-__global__ void __launch_bounds__(kThreads)
-    flow_down_sum_generic(int type, int diag, const int32_t* __restrict__ child, const float* __restrict__ w, int64_t F, int H,
-                          int Ki, int Ko, int M, const float* __restrict__ vals, const float* __restrict__ flow,
-                          const int64_t* __restrict__ val_off, int fold_off, int64_t B, int TR, int64_t row_tiles,
-                          float* __restrict__ msg) {
-  extern __shared__ float sh[];
-  float* const sa = sh;
-  float* const sm = sa + TR * Ko;
-  float* const sf = sm + TR;
-  const int64_t f = blockIdx.x / row_tiles;
-  const int64_t n0 = (blockIdx.x % row_tiles) * TR;
-  const int lane = threadIdx.x & (ck::kWave - 1), wave = threadIdx.x / ck::kWave;
-  const int64_t blk = val_off[fold_off + f];
-  for (int r = wave; r < TR; r += kWaves) {
-    const int64_t n = n0 + r;
-    float mx = -INFINITY;
-    for (int k = lane; k < Ko; k += ck::kWave)
-      if (n < B) mx = fmaxf(mx, flow_lg(flow[blk + n * Ko + k], vals[blk + n * Ko + k]));
-    const float m = ck::wave_max(mx);
-    for (int k = lane; k < Ko; k += ck::kWave)
-      sa[r * Ko + k] = n < B ? flow_a(flow[blk + n * Ko + k], vals[blk + n * Ko + k], m) : 0.f;
-    if (lane == 0) sm[r] = m;
-  }
-  __syncthreads();
-  const int32_t* ch = child + f * H;
-  const float* wf = w + f * Ko * M;
-  for (int it = threadIdx.x; it < TR * M; it += kThreads) {
-    const int r = it / M, i = it % M;
-    const int64_t n = n0 + r;
+// The flow pass as a policy of ck_down.h: the factor of a unit is a = f exp(-v - m), entry i receives the flow
+// T exp(m + e_i), a child adds what its consumers send.
+struct FlowPass {
+  static __device__ __forceinline__ float key(float f, float v) { return ck::flow_lg(f, v); }
+  static __device__ __forceinline__ float factor(float f, float v, float m) { return ck::flow_a(f, v, m); }
+  static __device__ __forceinline__ float emit(bool tucker, int type, const int32_t* __restrict__ ch, int64_t f, int H, int Ki,
+                                               int64_t B, int64_t n, int i, float T, float m, const float* __restrict__ vals,
+                                               const int64_t* __restrict__ val_off, float* __restrict__ msg) {
     float fl = 0.f;
-    if (n < B) {
-      float T = 0.f;
-      if (diag) {  // mixing: the (K, H K) weight is block diagonal, entry i only meets unit i % Ki
-        const int k = i % Ki;
-        T = sa[r * Ko + k] * wf[static_cast<int64_t>(k) * M + i];
-      } else {
-        for (int k = 0; k < Ko; ++k) T = fmaf(sa[r * Ko + k], wf[static_cast<int64_t>(k) * M + i], T);
-      }
-      if (T > 0.f) fl = flow_out(T, sm[r], ck::entry_value(type, ch, H, Ki, vals, val_off, n, i));
-      if (type != CK_SAMPLE_TUCKER) msg[msg_index(type, f, H, Ki, B, n, i)] = fl;
-    }
-    if (type == CK_SAMPLE_TUCKER) sf[it] = fl;
+    if (T > 0.f) fl = flow_out(T, m, ck::entry_value(type, ch, H, Ki, vals, val_off, n, i));
+    if (!tucker) msg[msg_index(type, f, H, Ki, B, n, i)] = fl;
+    return fl;
   }
-  if (type != CK_SAMPLE_TUCKER) return;
-  __syncthreads();
   // Tucker: input 0 unit a receives the sum over b, input 1 unit b the sum over a
-  for (int it = threadIdx.x; it < TR * 2 * Ki; it += kThreads) {
-    const int u = it % Ki, s = (it / Ki) % 2, r = it / (2 * Ki);
-    const int64_t n = n0 + r;
-    if (n >= B) continue;
-    const float* row = sf + r * M;
+  static __device__ __forceinline__ float tucker(const float* row, int Ki, int s, int u, const int32_t* __restrict__,
+                                                 const float* __restrict__, const int64_t* __restrict__, int64_t) {
     float acc = 0.f;
     if (s == 0) {
       for (int b = 0; b < Ki; ++b) acc += row[u * Ki + b];
     } else {
       for (int a = 0; a < Ki; ++a) acc += row[a * Ki + u];
     }
-    msg[((f * 2 + s) * B + n) * Ki + u] = acc;
+    return acc;
   }
-}
-
-// ---- the contraction on the fp32 matrix cores: sum and CP-T layers of KO = 32 / 64 units, M a multiple of 32 ---------
-// One wave owns (fold, 32 rows) and walks the entry tiles: T (32 rows x 32 entries) = a (32 x KO) W (KO x 32) on
-// v_mfma_f32_32x32x2_f32.  Lane (b = lane & 31, hi = lane >> 5) holds a[row b][hi KO/2 + kk], so step kk contracts units kk
-// and KO/2 + kk: a fixed order, the same for every row wherever its tile starts.
-template <int KO>
-__global__ void __launch_bounds__(kThreads)
-    flow_down_sum_mfma(int type, const int32_t* __restrict__ child, const float* __restrict__ w, int64_t F, int H, int Ki,
-                       int M, const float* __restrict__ vals, const float* __restrict__ flow,
-                       const int64_t* __restrict__ val_off, int fold_off, int64_t B, int64_t row_tiles,
-                       float* __restrict__ msg) {
-  constexpr int KH = KO / 2;
-  __shared__ float sm[kWaves][32];
-  const int lane = threadIdx.x & (ck::kWave - 1), wave = threadIdx.x / ck::kWave;
-  const int b = lane & 31, hi = lane >> 5;
-  const int64_t tile = static_cast<int64_t>(blockIdx.x) * kWaves + wave;
-  if (tile >= F * row_tiles) return;  // (no workgroup barrier below: the LDS row is the wave's own)
-  const int64_t f = tile / row_tiles, n0 = (tile % row_tiles) * 32;
-  const int64_t nb = n0 + b < B ? n0 + b : B - 1;
-  const int64_t at = val_off[fold_off + f] + nb * KO + hi * KH;
-  float a[KH], vk[KH];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int kk = 0; kk < KH; ++kk) {
-    a[kk] = flow[at + kk];
-    vk[kk] = vals[at + kk];
-    mx = fmaxf(mx, flow_lg(a[kk], vk[kk]));
-  }
-  const float m = ck::xhalf_max(mx);
-#pragma unroll
-  for (int kk = 0; kk < KH; ++kk) a[kk] = flow_a(a[kk], vk[kk], m);
-  if (hi == 0) sm[wave][b] = m;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int32_t* ch = child + f * H;
-  const float* wf = w + f * KO * M + static_cast<int64_t>(hi) * KH * M + b;
-  for (int i0 = 0; i0 < M; i0 += 32) {
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < KH; ++kk)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], wf[static_cast<int64_t>(kk) * M + i0], acc, 0, 0, 0);
-    const int i = i0 + b;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 8 * (r >> 2) + 4 * hi + (r & 3);
-      const int64_t n = n0 + row;
-      if (n >= B) continue;
-      const float T = acc[r];
-      float fl = 0.f;
-      if (T > 0.f) fl = flow_out(T, sm[wave][row], ck::entry_value(type, ch, H, Ki, vals, val_off, n, i));
-      msg[msg_index(type, f, H, Ki, B, n, i)] = fl;
-    }
-  }
-}
-
-// ---- accumulation: every child fold adds its consumers' blocks in list order ----------------------------------------
-// Child c of the launch (global fold cfold[c]) has the items cstart[c] .. cstart[c + 1] - 1.  An item is a message slot of
-// `src` ((B, Ki) block at item B Ki), or with src_is_flow a global fold of the flow arena itself (Hadamard: unit k of every
-// input receives f_k).  cfirst[c] != 0: no earlier launch of this pass wrote the child, the sum is stored, not added.
-__global__ void __launch_bounds__(kThreads)
-    flow_add_rows_kernel(const float* __restrict__ src, int src_is_flow, const int32_t* __restrict__ cstart,
-                         const int32_t* __restrict__ cfold, const int32_t* __restrict__ cfirst,
-                         const int32_t* __restrict__ items, float* flow, const int64_t* __restrict__ val_off, int64_t n_child,
-                         int Ki, int64_t B) {
-  const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  const int64_t per = B * Ki;
-  if (idx >= n_child * per) return;
-  const int64_t c = idx / per, rem = idx % per;
-  float* dst = flow + val_off[cfold[c]] + rem;
-  float acc = cfirst[c] ? 0.f : *dst;
-  for (int s = cstart[c]; s < cstart[c + 1]; ++s) {
-    const int64_t base = src_is_flow ? val_off[items[s]] : static_cast<int64_t>(items[s]) * per;
-    acc += src[base + rem];
-  }
-  *dst = acc;
-}
+  static __device__ __forceinline__ float identity() { return 0.f; }
+  static __device__ __forceinline__ float combine(float a, float b) { return a + b; }
+};
 
 // Kronecker: item (parent global fold g, input position h); unit i of the child receives the sum of the parent's flow over
 // the outputs whose digit h (base Ki, input 0 most significant) is i, in ascending output order.
@@ -294,7 +156,7 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 // The same on the fp32 matrix cores, every entry with K units: a workgroup owns (q, 32 rows), its waves the 32-state column
-// tiles; (32 rows x K) flows x (K x 32) normalised table rows per entry, the unit order of flow_down_sum_mfma.  A wave
+// tiles; (32 rows x K) flows x (K x 32) normalised table rows per entry, the unit order of down_sum_mfma.  A wave
 // stores, per accumulator register, two rows of 32 consecutive states: whole 128-byte lines.
 template <int K>
 __global__ void __launch_bounds__(kThreads)
@@ -368,68 +230,20 @@ __global__ void __launch_bounds__(kThreads)
   out[idx * 2 + 1] = s2 - s1 * s1;
 }
 
-int64_t blocks_of(int64_t items, int threads) { return (items + threads - 1) / threads; }
-
 }  // namespace
 
 int ck_flow_down_sum(int type, int diag, const int32_t* child, const float* w, int64_t F, int H, int Ki, int Ko, int M,
                      const float* vals, const float* flow, const int64_t* val_off, int fold_off, int64_t B, float* msg,
                      void* stream) {
-  CK_REQUIRE(type == CK_SAMPLE_SUM || type == CK_SAMPLE_CPT || type == CK_SAMPLE_TUCKER, "ck_flow_down_sum: not a sum-type layer");
-  CK_REQUIRE(child != nullptr && w != nullptr && vals != nullptr && flow != nullptr && val_off != nullptr && msg != nullptr,
-             "ck_flow_down_sum: null pointer");
-  CK_REQUIRE(F > 0 && H > 0 && Ki > 0 && Ko > 0 && M > 0 && B > 0 && fold_off >= 0, "ck_flow_down_sum: non-positive size");
-  CK_REQUIRE(M == (type == CK_SAMPLE_SUM ? H * Ki : type == CK_SAMPLE_CPT ? Ki : Ki * Ki) && (type != CK_SAMPLE_TUCKER || H == 2),
-             "ck_flow_down_sum: %d entries for type %d, arity %d, %d input units", M, type, H, Ki);
-  CK_REQUIRE(!diag || (type == CK_SAMPLE_SUM && Ko == Ki), "ck_flow_down_sum: a mixing layer is a sum layer with Ko = Ki");
-  if (!diag && type != CK_SAMPLE_TUCKER && (Ko == 32 || Ko == 64) && Ki % 32 == 0) {
-    const int64_t row_tiles = (B + 31) / 32;
-    const int64_t blocks = blocks_of(F * row_tiles, kWaves);
-    CK_REQUIRE(blocks <= 0x7fffffff, "ck_flow_down_sum: grid too large");
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          if (Ko == 32)
-            hipLaunchKernelGGL(flow_down_sum_mfma<32>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, type, child, w,
-                               F, H, Ki, M, vals, flow, val_off, fold_off, B, row_tiles, msg);
-          else
-            hipLaunchKernelGGL(flow_down_sum_mfma<64>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, type, child, w,
-                               F, H, Ki, M, vals, flow, val_off, fold_off, B, row_tiles, msg);
-          return hipGetLastError();
-        },
-        stream);
-  }
-  const int64_t per_row = static_cast<int64_t>(Ko) + 1 + (type == CK_SAMPLE_TUCKER ? M : 0);
-  int TR = 16;
-  while (TR > 1 && TR * per_row * 4 > kMaxLds) TR /= 2;
-  CK_REQUIRE(TR * per_row * 4 <= kMaxLds, "ck_flow_down_sum: %d units and %d entries exceed the LDS budget", Ko, M);
-  const int64_t row_tiles = (B + TR - 1) / TR;
-  CK_REQUIRE(F * row_tiles <= 0x7fffffff, "ck_flow_down_sum: grid too large");
-  const size_t lds = static_cast<size_t>(TR * per_row * 4);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(flow_down_sum_generic, dim3(static_cast<unsigned>(F * row_tiles)), dim3(kThreads), lds, s, type, diag,
-                           child, w, F, H, Ki, Ko, M, vals, flow, val_off, fold_off, B, TR, row_tiles, msg);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch_down_sum<FlowPass>("ck_flow_down_sum", type, diag, child, w, F, H, Ki, Ko, M, vals, flow, val_off, fold_off, B,
+                                       msg, stream);
 }
 
 int ck_flow_segment_add(const float* msg, const int32_t* cstart, const int32_t* cfold, const int32_t* cfirst,
                         const int32_t* items, float* flow, const int64_t* val_off, int64_t n_child, int Ki, int64_t B,
                         void* stream) {
-  CK_REQUIRE(msg != nullptr && cstart != nullptr && cfold != nullptr && cfirst != nullptr && items != nullptr &&
-                 flow != nullptr && val_off != nullptr,
-             "ck_flow_segment_add: null pointer");
-  CK_REQUIRE(n_child > 0 && Ki > 0 && B > 0, "ck_flow_segment_add: non-positive size");
-  const int64_t blocks = blocks_of(n_child * B * Ki, kThreads);
-  CK_REQUIRE(blocks <= 0x7fffffff, "ck_flow_segment_add: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(flow_add_rows_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, msg, 0, cstart, cfold,
-                           cfirst, items, flow, val_off, n_child, Ki, B);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch_segment<FlowPass>("ck_flow_segment_add", msg, 0, cstart, cfold, cfirst, items, flow, val_off, n_child, Ki, B,
+                                      stream);
 }
 
 int ck_flow_down_product(int type, const int32_t* cstart, const int32_t* cfold, const int32_t* cfirst, const int32_t* items,
@@ -440,23 +254,16 @@ int ck_flow_down_product(int type, const int32_t* cstart, const int32_t* cfold, 
                  val_off != nullptr,
              "ck_flow_down_product: null pointer");
   CK_REQUIRE(n_child > 0 && H > 0 && Ki > 0 && Ko > 0 && B > 0, "ck_flow_down_product: non-positive size");
-  if (type == CK_SAMPLE_HADAMARD) {
-    CK_REQUIRE(Ko == Ki, "ck_flow_down_product: Hadamard with %d inputs, %d outputs", Ki, Ko);
-  } else {
-    int64_t p = 1;
-    for (int h = 0; h < H && p <= Ko; ++h) p *= Ki;
-    CK_REQUIRE(p == Ko, "ck_flow_down_product: Kronecker of %d inputs of %d units with %d outputs", H, Ki, Ko);
-  }
+  if (int st = ck::check_product_shape("ck_flow_down_product", type, H, Ki, Ko)) return st;
+  if (type == CK_SAMPLE_HADAMARD)  // unit k of every input receives f_k: the items are folds of the flow arena itself
+    return ck::launch_segment<FlowPass>("ck_flow_down_product", flow, 1, cstart, cfold, cfirst, items, flow, val_off, n_child, Ki,
+                                        B, stream);
   const int64_t blocks = blocks_of(n_child * B * Ki, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_flow_down_product: too many entries");
   return ck::dispatch(
       [=](hipStream_t s) {
-        if (type == CK_SAMPLE_HADAMARD)
-          hipLaunchKernelGGL(flow_add_rows_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, flow, 1, cstart,
-                             cfold, cfirst, items, flow, val_off, n_child, Ki, B);
-        else
-          hipLaunchKernelGGL(flow_kron_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, cstart, cfold, cfirst,
-                             items, flow, val_off, n_child, H, Ki, Ko, B);
+        hipLaunchKernelGGL(flow_kron_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, cstart, cfold, cfirst,
+                           items, flow, val_off, n_child, H, Ki, Ko, B);
         return hipGetLastError();
       },
       stream);

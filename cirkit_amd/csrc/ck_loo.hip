@@ -3,20 +3,19 @@
 // forward of the evidence, D(u) = log (dc(x_O) / du) in LOG space, 0 at the root unit and -inf where the derivative is 0.
 // Unlike the flow of ck_flow.hip, f = (dc/du) u / c, nothing here divides by a value or multiplies by the child's own value:
 // a unit that gives the observed state probability 0 keeps its derivative, which is what the conditional of THAT variable
-// needs.  The arena is laid out as the value arena (global fold g's (B, Ko) block at val_off[g]).  A layer is sent down in two
-// launches, neither with a float atomic: the contraction writes one (B, Ki) MESSAGE block per (fold, input) into a scratch
-// buffer, then every child fold combines the messages of its consumers with logaddexp in list order (CSR), so results are
-// bit-identical from call to call and for any chunking of the rows.
+// needs.  The arena is laid out as the value arena (global fold g's (B, Ko) block at val_off[g]).  The pass itself --
+// contraction, message blocks, segment combine by logaddexp -- is ck_down.h's, instantiated with DerivativePass below; this
+// file adds the product kernel and the leaves.
 #include <math.h>
 
-#include "ck_walk.h"
+#include "ck_down.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / ck::kWave;
-constexpr int kMaxLds = 48 * 1024;
+using ck::blocks_of;
+using ck::kMaxLds;
+using ck::kThreads;
+using ck::kWaves;
 
 __device__ __forceinline__ bool finite_d(float d) { return d > -INFINITY && d < INFINITY; }
 // exp(D - m), 0 for a unit without a derivative (m is finite whenever some D is)
@@ -47,60 +46,21 @@ __device__ __forceinline__ void store_messages(int type, const int32_t* __restri
   }
 }
 
-// ---- the contraction, plain VALU path: any layer type, any unit counts ---------------------------------------------
-// A workgroup owns one fold and TR rows.  LDS: sa[TR][Ko] = exp(D - m), sm[TR] = m, and for Tucker sf[TR][M] = m + log T.
-__global__ void __launch_bounds__(kThreads)
-    loo_down_sum_generic(int type, int diag, const int32_t* __restrict__ child, const float* __restrict__ w, int64_t F, int H,
-                         int Ki, int Ko, int M, const float* __restrict__ vals, const float* __restrict__ der,
-                         const int64_t* __restrict__ val_off, int fold_off, int64_t B, int TR, int64_t row_tiles,
-                         float* __restrict__ msg) {
-  extern __shared__ float sh[];
-  float* const sa = sh;
-  float* const sm = sa + TR * Ko;
-  float* const sf = sm + TR;
-  const int64_t f = blockIdx.x / row_tiles;
-  const int64_t n0 = (blockIdx.x % row_tiles) * TR;
-  const int lane = threadIdx.x & (ck::kWave - 1), wave = threadIdx.x / ck::kWave;
-  const int64_t blk = val_off[fold_off + f];
-  for (int r = wave; r < TR; r += kWaves) {
-    const int64_t n = n0 + r;
-    float mx = -INFINITY;
-    for (int k = lane; k < Ko; k += ck::kWave) {
-      const float d = n < B ? der[blk + n * Ko + k] : -INFINITY;
-      if (finite_d(d)) mx = fmaxf(mx, d);
-    }
-    const float m = ck::wave_max(mx);
-    for (int k = lane; k < Ko; k += ck::kWave) sa[r * Ko + k] = n < B ? shifted_exp(der[blk + n * Ko + k], m) : 0.f;
-    if (lane == 0) sm[r] = m;
+// The derivative pass as a policy of ck_down.h: the factor of a unit is a = exp(D - m), the base of entry i is m + log T_i
+// and every input of the entry receives it with its SIBLINGS' values, a child combines what its consumers send by logaddexp.
+struct DerivativePass {
+  static __device__ __forceinline__ float key(float d, float) { return finite_d(d) ? d : -INFINITY; }
+  static __device__ __forceinline__ float factor(float d, float, float m) { return shifted_exp(d, m); }
+  static __device__ __forceinline__ float emit(bool tucker, int type, const int32_t* __restrict__ ch, int64_t f, int H, int Ki,
+                                               int64_t B, int64_t n, int i, float T, float m, const float* __restrict__ vals,
+                                               const int64_t* __restrict__ val_off, float* __restrict__ msg) {
+    const float base = lift(T, m);
+    if (!tucker) store_messages(type, ch, f, H, Ki, B, n, i, base, vals, val_off, msg);
+    return base;
   }
-  __syncthreads();
-  const int32_t* ch = child + f * H;
-  const float* wf = w + f * Ko * M;
-  for (int it = threadIdx.x; it < TR * M; it += kThreads) {
-    const int r = it / M, i = it % M;
-    const int64_t n = n0 + r;
-    float base = -INFINITY;
-    if (n < B) {
-      float T = 0.f;
-      if (diag) {  // mixing: the (K, H K) weight is block diagonal, entry i only meets unit i % Ki
-        const int k = i % Ki;
-        T = sa[r * Ko + k] * wf[static_cast<int64_t>(k) * M + i];
-      } else {
-        for (int k = 0; k < Ko; ++k) T = fmaf(sa[r * Ko + k], wf[static_cast<int64_t>(k) * M + i], T);
-      }
-      base = lift(T, sm[r]);
-      if (type != CK_SAMPLE_TUCKER) store_messages(type, ch, f, H, Ki, B, n, i, base, vals, val_off, msg);
-    }
-    if (type == CK_SAMPLE_TUCKER) sf[it] = base;
-  }
-  if (type != CK_SAMPLE_TUCKER) return;
-  __syncthreads();
   // Tucker: input 0 unit a receives lse_b(base[a, b] + v1[b]), input 1 unit b receives lse_a(base[a, b] + v0[a])
-  for (int it = threadIdx.x; it < TR * 2 * Ki; it += kThreads) {
-    const int u = it % Ki, s = (it / Ki) % 2, r = it / (2 * Ki);
-    const int64_t n = n0 + r;
-    if (n >= B) continue;
-    const float* row = sf + r * M;
+  static __device__ __forceinline__ float tucker(const float* row, int Ki, int s, int u, const int32_t* __restrict__ ch,
+                                                 const float* __restrict__ vals, const int64_t* __restrict__ val_off, int64_t n) {
     const float* other = vals + val_off[ch[1 - s]] + n * Ki;
     const int at = s == 0 ? u * Ki : u, step = s == 0 ? 1 : Ki;
     float mx = -INFINITY;
@@ -111,79 +71,11 @@ __global__ void __launch_bounds__(kThreads)
       for (int j = 0; j < Ki; ++j) acc += expf(row[at + j * step] + other[j] - mx);
       out = mx + logf(acc);
     }
-    msg[((f * 2 + s) * B + n) * Ki + u] = out;
+    return out;
   }
-}
-
-// ---- the contraction on the fp32 matrix cores: sum and CP-T layers of KO = 32 / 64 units, M a multiple of 32 ---------
-// One wave owns (fold, 32 rows) and walks the entry tiles: T (32 rows x 32 entries) = a (32 x KO) W (KO x 32) on
-// v_mfma_f32_32x32x2_f32, the lane layout of ck_flow.hip's flow_down_sum_mfma: lane (b = lane & 31, hi = lane >> 5) holds
-// a[row b][hi KO/2 + kk], so step kk contracts units kk and KO/2 + kk: a fixed order, the same for every row wherever its
-// tile starts.
-template <int KO>
-__global__ void __launch_bounds__(kThreads)
-    loo_down_sum_mfma(int type, const int32_t* __restrict__ child, const float* __restrict__ w, int64_t F, int H, int Ki, int M,
-                      const float* __restrict__ vals, const float* __restrict__ der, const int64_t* __restrict__ val_off,
-                      int fold_off, int64_t B, int64_t row_tiles, float* __restrict__ msg) {
-  constexpr int KH = KO / 2;
-  __shared__ float sm[kWaves][32];
-  const int lane = threadIdx.x & (ck::kWave - 1), wave = threadIdx.x / ck::kWave;
-  const int b = lane & 31, hi = lane >> 5;
-  const int64_t tile = static_cast<int64_t>(blockIdx.x) * kWaves + wave;
-  if (tile >= F * row_tiles) return;  // (no workgroup barrier below: the LDS row is the wave's own)
-  const int64_t f = tile / row_tiles, n0 = (tile % row_tiles) * 32;
-  const int64_t nb = n0 + b < B ? n0 + b : B - 1;
-  const int64_t at = val_off[fold_off + f] + nb * KO + hi * KH;
-  float a[KH];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int kk = 0; kk < KH; ++kk) {
-    a[kk] = der[at + kk];
-    if (finite_d(a[kk])) mx = fmaxf(mx, a[kk]);
-  }
-  const float m = ck::xhalf_max(mx);
-#pragma unroll
-  for (int kk = 0; kk < KH; ++kk) a[kk] = shifted_exp(a[kk], m);
-  if (hi == 0) sm[wave][b] = m;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const int32_t* ch = child + f * H;
-  const float* wf = w + f * KO * M + static_cast<int64_t>(hi) * KH * M + b;
-  for (int i0 = 0; i0 < M; i0 += 32) {
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < KH; ++kk)
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], wf[static_cast<int64_t>(kk) * M + i0], acc, 0, 0, 0);
-    const int i = i0 + b;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = 8 * (r >> 2) + 4 * hi + (r & 3);
-      const int64_t n = n0 + row;
-      if (n >= B) continue;
-      store_messages(type, ch, f, H, Ki, B, n, i, lift(acc[r], sm[wave][row]), vals, val_off, msg);
-    }
-  }
-}
-
-// ---- accumulation: every child fold combines its consumers' blocks in list order -----------------------------------
-// Child c of the launch (global fold cfold[c]) has the items cstart[c] .. cstart[c + 1] - 1, message slots of msg ((B, Ki)
-// block at item B Ki).  cfirst[c] != 0: no earlier launch of this pass wrote the child, the result is stored, not combined.
-__global__ void __launch_bounds__(kThreads)
-    loo_segment_kernel(const float* __restrict__ msg, const int32_t* __restrict__ cstart, const int32_t* __restrict__ cfold,
-                       const int32_t* __restrict__ cfirst, const int32_t* __restrict__ items, float* der,
-                       const int64_t* __restrict__ val_off, int64_t n_child, int Ki, int64_t B) {
-  const int64_t idx = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  const int64_t per = B * Ki;
-  if (idx >= n_child * per) return;
-  const int64_t c = idx / per, rem = idx % per;
-  float* dst = der + val_off[cfold[c]] + rem;
-  float acc = cfirst[c] ? -INFINITY : *dst;
-  for (int s = cstart[c]; s < cstart[c + 1]; ++s) acc = logaddexp(acc, msg[static_cast<int64_t>(items[s]) * per + rem]);
-  *dst = acc;
-}
+  static __device__ __forceinline__ float identity() { return -INFINITY; }
+  static __device__ __forceinline__ float combine(float a, float b) { return logaddexp(a, b); }
+};
 
 // Product layers, read from the derivative arena itself.  An item is the pair (consumer's global fold g, input position h);
 // child holds the (F, H) global child folds of the layer whose first global fold is layer_fold.  Hadamard: unit i receives
@@ -401,68 +293,20 @@ __global__ void __launch_bounds__(kThreads)
   out[idx] = res;
 }
 
-int64_t blocks_of(int64_t items, int threads) { return (items + threads - 1) / threads; }
-
 }  // namespace
 
 int ck_loo_down_sum(int type, int diag, const int32_t* child, const float* w, int64_t F, int H, int Ki, int Ko, int M,
                     const float* vals, const float* der, const int64_t* val_off, int fold_off, int64_t B, float* msg,
                     void* stream) {
-  CK_REQUIRE(type == CK_SAMPLE_SUM || type == CK_SAMPLE_CPT || type == CK_SAMPLE_TUCKER, "ck_loo_down_sum: not a sum-type layer");
-  CK_REQUIRE(child != nullptr && w != nullptr && vals != nullptr && der != nullptr && val_off != nullptr && msg != nullptr,
-             "ck_loo_down_sum: null pointer");
-  CK_REQUIRE(F > 0 && H > 0 && Ki > 0 && Ko > 0 && M > 0 && B > 0 && fold_off >= 0, "ck_loo_down_sum: non-positive size");
-  CK_REQUIRE(M == (type == CK_SAMPLE_SUM ? H * Ki : type == CK_SAMPLE_CPT ? Ki : Ki * Ki) && (type != CK_SAMPLE_TUCKER || H == 2),
-             "ck_loo_down_sum: %d entries for type %d, arity %d, %d input units", M, type, H, Ki);
-  CK_REQUIRE(!diag || (type == CK_SAMPLE_SUM && Ko == Ki), "ck_loo_down_sum: a mixing layer is a sum layer with Ko = Ki");
-  if (!diag && type != CK_SAMPLE_TUCKER && (Ko == 32 || Ko == 64) && Ki % 32 == 0) {
-    const int64_t row_tiles = (B + 31) / 32;
-    const int64_t blocks = blocks_of(F * row_tiles, kWaves);
-    CK_REQUIRE(blocks <= 0x7fffffff, "ck_loo_down_sum: grid too large");
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          if (Ko == 32)
-            hipLaunchKernelGGL(loo_down_sum_mfma<32>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, type, child, w,
-                               F, H, Ki, M, vals, der, val_off, fold_off, B, row_tiles, msg);
-          else
-            hipLaunchKernelGGL(loo_down_sum_mfma<64>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, type, child, w,
-                               F, H, Ki, M, vals, der, val_off, fold_off, B, row_tiles, msg);
-          return hipGetLastError();
-        },
-        stream);
-  }
-  const int64_t per_row = static_cast<int64_t>(Ko) + 1 + (type == CK_SAMPLE_TUCKER ? M : 0);
-  int TR = 16;
-  while (TR > 1 && TR * per_row * 4 > kMaxLds) TR /= 2;
-  CK_REQUIRE(TR * per_row * 4 <= kMaxLds, "ck_loo_down_sum: %d units and %d entries exceed the LDS budget", Ko, M);
-  const int64_t row_tiles = (B + TR - 1) / TR;
-  CK_REQUIRE(F * row_tiles <= 0x7fffffff, "ck_loo_down_sum: grid too large");
-  const size_t lds = static_cast<size_t>(TR * per_row * 4);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(loo_down_sum_generic, dim3(static_cast<unsigned>(F * row_tiles)), dim3(kThreads), lds, s, type, diag,
-                           child, w, F, H, Ki, Ko, M, vals, der, val_off, fold_off, B, TR, row_tiles, msg);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch_down_sum<DerivativePass>("ck_loo_down_sum", type, diag, child, w, F, H, Ki, Ko, M, vals, der, val_off,
+                                             fold_off, B, msg, stream);
 }
 
 int ck_loo_segment_lse(const float* msg, const int32_t* cstart, const int32_t* cfold, const int32_t* cfirst,
                        const int32_t* items, float* der, const int64_t* val_off, int64_t n_child, int Ki, int64_t B,
                        void* stream) {
-  CK_REQUIRE(msg != nullptr && cstart != nullptr && cfold != nullptr && cfirst != nullptr && items != nullptr &&
-                 der != nullptr && val_off != nullptr,
-             "ck_loo_segment_lse: null pointer");
-  CK_REQUIRE(n_child > 0 && Ki > 0 && B > 0, "ck_loo_segment_lse: non-positive size");
-  const int64_t blocks = blocks_of(n_child * B * Ki, kThreads);
-  CK_REQUIRE(blocks <= 0x7fffffff, "ck_loo_segment_lse: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(loo_segment_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, msg, cstart, cfold,
-                           cfirst, items, der, val_off, n_child, Ki, B);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch_segment<DerivativePass>("ck_loo_segment_lse", msg, 0, cstart, cfold, cfirst, items, der, val_off, n_child, Ki,
+                                            B, stream);
 }
 
 int ck_loo_down_product(int type, const int32_t* cstart, const int32_t* cfold, const int32_t* cfirst, const int32_t* items,
@@ -473,13 +317,7 @@ int ck_loo_down_product(int type, const int32_t* cstart, const int32_t* cfold, c
                  vals != nullptr && der != nullptr && val_off != nullptr,
              "ck_loo_down_product: null pointer");
   CK_REQUIRE(n_child > 0 && H > 0 && Ki > 0 && Ko > 0 && B > 0 && layer_fold >= 0, "ck_loo_down_product: non-positive size");
-  if (type == CK_SAMPLE_HADAMARD) {
-    CK_REQUIRE(Ko == Ki, "ck_loo_down_product: Hadamard with %d inputs, %d outputs", Ki, Ko);
-  } else {
-    int64_t p = 1;
-    for (int h = 0; h < H && p <= Ko; ++h) p *= Ki;
-    CK_REQUIRE(p == Ko, "ck_loo_down_product: Kronecker of %d inputs of %d units with %d outputs", H, Ki, Ko);
-  }
+  if (int st = ck::check_product_shape("ck_loo_down_product", type, H, Ki, Ko)) return st;
   const int64_t blocks = blocks_of(n_child * B * Ki, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_loo_down_product: too many entries");
   return ck::dispatch(

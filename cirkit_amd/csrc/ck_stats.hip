@@ -10,35 +10,23 @@
 // unit on that entry are <= e^-40, or zero) leaves the factored product: its terms are f_k exp(e_i - v_k) in fp64, no shift.
 #include <math.h>
 
-#include "ck_walk.h"
+#include "ck_down.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / ck::kWave;
-constexpr int kMaxLds = 48 * 1024;
+using ck::blocks_of;
+using ck::f32x16;
+using ck::kMaxLds;
+using ck::kThreads;
+using ck::kWaves;
 constexpr int kTile = 1024;           // accumulators of one (MFMA tile | generic pair chunk)
 constexpr int kPairs = kTile / kThreads;
 constexpr float kSlowShift = 40.f;    // g <= e^40, so a >= e^-87 (the smallest normal fp32) loses nothing above e^-47
 constexpr int64_t kTargetWaves = 1024;  // rows are split into slices until a launch has about this many waves
 constexpr int64_t kMinSliceRows = 64;
 
-// log f - v of a unit that carries flow (ck_flow.hip's flow_lg): only the shift is taken from it.
-__device__ __forceinline__ float stats_lg(float f, float v) {
-  return (f > 0.f && v > -INFINITY && v < INFINITY) ? __logf(f) - v : -INFINITY;
-}
-// x exp(a + b) with the sum taken exactly as hi + lo (ck_flow.hip's scaled_exp; callers keep hi below kSlowShift)
-__device__ __forceinline__ float stats_exp(float x, float a, float b) {
-  const float hi = a + b;
-  const float t = hi - a;
-  const float lo = (a - (hi - t)) + (b - t);
-  const float e = x * expf(hi);
-  return fmaf(e, lo, e);
-}
-__device__ __forceinline__ float stats_a(float f, float v, float m) {
-  return (f > 0.f && v > -INFINITY && v < INFINITY) ? stats_exp(f, -v, -m) : 0.f;
-}
+// The shift and the factor a are the flow pass's (ck_down.h: flow_lg, flow_a); callers keep the exponent below kSlowShift, so
+// the two-sum exponential is taken without its overflow branch (scaled_exp_core).
 // One term without its weight, unfactored: f exp(e - v) in fp64 (the rows that left the factored product).
 __device__ __forceinline__ float stats_term(float f, float v, float e) {
   if (!(f > 0.f && v > -INFINITY && v < INFINITY) || e == -INFINITY) return 0.f;
@@ -88,14 +76,14 @@ __global__ void __launch_bounds__(kThreads)
     const bool ok = n < n_end && live[n < n_end ? n : n0] != 0;
     const int64_t nn = n < n_end ? n : n0;  // (a row the loads may touch)
     const float fk = flow[blk + nn * KO + k0 + b], vk = vals[blk + nn * KO + k0 + b];
-    const float m = half_max(ok ? stats_lg(fk, vk) : -INFINITY);
+    const float m = half_max(ok ? ck::flow_lg(fk, vk) : -INFINITY);
     float a = 0.f, g = 0.f;
     bool slow = false;
     if (m > -INFINITY) {  // (uniform over the half: some unit of the row carries flow)
       const float e = ck::entry_value(type, ch, H, Ki, vals, val_off, nn, i);
       slow = e > -INFINITY && e + m >= kSlowShift;
-      a = stats_a(fk, vk, m);
-      g = (e > -INFINITY && !slow) ? stats_exp(1.f, e, m) : 0.f;
+      a = ck::flow_a<false>(fk, vk, m);
+      g = (e > -INFINITY && !slow) ? ck::scaled_exp_core(1.f, e, m) : 0.f;
     }
     const uint64_t sl = __ballot(slow);
     if (__builtin_expect(sl != 0, 0)) {
@@ -165,7 +153,7 @@ __global__ void __launch_bounds__(kThreads)
       const bool ok = n < n_end && live[n] != 0;
       float mx = -INFINITY;
       if (ok)
-        for (int k = lane; k < Ko; k += ck::kWave) mx = fmaxf(mx, stats_lg(flow[blk + n * Ko + k], vals[blk + n * Ko + k]));
+        for (int k = lane; k < Ko; k += ck::kWave) mx = fmaxf(mx, ck::flow_lg(flow[blk + n * Ko + k], vals[blk + n * Ko + k]));
       const float m = ck::wave_max(mx);
       bool slow = false;
       for (int i = lane; i < M; i += ck::kWave) {
@@ -174,14 +162,14 @@ __global__ void __launch_bounds__(kThreads)
           const float e = ck::entry_value(type, ch, H, Ki, vals, val_off, n, i);
           if (e > -INFINITY) {
             if (e + m >= kSlowShift) slow = true;
-            else g = stats_exp(1.f, e, m);
+            else g = ck::scaled_exp_core(1.f, e, m);
           }
         }
         sg[r * M + i] = g;
       }
       const bool any_slow = __ballot(slow) != 0;
       for (int k = lane; k < Ko; k += ck::kWave)
-        sa[r * Ko + k] = (m > -INFINITY && !any_slow) ? stats_a(flow[blk + n * Ko + k], vals[blk + n * Ko + k], m) : 0.f;
+        sa[r * Ko + k] = (m > -INFINITY && !any_slow) ? ck::flow_a<false>(flow[blk + n * Ko + k], vals[blk + n * Ko + k], m) : 0.f;
       if (lane == 0) ss[r] = any_slow ? 1 : 0;
     }
     __syncthreads();
@@ -355,8 +343,6 @@ __global__ void __launch_bounds__(kThreads)
     out[threadIdx.x] += t;
   }
 }
-
-int64_t blocks_of(int64_t items, int threads) { return (items + threads - 1) / threads; }
 
 // The number of row slices of a launch of `tiles` tiles over B rows: a function of (tiles, B) alone.
 int slices_of(int64_t tiles, int64_t B) {

@@ -135,7 +135,7 @@ class HipEMTrainer:
         self._es = _expected(self.circuit)
         ps = self._es.ps
         s = ps.s
-        ps.structure()
+        ps.down.structure()
         ps.tables()  # (the evaluated weights behind the support pointers exist from here on)
         dev = self.device
         with torch.cuda.device(dev):

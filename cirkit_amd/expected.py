@@ -25,8 +25,9 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .posterior import _SUM_KINDS, PosteriorState, _state, query_ids
+from .posterior import PosteriorState, _state, query_ids
 from .sampling import _is_mixing, check_plan
+from .topdown import SUM_KINDS, run_chunks
 
 if TYPE_CHECKING:  # pragma: no cover
     from .circuit import HipCircuit
@@ -112,7 +113,7 @@ class ExpectedState:
         self.unit_off = torch.from_numpy(np.concatenate(
             [self.unit_at[j] + np.arange(f, dtype=np.int64) * k for j, (f, k) in enumerate(zip(folds, units))])).to(dev)
         user = s.hc.user_plan.layers
-        self.cols = [None if "child" not in d or d["kind"] not in _SUM_KINDS else _entry_columns(d["spec"], us)
+        self.cols = [None if "child" not in d or d["kind"] not in SUM_KINDS else _entry_columns(d["spec"], us)
                      for d, us in zip(s.layers, user)]
         self.cols_d = [None if c is None else torch.from_numpy(c).to(dev) for c in self.cols]
         self._scratch: torch.Tensor | None = None
@@ -129,7 +130,7 @@ class ExpectedState:
             self._scratch = torch.empty(SCRATCH_FLOATS, dtype=torch.float32, device=s.device)
         vals, fl, vo = bd.arena.data_ptr(), flow.data_ptr(), s._val_off_table(bd).data_ptr()
         for j, d in enumerate(s.layers):
-            if d["kind"] in _SUM_KINDS:
+            if d["kind"] in SUM_KINDS:
                 capi.call("ck_stats_edge_sum", d["kind"], 1 if _is_mixing(d["spec"]) else 0, d["child"].data_ptr(),
                           d["w"].data_ptr(), d["F"], d["H"], d["Ki"], d["Ko"], d["M"], vals, fl, vo, int(s.fold_off[j]),
                           live.data_ptr(), bd.B, edge[j].data_ptr(), self._scratch.data_ptr(), SCRATCH_FLOATS, stream)
@@ -153,7 +154,7 @@ class ExpectedState:
         """Zeroed (edge, leaf, unit) accumulators in the DEVICE plan's shapes, after `PosteriorState.tables()`."""
         s = self.ps.s
         dev = s.device
-        edge = {j: torch.zeros_like(d["w"]) for j, d in enumerate(s.layers) if d["kind"] in _SUM_KINDS}
+        edge = {j: torch.zeros_like(d["w"]) for j, d in enumerate(s.layers) if d["kind"] in SUM_KINDS}
         leaf = {j: torch.zeros((d["F"], d["Ko"], 3 if d["kind"] == capi.CK_SAMPLE_GAUSSIAN else d["M"]), dtype=torch.float32,
                                device=dev) for j, d in enumerate(s.layers) if "scope" in d}
         return edge, leaf, torch.zeros(int(self.unit_at[-1]), dtype=torch.float32, device=dev)
@@ -164,33 +165,27 @@ class ExpectedState:
         running sums over several batches); otherwise they start at zero."""
         ps, s = self.ps, self.ps.s
         ids = [] if missing_vars is None else query_ids(missing_vars, s.D)  # (refusals first: nothing copied or launched)
-        if rows_per_chunk is not None and int(rows_per_chunk) <= 0:
-            raise ValueError("rows_per_chunk must be positive")
-        xm = s.evidence_batch(x, ids)
-        B = int(xm.shape[0])
-        chunks = ps.chunks_of(B, rows_per_chunk)
-        ps.tables()
-        dev = s.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def start(B: int):
+            dev = s.device
             edge, leaf, unit = self.accumulators() if into is None else into
             logev = torch.empty(B, dtype=torch.float32, device=dev)
-            bad = torch.zeros(B, dtype=torch.int32, device=dev)
             rows = torch.zeros((), dtype=torch.int64, device=dev)
             nan = torch.full((), float("nan"), device=dev)
-            for r0, nb in chunks:
-                xc = xm[r0 : r0 + nb]
-                bd = ps.evidence_forward(xc, bad[r0:], stream)
-                flow = ps.flow_pass(bd, stream)
+
+            def tail(r0, xc, bd, flow, bad, stream):
                 root = bd.views[s.root_layer][s.root_f, :, 0]
-                ok = bad[r0 : r0 + nb] == 0
+                ok = bad[: bd.B] == 0
                 live = (ok & torch.isfinite(root)).to(torch.int32)
-                logev[r0 : r0 + nb] = torch.where(ok, root, nan)
-                rows += live.sum()
+                logev[r0 : r0 + bd.B] = torch.where(ok, root, nan)
+                rows.add_(live.sum())
                 self.unit_sums(bd, flow, live, unit, stream)
                 self.edge_sums(bd, flow, live, edge, stream)
                 self.leaf_sums(bd, flow, xc, live, leaf, stream)
-        return edge, leaf, unit, logev, rows
+
+            return (edge, leaf, unit, logev, rows), tail
+
+        return run_chunks(ps, ps.down, x, ids, rows_per_chunk, ps.tables, start)
 
     def expected_statistics(self, x: torch.Tensor, missing_vars, rows_per_chunk: int | None) -> ExpectedStatistics:
         ps, s = self.ps, self.ps.s

@@ -21,63 +21,19 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .plan import Plan, resolve_fold_index
-from .sampling import Sampler, _is_mixing, check_plan, chunk_rows, sampler
+from . import topdown
+from .plan import Plan
+from .sampling import Sampler, check_plan, sampler
+from .topdown import (FLOW, QuerySets, TopDownPass, check_query, discrete_tables, leaf_entries, num_consumers,  # noqa: F401
+                      run_chunks, variable_kinds)
 
 if TYPE_CHECKING:  # pragma: no cover
     from .circuit import HipCircuit
 
-_SUM_KINDS = (capi.CK_SAMPLE_SUM, capi.CK_SAMPLE_CPT, capi.CK_SAMPLE_TUCKER)
-
 
 def consumer_lists(plan: Plan) -> list[dict | None]:
-    """Per layer (None for input layers) the consumer lists of the folds it reads, for the flow pass: ``children`` the
-    global folds it feeds, ascending; ``start`` the CSR offsets into ``items``; ``items`` what each child adds, in (fold,
-    input position) order -- a message slot for sum-type layers (sum / mixing ``f H + h``, CP-T ``f``, Tucker ``2 f + h``),
-    the consumer's global fold for Hadamard, the pair (consumer's global fold, input position) for Kronecker; ``first``
-    whether no LATER layer feeds the child (the pass walks the layers last to first: the first writer stores)."""
-    folds = [l.num_folds for l in plan.layers]
-    fold_off = np.concatenate([[0], np.cumsum(folds)]).astype(np.int64)
-    out: list[dict | None] = [None] * len(plan.layers)
-    seen: set[int] = set()
-    for j in range(len(plan.layers) - 1, -1, -1):
-        l = plan.layers[j]
-        if l.inputs is None:
-            continue
-        ch = resolve_fold_index(l.inputs, folds)  # (F, H, 2)
-        g = fold_off[ch[..., 0]] + ch[..., 1]  # (F, H) global folds
-        lists: dict[int, list] = {}
-        for f in range(l.num_folds):
-            for h in range(l.arity):
-                if l.type == "sum":
-                    item = f * l.arity + h
-                elif l.type == "cpt":
-                    item = f
-                elif l.type == "tucker":
-                    item = 2 * f + h
-                elif l.type == "hadamard":
-                    item = int(fold_off[j]) + f
-                else:  # kronecker
-                    item = (int(fold_off[j]) + f, h)
-                lists.setdefault(int(g[f, h]), []).append(item)
-        children = sorted(lists)
-        start = np.concatenate([[0], np.cumsum([len(lists[c]) for c in children])]).astype(np.int32)
-        items = np.array([it for c in children for it in lists[c]], dtype=np.int32).reshape(-1)
-        first = np.array([c not in seen for c in children], dtype=np.int32)
-        seen.update(children)
-        slots = {"sum": l.num_folds * l.arity, "cpt": l.num_folds, "tucker": 2 * l.num_folds}.get(l.type, 0)
-        out[j] = {"children": np.array(children, dtype=np.int32), "start": start, "items": items, "first": first,
-                  "slots": slots}
-    return out
-
-
-def num_consumers(plan: Plan) -> np.ndarray:
-    """(total folds) how many (fold, input position) pairs read each global fold."""
-    n = np.zeros(int(sum(l.num_folds for l in plan.layers)), dtype=np.int64)
-    for c in consumer_lists(plan):
-        if c is not None:
-            n[c["children"]] += np.diff(c["start"])
-    return n
+    """The consumer lists of the flow pass: `topdown.consumer_lists` with one CP-T message per fold."""
+    return topdown.consumer_lists(plan, False)
 
 
 def query_ids(query_vars, D: int) -> list[int]:
@@ -103,83 +59,40 @@ class PosteriorState:
 
     def __init__(self, s: Sampler) -> None:
         self.s = s
-        plan = s.plan
         self.var_folds: dict[int, list[tuple[int, int]]] = {}  # variable -> [(input layer, fold)]
-        self.gauss_var: dict[int, bool] = {}
         self.tab_off: dict[int, int] = {}  # input layer -> element offset of its block in the per-state flat tables
         n_cat = n_gauss = 0
         for j, d in enumerate(s.layers):
             if "scope" not in d:
                 continue
-            gauss = d["kind"] == capi.CK_SAMPLE_GAUSSIAN
             for f, v in enumerate(np.asarray(d["spec"].scope_idx[:, 0], dtype=np.int64)):
                 self.var_folds.setdefault(int(v), []).append((j, f))
-                self.gauss_var[int(v)] = gauss or self.gauss_var.get(int(v), False)
-            if gauss:
+            if d["kind"] == capi.CK_SAMPLE_GAUSSIAN:
                 self.tab_off[j], n_gauss = n_gauss, n_gauss + d["F"] * d["Ko"]
             else:
                 self.tab_off[j], n_cat = n_cat, n_cat + d["F"] * d["Ko"] * d["M"]
-        self.mixed_var = {v for v, fl in self.var_folds.items()
-                          if len({s.layers[j]["kind"] == capi.CK_SAMPLE_GAUSSIAN for j, _ in fl}) > 1}
-        self._lists: list[dict | None] | None = None
-        self.msg_per_row = 0
-        self._queries: dict[tuple, dict] = {}
+        self.kinds = variable_kinds(s.plan)
+        self.down = TopDownPass(s, FLOW)
+        self._queries = QuerySets(self._entries)
         self._key = None
         self._ntab: torch.Tensor | None = None
         self._mean: torch.Tensor | None = None
         self._stddev: torch.Tensor | None = None
-        self._buffers: dict[int, tuple[torch.Tensor, torch.Tensor | None]] = {}  # chunk rows -> (flow arena, messages)
-        self.bytes_per_row = 2 * s.hc.arena_bytes(1)
 
     # -- refusals: nothing is prepared or launched before them -----------------------------------------------------------
     def check_query(self, ids: list[int]) -> bool:
         """Whether the query variables are Gaussian; raises for an empty, uncovered or mixed query set."""
-        if not ids:
-            raise ValueError("posterior_marginals needs at least one query variable")
-        missing = [v for v in ids if v not in self.var_folds]
-        if missing:
-            raise ValueError(f"query variables {missing[:8]} are outside the scope of every input layer")
-        kinds = {self.gauss_var[v] for v in ids}
-        if len(kinds) > 1 or any(v in self.mixed_var for v in ids):
-            raise NotImplementedError("a query set that mixes discrete and Gaussian variables")
-        return kinds.pop()
+        return check_query(self.kinds, ids, "posterior_marginals")
 
-    # -- once per circuit --------------------------------------------------------------------------------------------
-    def structure(self) -> list[dict | None]:
-        if self._lists is None:
-            dev = self.s.device
-            lists = consumer_lists(self.s.plan)
-            for j, c in enumerate(lists):
-                if c is None:
-                    continue
-                for n in ("children", "start", "items", "first"):
-                    c[n + "_d"] = torch.from_numpy(c[n]).to(dev)
-                self.msg_per_row = max(self.msg_per_row, c["slots"] * self.s.layers[j]["Ki"])
-            self._lists = lists
-            self.bytes_per_row += 4 * self.msg_per_row
-        return self._lists
+    # -- once per query set ------------------------------------------------------------------------------------------
+    def _entries(self, ids: list[int], gauss: bool) -> dict:
+        q, e, _ = leaf_entries(self.s, self.var_folds, self.tab_off, ids, gauss)
+        ks = set(e[:, 1].tolist())  # (the matrix-core leaf kernel wants every entry with the same 32 or 64 units)
+        q["K_uniform"] = ks.pop() if len(ks) == 1 and next(iter(ks)) in (32, 64) else 0
+        return q
 
     def query_tables(self, ids: list[int], gauss: bool) -> dict:
-        key = tuple(ids)
-        q = self._queries.get(key)
-        if q is None:
-            s = self.s
-            ent, start = [], [0]
-            for v in ids:
-                for j, f in self.var_folds[v]:
-                    d = s.layers[j]
-                    K, C = d["Ko"], 1 if gauss else d["M"]
-                    ent.append((int(s.fold_off[j]) + f, K, C, self.tab_off[j] + f * K * C))
-                start.append(len(ent))
-            e = np.array(ent, dtype=np.int64)
-            ks = set(e[:, 1].tolist())
-            if len(self._queries) >= 8:  # (a handful of query sets per circuit; the tables are small but not free)
-                self._queries.pop(next(iter(self._queries)))
-            q = self._queries[key] = {
-                "entries": torch.from_numpy(e).to(s.device), "start": torch.from_numpy(np.array(start, dtype=np.int32)).to(s.device),
-                "Q": len(ids), "C": 2 if gauss else int(e[:, 2].max()),
-                "K_uniform": ks.pop() if len(ks) == 1 and next(iter(ks)) in (32, 64) else 0}
-        return q
+        return self._queries.get(ids, gauss)
 
     # -- once per parameter state ------------------------------------------------------------------------------------
     def tables(self) -> None:
@@ -190,47 +103,16 @@ class PosteriorState:
         if self._key == s._key:
             return
         dev = s.device
-        cats, means, sds = [], [], []
         with torch.cuda.device(dev):
             zero = torch.zeros((), device=dev)
-            for d in s.layers:
-                if "scope" not in d:
-                    continue
-                if d["kind"] == capi.CK_SAMPLE_GAUSSIAN:
-                    means.append(d["mean_v"].reshape(-1))
-                    sds.append(d["stddev_v"].reshape(-1))
-                    continue
-                M = d["M"]
-                if d["spec"].type == "binomial":  # prepare()'s (F, T + 2, K) log-pmf table, last row the integral
-                    t, is_log = d["tab"][:, :M, :].permute(0, 2, 1), True
-                else:  # prepare()'s (F, K, C) probabilities or logits
-                    t, is_log = d["tab"], bool(d["is_logits"])
-                if is_log:
-                    mx = t.amax(dim=2, keepdim=True)
-                    t = torch.exp(t - torch.where(torch.isfinite(mx), mx, zero))
-                tot = t.sum(dim=2, keepdim=True)
-                cats.append(torch.where(tot > 0, t / tot, zero).contiguous().reshape(-1))
+            cats = [torch.where(tot > 0, t / tot, zero).contiguous().reshape(-1) for _, t, _, tot in discrete_tables(s)]
+            gauss = [d for d in s.layers if "scope" in d and d["kind"] == capi.CK_SAMPLE_GAUSSIAN]
             self._ntab = torch.cat(cats) if cats else None
-            self._mean = torch.cat(means) if means else None
-            self._stddev = torch.cat(sds) if sds else None
+            self._mean = torch.cat([d["mean_v"].reshape(-1) for d in gauss]) if gauss else None
+            self._stddev = torch.cat([d["stddev_v"].reshape(-1) for d in gauss]) if gauss else None
         self._key = s._key
 
     # -- per chunk: the three phases (scripts/bench_posterior.py times them one by one) ------------------------------------
-    def chunks_of(self, B: int, rows_per_chunk: int | None) -> list[tuple[int, int]]:
-        """The (first row, rows) chunks of a batch, with the bindings and buffers of other sizes released (two sizes stay
-        bound: the chunk and the tail)."""
-        s = self.s
-        self.structure()
-        chunks = chunk_rows(B, rows_per_chunk, self.bytes_per_row)
-        sizes = {nb for _, nb in chunks}
-        zc = s._z_circuit()
-        for b in [b for b in zc._bindings if b != 1 and b not in sizes]:
-            zc._bindings.pop(b).destroy()
-            s._val_off.pop(b, None)
-        for b in [b for b in self._buffers if b not in sizes]:
-            del self._buffers[b]
-        return chunks
-
     def evidence_forward(self, xc: torch.Tensor, bad: torch.Tensor, stream: int):
         """The layer-wise marginal forward of a chunk of masked evidence, after its range check: an out-of-range observed
         category sets bad[n] and the flag `hc.check_inputs()` reports, and is replaced by 0 for the forward, so that the
@@ -249,33 +131,7 @@ class PosteriorState:
 
     def flow_pass(self, bd, stream: int) -> torch.Tensor:
         """The flows of every unit under the values of binding `bd`, layers last to first; returns the flow arena."""
-        s, lists = self.s, self.structure()
-        nb, dev = bd.B, s.device
-        root_ko = s.layers[s.root_layer]["Ko"]
-        buf = self._buffers.get(nb)
-        if buf is None or buf[0].numel() != bd.arena.numel():
-            msg = torch.empty(max(1, self.msg_per_row * nb), dtype=torch.float32, device=dev)
-            # zeros: a fold nothing consumes is never written and carries no flow
-            buf = self._buffers[nb] = (torch.zeros(bd.arena.numel(), dtype=torch.float32, device=dev), msg)
-        flow, msg = buf
-        vals, fl, vo = bd.arena.data_ptr(), flow.data_ptr(), s._val_off_table(bd).data_ptr()
-        r_at = (bd.views[s.root_layer].data_ptr() - vals) // 4 + s.root_f * nb * root_ko
-        root = flow[r_at : r_at + nb * root_ko].view(nb, root_ko)
-        root.zero_()
-        root[:, 0] = 1.0
-        for j in range(len(s.layers) - 1, -1, -1):
-            c, d = lists[j], s.layers[j]
-            if c is None:
-                continue
-            F, H, Ki, Ko, kind = d["F"], d["H"], d["Ki"], d["Ko"], d["kind"]
-            csr = (c["start_d"].data_ptr(), c["children_d"].data_ptr(), c["first_d"].data_ptr(), c["items_d"].data_ptr())
-            if kind in _SUM_KINDS:
-                capi.call("ck_flow_down_sum", kind, 1 if _is_mixing(d["spec"]) else 0, d["child"].data_ptr(),
-                          d["w"].data_ptr(), F, H, Ki, Ko, d["M"], vals, fl, vo, int(s.fold_off[j]), nb, msg.data_ptr(), stream)
-                capi.call("ck_flow_segment_add", msg.data_ptr(), *csr, fl, vo, len(c["children"]), Ki, nb, stream)
-            else:
-                capi.call("ck_flow_down_product", kind, *csr, fl, vo, len(c["children"]), H, Ki, Ko, nb, stream)
-        return flow
+        return self.down.run(bd, stream)
 
     def leaves(self, bd, flow: torch.Tensor, q: dict, gauss: bool, bad: torch.Tensor, out: torch.Tensor,
                logev: torch.Tensor | None, stream: int) -> None:
@@ -297,21 +153,18 @@ class PosteriorState:
         s = self.s
         ids = query_ids(query_vars, s.D)
         gauss = self.check_query(ids)  # (refusals first: nothing has been copied, prepared or launched)
-        xm = s.evidence_batch(x, ids)
-        B = int(xm.shape[0])
-        chunks = self.chunks_of(B, rows_per_chunk)
-        self.tables()
-        q = self.query_tables(ids, gauss)
-        dev = s.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            out = torch.empty((B, q["Q"], q["C"]), dtype=torch.float32, device=dev)
-            logev = torch.empty(B, dtype=torch.float32, device=dev)
-            bad = torch.zeros(B, dtype=torch.int32, device=dev)
-            for r0, nb in chunks:
-                bd = self.evidence_forward(xm[r0 : r0 + nb], bad[r0:], stream)
-                flow = self.flow_pass(bd, stream)
-                self.leaves(bd, flow, q, gauss, bad[r0:], out[r0], logev[r0:], stream)
+
+        def start(B: int):
+            q = self.query_tables(ids, gauss)
+            out = torch.empty((B, q["Q"], q["C"]), dtype=torch.float32, device=s.device)
+            logev = torch.empty(B, dtype=torch.float32, device=s.device)
+
+            def tail(r0, xc, bd, flow, bad, stream):
+                self.leaves(bd, flow, q, gauss, bad, out[r0], logev[r0:], stream)
+
+            return (out, logev), tail
+
+        out, logev = run_chunks(self, self.down, x, ids, rows_per_chunk, self.tables, start)
         return (out, logev) if return_log_evidence else out
 
 

@@ -31,7 +31,7 @@ from cirkit_amd.circuit import HipCircuit  # noqa: E402
 from cirkit_amd.expected import _expected  # noqa: E402
 from cirkit_amd.initializers import init_plan_tensors  # noqa: E402
 from cirkit_amd.plan import Plan  # noqa: E402
-from cirkit_amd.posterior import _SUM_KINDS  # noqa: E402
+from cirkit_amd.topdown import SUM_KINDS  # noqa: E402
 
 CONFIGS = {"cfg2_qt784": ("config 2", 4096), "cfg4_pd784": ("config 4", 1024)}
 MFMA_FP32_FLOPS = 157.3e12
@@ -71,7 +71,7 @@ def main() -> None:
         es = _expected(hc)
         ps, s = es.ps, es.ps.s
         xm = s.evidence_batch(x, lower)
-        chunks = ps.chunks_of(B, None)
+        chunks = ps.down.chunks_of(B, None)
         bad = torch.zeros(B, dtype=torch.int32, device=dev)
         live = torch.ones(B, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -87,9 +87,9 @@ def main() -> None:
         phases = {
             "evidence_forward_ms": lambda: [ps.evidence_forward(xm[r0 : r0 + nb], bad[r0:], stream) for r0, nb in chunks],
             "flow_pass_ms": each(lambda r0, nb, bd: ps.flow_pass(bd, stream)),
-            "unit_sums_ms": each(lambda r0, nb, bd: es.unit_sums(bd, ps._buffers[nb][0], live[r0 : r0 + nb], unit, stream)),
-            "edge_sums_ms": each(lambda r0, nb, bd: es.edge_sums(bd, ps._buffers[nb][0], live[r0 : r0 + nb], edge, stream)),
-            "leaf_sums_ms": each(lambda r0, nb, bd: es.leaf_sums(bd, ps._buffers[nb][0], xm[r0 : r0 + nb], live[r0 : r0 + nb],
+            "unit_sums_ms": each(lambda r0, nb, bd: es.unit_sums(bd, ps.down._buffers[nb][0], live[r0 : r0 + nb], unit, stream)),
+            "edge_sums_ms": each(lambda r0, nb, bd: es.edge_sums(bd, ps.down._buffers[nb][0], live[r0 : r0 + nb], edge, stream)),
+            "leaf_sums_ms": each(lambda r0, nb, bd: es.leaf_sums(bd, ps.down._buffers[nb][0], xm[r0 : r0 + nb], live[r0 : r0 + nb],
                                                                  leaf, stream)),
         }
         row = {"config": label, "plan": name, "B": B, "missing": len(lower), "chunks": len(chunks),
@@ -98,7 +98,7 @@ def main() -> None:
             row[k] = round(_time(fn, args.reps, args.warmup), 4)
         yard = row["evidence_forward_ms"] + row["flow_pass_ms"]
         stats = row["unit_sums_ms"] + row["edge_sums_ms"] + row["leaf_sums_ms"]
-        flops = sum(2.0 * B * d["F"] * d["Ko"] * d["M"] for d in s.layers if d["kind"] in _SUM_KINDS)
+        flops = sum(2.0 * B * d["F"] * d["Ko"] * d["M"] for d in s.layers if d["kind"] in SUM_KINDS)
         arena_bytes = 2.0 * hc.arena_bytes(B)
         floor = max(flops / MFMA_FP32_FLOPS, arena_bytes / HBM_BYTES_PER_S) * 1e3
         row.update({"yardstick_ms": round(yard, 4), "statistics_over_yardstick": round(stats / yard, 3),

@@ -71,7 +71,7 @@ def main() -> None:
         gauss = st.check_query(query)
         q = st.query_tables(query, gauss)
         xm = s.evidence_batch(x, [])
-        chunks = st.chunks_of(B, None)
+        chunks = st.down.chunks_of(B, None)
         bad = torch.zeros(B, dtype=torch.int32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         zc = s._z_circuit()
@@ -90,14 +90,14 @@ def main() -> None:
 
         def log_probs():
             for r0, nb in chunks:
-                st.log_probs(zc._bindings[nb], st._buffers[nb][0], xm[r0 : r0 + nb], bad[r0:], lp[r0], stream)
+                st.log_probs(zc._bindings[nb], st.down._buffers[nb][0], xm[r0 : r0 + nb], bad[r0:], lp[r0], stream)
 
         def leaves():
             for r0, nb in chunks:
-                st.leaves(zc._bindings[nb], st._buffers[nb][0], q, gauss, bad[r0:], p[r0], stream)
+                st.leaves(zc._bindings[nb], st.down._buffers[nb][0], q, gauss, bad[r0:], p[r0], stream)
 
         row = {"config": label, "plan": name, "B": B, "D": D, "query_vars": len(query), "states": int(p.shape[2]),
-               "chunks": len(chunks), "rows_per_chunk": chunks[0][1], "bytes_per_row": st.bytes_per_row,
+               "chunks": len(chunks), "rows_per_chunk": chunks[0][1], "bytes_per_row": st.down.bytes_per_row,
                "conditional_log_probs_ms": round(_time(lambda: hc.conditional_log_probs(x), args.reps, args.warmup), 4),
                "leave_one_out_ms": round(_time(lambda: hc.leave_one_out(x, query), args.reps, args.warmup), 4)}
         hc.conditional_log_probs(x)  # (the phases replay the values and derivatives of a complete-row call)

@@ -75,7 +75,7 @@ def main() -> None:
             gauss = st.check_query(query_ids(query, D))
             q = st.query_tables(query, gauss)
             xm = s.evidence_batch(x, lower)  # (the evidence of the phases: the whole lower half masked)
-            chunks = st.chunks_of(B, None)
+            chunks = st.down.chunks_of(B, None)
             bad = torch.zeros(B, dtype=torch.int32, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
             zc = s._z_circuit()
@@ -91,7 +91,7 @@ def main() -> None:
             def leaves():
                 for r0, nb in chunks:
                     bd = zc._bindings[nb]
-                    st.leaves(bd, st._buffers[nb][0], q, gauss, bad[r0:], p[r0], None, stream)
+                    st.leaves(bd, st.down._buffers[nb][0], q, gauss, bad[r0:], p[r0], None, stream)
 
             t_call = _time(lambda: hc.posterior_marginals(x, query), args.reps, args.warmup)
             t_fwd = _time(forwards, args.reps, args.warmup)
@@ -102,7 +102,7 @@ def main() -> None:
                    "states": int(p.shape[2]), "output_bytes": out_bytes, "chunks": len(chunks), "rows_per_chunk": chunks[0][1],
                    "call_ms": round(t_call, 4), "evidence_forward_ms": round(t_fwd, 4), "flow_pass_ms": round(t_flow, 4),
                    "leaf_ms": round(t_leaf, 4), "leaf_output_GB_per_s": round(out_bytes / (t_leaf * 1e-3) / 1e9, 1),
-                   "bytes_per_row": st.bytes_per_row}
+                   "bytes_per_row": st.down.bytes_per_row}
             del p
             torch.cuda.empty_cache()
             row["sample_conditional_ms"] = round(_time(lambda: hc.sample_conditional(x, mask, seed=1), args.reps, args.warmup), 4)

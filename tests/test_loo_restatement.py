@@ -113,6 +113,9 @@ def test_leave_one_out_is_the_posterior_with_the_variable_missing(name):
         assert (res["p"][:, q, post.shape[1] :] == 0).all()
 
 
+LIST_PLANS = ("plan_quadgraph_1x4x4_cp", "quadgraph_6x6_tucker_k4", "quadtree_4x4_kron_k3", "pd_gauss_6x6_k4")
+
+
 def test_message_lists_follow_the_consumer_lists():
     from cirkit_amd.leave_one_out import message_lists
     from cirkit_amd.posterior import consumer_lists
@@ -124,6 +127,62 @@ def test_message_lists_follow_the_consumer_lists():
             if a is not None:
                 for n in ("children", "start", "first"):
                     assert np.array_equal(a[n], b[n]), (name, n)
+
+
+@pytest.mark.parametrize("per_input", [False, True])
+def test_consumer_lists_hold_every_pair_once(per_input):
+    """The one list builder (cirkit_amd/topdown.py), both modes: every (consumer fold, input position) pair is decoded from
+    `items` exactly once across the layers, under the child it feeds; `first` is set on exactly the last-walked layer that
+    feeds each child; `slots` is the number of distinct message slots."""
+    from cirkit_amd.plan import resolve_fold_index
+    from cirkit_amd.topdown import consumer_lists
+
+    for name in LIST_PLANS:
+        plan = _case(name)[0]
+        folds = [l.num_folds for l in plan.layers]
+        off = np.concatenate([[0], np.cumsum(folds)])
+        lists = consumer_lists(plan, per_input)
+        assert len(lists) == len(plan.layers)
+        want, got = {}, {}  # (consumer global fold, input position) -> child global fold
+        firsts: dict[int, list[int]] = {}  # child global fold -> the layers marked `first` for it
+        feeders: dict[int, list[int]] = {}  # child global fold -> the layers that feed it
+        for j, (l, c) in enumerate(zip(plan.layers, lists)):
+            assert (c is None) == (l.inputs is None), (name, j)
+            if c is None:
+                continue
+            H, F = l.arity, l.num_folds
+            ch = resolve_fold_index(l.inputs, folds)
+            for f in range(F):
+                for h in range(H):
+                    want[(int(off[j]) + f, h)] = int(off[ch[f, h, 0]] + ch[f, h, 1])
+            children, start = c["children"].tolist(), c["start"].tolist()
+            assert children == sorted(set(children)) and start[0] == 0 and len(start) == len(children) + 1
+            pairs = l.type == "kronecker" or (l.type == "hadamard" and per_input)
+            items = c["items"].reshape(-1, 2).tolist() if pairs else c["items"].tolist()
+            assert start[-1] == len(items) == F * H, (name, j)
+            slots = set()
+            for k, child in enumerate(children):
+                feeders.setdefault(child, []).append(j)
+                if c["first"][k]:
+                    firsts.setdefault(child, []).append(j)
+                for it in items[start[k] : start[k + 1]]:
+                    if pairs:
+                        decoded = [(it[0], it[1])]
+                    elif l.type == "hadamard":  # one item per consumer fold and input position, all naming the fold
+                        decoded = [(it, h) for h in range(H) if want[(it, h)] == child and (it, h) not in got][:1]
+                    elif l.type == "cpt" and not per_input:  # slot f, shared by the fold's inputs
+                        slots.add(it)
+                        decoded = [(int(off[j]) + it, h) for h in range(H) if want[(int(off[j]) + it, h)] == child
+                                   and (int(off[j]) + it, h) not in got][:1]
+                    else:  # slot f H + h
+                        slots.add(it)
+                        decoded = [(int(off[j]) + it // H, it % H)]
+                    assert len(decoded) == 1 and decoded[0] not in got, (name, j, it)
+                    got[decoded[0]] = child
+            assert c["slots"] == len(slots), (name, j)
+        assert got == want, name
+        for child, js in feeders.items():  # the pass walks the layers last to first: the first writer is the LAST layer
+            assert firsts.get(child) == [max(js)], (name, child)
 
 
 # ------------------------------------------------------------------------------------------------------------------ zeros
