@@ -346,6 +346,10 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_stats_leaf_categorical": [_p, _p, _l, _i, _i, _p, _i, _i, _p, _p, _i, _p, _l, _p, _p],
     "ck_stats_leaf_gaussian": [_p, _p, _p, _l, _i, _p, _i, _p, _p, _i, _p, _l, _p, _p],
     "ck_stats_unit_sum": [_p, _p, _p, _p, _l, _p, _l, _p, _p],
+    "ck_interval_stage": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "ck_interval_block_sums": [_p, _p, _i, _i, _i, _p],
+    "ck_categorical_interval_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "ck_gaussian_interval_fwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ck_em_job_blocks": [_i, _l, _i],
     "ck_em_update": [_p, _p, _i, _f, _f, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],

@@ -663,14 +663,18 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             self._scratch_buf = self._new_scratch(tuck, need)
         return self._scratch_buf
 
-    def _enqueue_layers(self, bd: _Binding, stream: int, *, with_ll: bool = False) -> None:
-        """The layer kernels of one forward, in plan order (graph/modules.py:326-334)."""
+    def _enqueue_layers(self, bd: _Binding, stream: int, *, with_ll: bool = False, inputs: bool = True) -> None:
+        """The layer kernels of one forward, in plan order (graph/modules.py:326-334).  `inputs=False` (layer-wise circuits
+        only, `fuse=False`): without the launches of the data input layers, whose arena views the caller has filled itself
+        (`interval_log_prob`, cirkit_amd/interval.py)."""
+        if not inputs and (self._virtual or self._groups or self._tail or self._clin is not None):
+            raise RuntimeError("the input layers can only be left out of a layer-wise circuit (fuse=False)")
         ws = self._scratch_for(bd.B)
         if ws is None:
-            return self._enqueue_layers_(bd, stream, with_ll=with_ll)
+            return self._enqueue_layers_(bd, stream, with_ll=with_ll, inputs=inputs)
         capi.call("ck_set_workspace", ws.data_ptr(), ws.numel() * 4)
         try:
-            self._enqueue_layers_(bd, stream, with_ll=with_ll)
+            self._enqueue_layers_(bd, stream, with_ll=with_ll, inputs=inputs)
         finally:
             capi.call("ck_set_workspace", None, 0)
 
@@ -695,7 +699,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         capi.call("ck_cp_lse_fwd", bd.arena.data_ptr(), ro.data_ptr(), tab.data_ptr(), None, oo.data_ptr(),
                   bd.arena.data_ptr(), None, None, None, 0, int(ro.numel()), 1, 1, bd.B, K, stream)
 
-    def _enqueue_layers_(self, bd: _Binding, stream: int, *, with_ll: bool = False) -> None:
+    def _enqueue_layers_(self, bd: _Binding, stream: int, *, with_ll: bool = False, inputs: bool = True) -> None:
         B = bd.B
         if self._clin is not None:
             self._clin.enqueue(bd, stream)
@@ -734,7 +738,8 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             elif isinstance(l, HipConstantValueLayer):
                 l.launch_const(view, B, stream)
             elif isinstance(l, HipInputLayer):
-                l.launch_input(bd.xt if l.wants_float_input else bd.xt_i, self.plan.num_variables, view, B, stream)
+                if inputs:
+                    l.launch_input(bd.xt if l.wants_float_input else bd.xt_i, self.plan.num_variables, view, B, stream)
             else:
                 l.launch(bd.arena, ro, view, B, stream)
         if pending:
@@ -1104,6 +1109,40 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         from .expected import expected_statistics
 
         return expected_statistics(self, x, missing_vars, rows_per_chunk=rows_per_chunk)
+
+    def interval_log_prob(self, lo: torch.Tensor, hi: torch.Tensor, *, integrate_vars=None, rows_per_chunk: int | None = None):
+        """``(B, O, K)`` fp32, as `forward`: the log of the circuit integrated over a BOX per row, ``log int_box c(x) dx`` with
+        sums over the discrete variables -- row n's variable v ranges over the closed interval ``[lo[n, v], hi[n, v]]``.  Exact,
+        in one bottom-up pass: every input unit emits the log mass of its own interval, the inner layers are the layer-wise
+        forward's.  Real lse-sum circuits with Categorical / Binomial / Gaussian inputs; refused before any launch: a complex
+        semiring (``ValueError``), Embedding / ConstantValue / TensorDot layers (``TypeError``), input layers that cannot
+        integrate (``NotImplementedError``).  The reference's ``IntegrateQuery`` knows "observed" and "integrated" only.
+
+        `lo`, `hi`: ``(B, D)``, the same dtype, inclusive on both sides; int64 for an all-discrete circuit, floating point
+        otherwise (the discrete layers then read ``ceil(lo)`` and ``floor(hi)``).  A variable read by a Categorical /
+        Binomial layer of ``C`` states: ``lo < 0`` and ``hi < 0`` integrates it (the sentinel of `forward`, so
+        ``interval_log_prob(x, x)`` means what ``forward(x)`` means); otherwise the bounds are clamped into ``0 .. C - 1`` and
+        the unit emits ``log sum_c exp(table[c])`` over them (unnormalised tables included), ``-inf`` for an empty set --
+        probability 0, not an input error: `check_inputs` is not involved.  A single state emits its table entry itself and
+        the full range the layer's integral, which makes ``interval_log_prob(x, x)`` bit-identical to the layer-wise forward
+        of ``x``.  A Gaussian variable: ``log_partition + log(Phi((hi - mean) / stddev) - Phi((lo - mean) / stddev))``,
+        evaluated in fp64 and rounded once; ``+-inf`` bounds are allowed, a NaN in either bound integrates the variable,
+        ``lo >= hi`` gives ``-inf`` (a point has mass 0: these are masses, not densities).  `integrate_vars`: as in `forward`,
+        the marked entries become the full range.  A variable in no input layer's scope is ignored.
+
+        The result is the caller's own tensor (not a view of an arena).  `rows_per_chunk`: rows per pass (None: the
+        activation arena stays <= 2 GiB); results do not depend on it.  No host synchronisation (cirkit_amd/interval.py,
+        cirkit_amd/csrc/ck_interval.hip, DESIGN.md section 11 "Interval evidence")."""
+        from .interval import interval_log_prob
+
+        return interval_log_prob(self, lo, hi, integrate_vars=integrate_vars, rows_per_chunk=rows_per_chunk)
+
+    def log_cdf(self, x: torch.Tensor, *, integrate_vars=None, rows_per_chunk: int | None = None):
+        """``(B, O, K)`` fp32 ``log P(X <= x)`` per row (times the circuit's normaliser when it is not normalised):
+        ``interval_log_prob(lo, x)`` with ``lo`` 0 for an integer batch and ``-inf`` for a floating-point one."""
+        from .interval import log_cdf
+
+        return log_cdf(self, x, integrate_vars=integrate_vars, rows_per_chunk=rows_per_chunk)
 
     def log_likelihood_sum(self, x: torch.Tensor, out: torch.Tensor | None = None, *, reduce: bool = False) -> torch.Tensor:
         """Device tensor ``[sum_b log p(x_b), B]`` in fp64 -- the two numbers the data-parallel

@@ -182,6 +182,7 @@ class Sampler:
         self._desc: np.ndarray | None = None
         self._mpe = None  # the `MPEState` (cirkit_amd/mpe.py), built by the first `mpe` call
         self._posterior = None  # the `PosteriorState` (cirkit_amd/posterior.py), built by the first `posterior_marginals` call
+        self._interval = None  # the `IntervalState` (cirkit_amd/interval.py), built by the first `interval_log_prob` call
 
     # -- once per parameter state ------------------------------------------------------------------------------------
     def _z_circuit(self):

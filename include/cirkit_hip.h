@@ -1374,6 +1374,32 @@ int ck_em_job_blocks(int kind, int64_t rows, int len);
  * float atomics; s = (sigma - lo) / (hi - lo) and p are clamped into [2^-24, 1 - 2^-24] before log s - log1p(-s). */
 int ck_em_update(const ck_em_job* jobs, const ck_em_job* device_jobs, int njobs, float step_size, float pseudocount, void* stream);
 
+/* ---- interval evidence ("Interval evidence"; additive, ABI 51) ---------------------------------------
+ * Every variable of a row carries a closed interval [lo, hi]; an input unit emits the log of the mass of its interval.
+ *
+ * ck_interval_stage: the (B, D) bounds -- int64, or fp32 with is_float != 0 -- become (D, B) staging copies with the
+ * contract's rules applied once.  (lo_i, hi_i) int32, for the discrete layers (NULL: none): both bounds negative, or a NaN
+ * in either, is (-1, -1) = integrated; otherwise ceil(lo) / floor(hi) of floating-point bounds, clamped into
+ * 0 .. num_states[d] - 1 (num_states NULL or 0: only lo is clamped at 0); an empty set is (1, 0).  (lo_f, hi_f) fp32, for
+ * the Gaussian layers (NULL: none): the bounds themselves, both NaN where either was. */
+int ck_interval_stage(const void* lo, const void* hi, int is_float, int B, int D, const int32_t* num_states, int32_t* lo_i,
+                      int32_t* hi_i, float* lo_f, float* hi_f, void* stream);
+/* Once per parameter state: side (F, ceil(C / 16), 2, K) of a (F, C+1, K) log table -- per aligned block of 16 states and
+ * unit, row 0 the maximum m of the block's log terms and row 1 sum_c exp(t_c - m) (m = -inf: 0). */
+int ck_interval_block_sums(const float* table, float* side, int F, int C, int K, void* stream);
+/* out (F, B, K) = log sum_{c = lo .. hi} exp(table[f, c, k]) for the staged bounds of variable scope[f]: (-1, -1) or the
+ * full range 0 .. C - 1 (C > 1) copies the integral row C, lo == hi copies row lo, lo > hi gives -inf; any other range is
+ * summed from non-negative terms only -- at most 15 head states, whole blocks of `side`, at most 15 tail states, relative
+ * to their common maximum; a range of -inf terms gives -inf.  hi is clamped to C - 1 for memory safety. */
+int ck_categorical_interval_fwd(const float* table, const float* side, const int32_t* lo, const int32_t* hi,
+                                const int64_t* scope, float* out, int F, int B, int K, int C, int D, void* stream);
+/* out (F, B, K) = log_partition (or 0) + log(Phi((hi - mean) / stddev) - Phi((lo - mean) / stddev)), the mass evaluated in
+ * fp64 as (erfc(-b / sqrt 2) - erfc(-a / sqrt 2)) / 2 after (a, b) -> (-b, -a) where a + b > 0, rounded once to fp32.
+ * lo / hi: (D, B) fp32 of ck_interval_stage; +-inf allowed; NaN = integrated (log_partition or 0); lo >= hi gives -inf
+ * (a point has mass 0); a mass that underflows fp64 gives -inf. */
+int ck_gaussian_interval_fwd(const float* mean, const float* stddev, const float* log_partition, const float* lo,
+                             const float* hi, const int64_t* scope, float* out, int F, int B, int K, int D, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
