@@ -1345,24 +1345,13 @@ int ck_debug_force_generic_bwd(int on) {
 int ck_fill_f32(float* p, int64_t n, float value, void* stream) {
   CK_REQUIRE(p != nullptr && n > 0, "ck_fill_f32: bad arguments");
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(fill_kernel, grid, block, 0, s, p, n, value, static_cast<int32_t*>(nullptr), static_cast<int32_t*>(nullptr),
-                           static_cast<int32_t*>(nullptr), static_cast<ck_opt_state*>(nullptr));
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(fill_kernel, grid, block, 0, stream, p, n, value, nullptr, nullptr, nullptr, nullptr);
 }
 
 int ck_fill_latch(float* p, int64_t n, float value, int32_t* src, int32_t* step_flag, int32_t* sticky, ck_opt_state* opt, void* stream) {
   CK_REQUIRE(p != nullptr && n > 0 && src && step_flag && sticky, "ck_fill_latch: bad arguments");
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(fill_kernel, grid, block, 0, s, p, n, value, src, step_flag, sticky, opt);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(fill_kernel, grid, block, 0, stream, p, n, value, src, step_flag, sticky, opt);
 }
 
 int ck_gaussian_bwd(const float* gout, const float* xt, const int64_t* scope, const float* mean, const float* stddev,
@@ -1372,12 +1361,7 @@ int ck_gaussian_bwd(const float* gout, const float* xt, const int64_t* scope, co
   const int kk = K <= 256 ? K : 256;
   const size_t lds = static_cast<size_t>(2) * (256 / kk) * kk * sizeof(float);
   dim3 grid(F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gaussian_bwd_kernel, grid, block, lds, s, gout, xt, scope, mean, stddev, dmean, dstddev, B, K);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gaussian_bwd_kernel, grid, block, lds, stream, gout, xt, scope, mean, stddev, dmean, dstddev, B, K);
 }
 
 int ck_mixing_lse_bwd(const float* arena, float* garena, const int64_t* row_off, const int64_t* grad_row_off,
@@ -1394,27 +1378,16 @@ int ck_mixing_lse_bwd(const float* arena, float* garena, const int64_t* row_off,
     int rpb = 16;  // rows per workgroup: more amortise the final atomics, fewer fill the chip when there are few folds
     while (rpb < 512 && static_cast<int64_t>(F) * ((B + 2 * rpb - 1) / (2 * rpb)) >= 2048) rpb *= 2;
     dim3 grid((B + rpb - 1) / rpb, F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          if (H <= 4)
-            hipLaunchKernelGGL(mixing_bwd_reg_kernel<4>, grid, block, 0, s, arena, garena, row_off, grow, mw, gout, dmw, H, B, K, rpb, accumulate);
-          else if (H <= 8)
-            hipLaunchKernelGGL(mixing_bwd_reg_kernel<8>, grid, block, 0, s, arena, garena, row_off, grow, mw, gout, dmw, H, B, K, rpb, accumulate);
-          else
-            hipLaunchKernelGGL(mixing_bwd_reg_kernel<16>, grid, block, 0, s, arena, garena, row_off, grow, mw, gout, dmw, H, B, K, rpb, accumulate);
-          return hipGetLastError();
-        },
-        stream);
+    decltype(&mixing_bwd_reg_kernel<4>) kern;
+    if (H <= 4) kern = mixing_bwd_reg_kernel<4>;
+    else if (H <= 8) kern = mixing_bwd_reg_kernel<8>;
+    else kern = mixing_bwd_reg_kernel<16>;
+    return ck::launch(kern, grid, block, 0, stream, arena, garena, row_off, grow, mw, gout, dmw, H, B, K, rpb, accumulate);
   }
   const int rows_per_block = 64;
   dim3 grid((B + rows_per_block - 1) / rows_per_block, F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(mixing_bwd_kernel, grid, block, lds, s, arena, garena, row_off, grow, mw, gout, dmw, H, B, K,
-                           rows_per_block, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(mixing_bwd_kernel, grid, block, lds, stream, arena, garena, row_off, grow, mw, gout, dmw, H, B, K,
+                    rows_per_block, accumulate);
 }
 
 int ck_param_scaled_sigmoid_bwd(const float* y, const float* dy, float* dx, int64_t n, float vmin, float vmax,
@@ -1422,24 +1395,14 @@ int ck_param_scaled_sigmoid_bwd(const float* y, const float* dy, float* dx, int6
   CK_REQUIRE(y && dy && dx && n > 0, "ck_param_scaled_sigmoid_bwd: bad arguments");
   CK_REQUIRE(vmax > vmin, "ck_param_scaled_sigmoid_bwd: vmax must exceed vmin");
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(scaled_sigmoid_bwd_kernel, grid, block, 0, s, y, dy, dx, n, vmin, vmax, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(scaled_sigmoid_bwd_kernel, grid, block, 0, stream, y, dy, dx, n, vmin, vmax, accumulate);
 }
 
 int ck_param_softmax_bwd_strided(const float* y, const float* dy, float* dx, int64_t outer, int len, int64_t inner, int log_space,
                                  int accumulate, void* stream) {
   CK_REQUIRE(y && dy && dx && outer > 0 && len > 0 && inner > 0, "ck_param_softmax_bwd_strided: bad arguments");
   dim3 grid(grid1(outer * inner)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(softmax_bwd_strided_kernel, grid, block, 0, s, y, dy, dx, outer, len, inner, log_space, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(softmax_bwd_strided_kernel, grid, block, 0, stream, y, dy, dx, outer, len, inner, log_space, accumulate);
 }
 
 int ck_param_unary_bwd(int op, const float* x, const float* y, const float* dy, float* dx, int64_t n, int accumulate, void* stream) {
@@ -1448,24 +1411,14 @@ int ck_param_unary_bwd(int op, const float* x, const float* y, const float* dy, 
                  op == CK_UNARY_SOFTPLUS,
              "ck_param_unary_bwd: op %d (scaled sigmoid: ck_param_scaled_sigmoid_bwd)", op);
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(unary_bwd_kernel, grid, block, 0, s, op, x, y, dy, dx, n, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(unary_bwd_kernel, grid, block, 0, stream, op, x, y, dy, dx, n, accumulate);
 }
 
 int ck_param_mixing_weight_bwd(const float* dy, float* dx, int F, int K, int H, int accumulate, void* stream) {
   CK_REQUIRE(dy && dx && F > 0 && K > 0 && H > 0, "ck_param_mixing_weight_bwd: bad arguments");
   const int64_t n = static_cast<int64_t>(F) * K * H;
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(mixing_weight_bwd_kernel, grid, block, 0, s, dy, dx, n, K, H, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(mixing_weight_bwd_kernel, grid, block, 0, stream, dy, dx, n, K, H, accumulate);
 }
 
 int ck_param_scatter_add_folds(const float* dsrc, const int64_t* idx, float* ddst, int64_t n, int64_t per_fold,
@@ -1473,23 +1426,13 @@ int ck_param_scatter_add_folds(const float* dsrc, const int64_t* idx, float* dds
   CK_REQUIRE(dsrc && idx && ddst && n > 0 && per_fold > 0, "ck_param_scatter_add_folds: bad arguments");
   CK_REQUIRE(n <= 65535, "ck_param_scatter_add_folds: n exceeds grid.y");
   dim3 grid(grid1(per_fold, 64), static_cast<unsigned>(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(scatter_add_folds_kernel, grid, block, 0, s, dsrc, idx, ddst, per_fold);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(scatter_add_folds_kernel, grid, block, 0, stream, dsrc, idx, ddst, per_fold);
 }
 
 int ck_axpy_f32(float* y, const float* x, float a, int64_t n, void* stream) {
   CK_REQUIRE(y && x && n > 0, "ck_axpy_f32: bad arguments");
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(axpy_kernel, grid, block, 0, s, y, x, a, n);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(axpy_kernel, grid, block, 0, stream, y, x, a, n);
 }
 
 int ck_segment_add_rows(const float* tmp, const int32_t* cptr, const int32_t* clist, const int64_t* coff, float* garena,
@@ -1500,12 +1443,7 @@ int ck_segment_add_rows(const float* tmp, const int32_t* cptr, const int32_t* cl
   CK_REQUIRE((block_elems & 3) != 0 || (ck::aligned16(tmp) && ck::aligned16(garena)), "ck_segment_add_rows: unaligned buffers");
   const int64_t work = (block_elems & 3) == 0 ? block_elems >> 2 : block_elems;
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((work + 255) / 256, 4096)), n_child), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(segment_add_kernel, grid, block, 0, s, tmp, cptr, clist, coff, garena, block_elems);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(segment_add_kernel, grid, block, 0, stream, tmp, cptr, clist, coff, garena, block_elems);
 }
 
 int ck_sum_lse_bwd(const float* arena, float* garena, const int64_t* row_off, const int64_t* grad_row_off, const float* w,
@@ -1520,12 +1458,8 @@ int ck_sum_lse_bwd(const float* arena, float* garena, const int64_t* row_off, co
   if ((mode == CK_SUM_PROD || H == 1) && Ki == kK && Ko == 1 && !g_bwd_force_generic) {
     const int rpb = 256;  // rows per block of 32 half-waves (8 rows each)
     dim3 grid((B + rpb - 1) / rpb, F), block(1024);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(sum_lse_bwd_scalar32, grid, block, 0, s, arena, garena, row_off, grow, w, gout, dw, H, B, rpb, accumulate);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(sum_lse_bwd_scalar32, grid, block, 0, stream, arena, garena, row_off, grow, w, gout, dw, H, B, rpb,
+                      accumulate);
   }
   if ((mode == CK_SUM_PROD || H == 1) && Ki == kK && Ko == kK && !g_bwd_force_generic && ck::aligned16(arena) &&
       ck::aligned16(garena) && ck::aligned16(w) && ck::aligned16(gout)) {
@@ -1536,12 +1470,8 @@ int ck_sum_lse_bwd(const float* arena, float* garena, const int64_t* row_off, co
     while (tpw < 8 && 4 * tpw * 2 <= tiles && static_cast<int64_t>(F) * ((tiles + 4 * tpw * 2 - 1) / (4 * tpw * 2)) >= 2048)
       tpw *= 2;
     dim3 grid((tiles + 4 * tpw - 1) / (4 * tpw), F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(sum_lse_bwd_tile32, grid, block, 0, s, arena, garena, row_off, grow, w, gout, dw, H, B, tpw, accumulate);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(sum_lse_bwd_tile32, grid, block, 0, stream, arena, garena, row_off, grow, w, gout, dw, H, B, tpw,
+                      accumulate);
   }
   if ((mode == CK_SUM_PROD || H == 1) && Ki == 64 && Ko == 64 && !g_bwd_force_generic && ck::aligned16(arena) &&
       ck::aligned16(garena) && ck::aligned16(w) && ck::aligned16(gout)) {
@@ -1612,12 +1542,7 @@ int ck_kronecker_bwd(float* garena, const int64_t* row_off, const float* gout, i
   const int64_t words = static_cast<int64_t>(B) * H * K;
   dim3 grid(grid1(words), F), block(256);
   const int n = static_cast<int>(N);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(kronecker_bwd_kernel, grid, block, 0, s, garena, row_off, gout, H, B, K, n, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(kronecker_bwd_kernel, grid, block, 0, stream, garena, row_off, gout, H, B, K, n, accumulate);
 }
 
 int ck_hadamard_bwd(float* garena, const int64_t* row_off, const float* gout, int F, int H, int B, int K,
@@ -1628,12 +1553,7 @@ int ck_hadamard_bwd(float* garena, const int64_t* row_off, const float* gout, in
   CK_REQUIRE(F <= 65535, "ck_hadamard_bwd: F=%d exceeds grid.y", F);
   const int64_t words = static_cast<int64_t>(B) * K;
   dim3 grid(grid1(words), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(hadamard_bwd_kernel, grid, block, 0, s, garena, row_off, gout, H, words, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(hadamard_bwd_kernel, grid, block, 0, stream, garena, row_off, gout, H, words, accumulate);
 }
 
 int ck_categorical_bwd(const float* gout, const int32_t* gfold, const int32_t* xt, const int64_t* scope, float* dtable, int F,
@@ -1703,24 +1623,14 @@ int ck_param_softmax_bwd(const float* w, const float* dw, float* dtheta, int64_t
   CK_REQUIRE(w && dw && dtheta, "ck_param_softmax_bwd: null pointer");
   CK_REQUIRE(rows > 0 && len > 0, "ck_param_softmax_bwd: non-positive size");
   dim3 grid(static_cast<unsigned>((rows + 3) / 4)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(softmax_bwd_rows_kernel, grid, block, 0, s, w, dw, dtheta, rows, len, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(softmax_bwd_rows_kernel, grid, block, 0, stream, w, dw, dtheta, rows, len, accumulate);
 }
 
 int ck_param_softmax_bwd_batch(const ck_softmax_bwd_job* jobs, int n_jobs, int n_blocks, const ck_opt_state* opt, void* stream) {
   CK_REQUIRE(jobs != nullptr && n_jobs > 0 && n_blocks > 0, "ck_param_softmax_bwd_batch: bad arguments");
   static_assert(sizeof(SoftmaxBwdJob) == sizeof(ck_softmax_bwd_job), "job layout");
   dim3 grid(static_cast<unsigned>(n_blocks)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(softmax_bwd_batch_kernel, grid, block, 0, s, reinterpret_cast<const SoftmaxBwdJob*>(jobs), n_jobs, opt);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(softmax_bwd_batch_kernel, grid, block, 0, stream, reinterpret_cast<const SoftmaxBwdJob*>(jobs), n_jobs, opt);
 }
 
 int ck_param_log_table_bwd(const float* table, const float* dtable, float* dtheta, int F, int K, int C,
@@ -1749,77 +1659,43 @@ int ck_adam_step(float* p, const float* g, float* m1, float* m2, int64_t n, floa
   CK_REQUIRE(p && g && m1 && m2, "ck_adam_step: null pointer");
   CK_REQUIRE(n > 0 && step > 0, "ck_adam_step: n and step must be positive");
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(adam_kernel, grid, block, 0, s, p, g, m1, m2, n, lr, beta1, beta2, eps, step, grad_scale, skip_flag, skipped);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(adam_kernel, grid, block, 0, stream, p, g, m1, m2, n, lr, beta1, beta2, eps, step, grad_scale, skip_flag,
+                    skipped);
 }
 
 int ck_sgd_step(float* p, const float* g, int64_t n, float lr, float grad_scale, const int32_t* skip_flag, void* stream) {
   CK_REQUIRE(p && g, "ck_sgd_step: null pointer");
   CK_REQUIRE(n > 0, "ck_sgd_step: n must be positive");
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(sgd_kernel, grid, block, 0, s, p, g, n, lr, grad_scale, skip_flag);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(sgd_kernel, grid, block, 0, stream, p, g, n, lr, grad_scale, skip_flag);
 }
 
 int ck_copy_strided_f32(const float* src, float* dst, int64_t n, int64_t src_stride, int64_t dst_stride, void* stream) {
   CK_REQUIRE(src && dst && n > 0 && src_stride > 0 && dst_stride > 0, "ck_copy_strided_f32: bad arguments");
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(copy_strided_kernel, grid, block, 0, s, src, dst, n, src_stride, dst_stride);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(copy_strided_kernel, grid, block, 0, stream, src, dst, n, src_stride, dst_stride);
 }
 
 int ck_fill_strided_f32(float* p, int64_t n, int64_t stride, float value, void* stream) {
   CK_REQUIRE(p && n > 0 && stride > 0, "ck_fill_strided_f32: bad arguments");
   dim3 grid(grid1(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(fill_strided_kernel, grid, block, 0, s, p, n, stride, value);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(fill_strided_kernel, grid, block, 0, stream, p, n, stride, value);
 }
 
 int ck_embedding_weight_bwd(const float* table, const float* dtable, float* dw, int F, int C, int K, void* stream) {
   CK_REQUIRE(table && dtable && dw && F > 0 && F <= 65535 && C > 0 && K > 0, "ck_embedding_weight_bwd: bad arguments");
   dim3 grid(static_cast<unsigned>(std::min((K * C + 255) / 256, 64)), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(embedding_weight_bwd_kernel, grid, block, 0, s, table, dtable, dw, C, K);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(embedding_weight_bwd_kernel, grid, block, 0, stream, table, dtable, dw, C, K);
 }
 
 int ck_squared_ll(const float* yc, int64_t B, int64_t stride, const float* z, double* out, void* stream) {
   CK_REQUIRE(yc && z && out && B > 0 && stride > 0, "ck_squared_ll: bad arguments");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(squared_ll_kernel, dim3(1), dim3(1024), 0, s, yc, B, stride, z, out);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(squared_ll_kernel, dim3(1), dim3(1024), 0, stream, yc, B, stride, z, out);
 }
 
 int ck_latch_flag(int32_t* src, int32_t* dst, void* stream) {
   CK_REQUIRE(src && dst, "ck_latch_flag: null pointer");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(latch_flag_kernel, dim3(1), dim3(1), 0, s, src, dst);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(latch_flag_kernel, dim3(1), dim3(1), 0, stream, src, dst);
 }
 
 }  // extern "C"

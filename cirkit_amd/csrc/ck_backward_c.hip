@@ -883,13 +883,9 @@ extern "C" int ck_sum_lse_bwd_c(const float* arena_c, float* garena_c, const int
       ck::aligned16(out_c) && ck::aligned16(gout_c)) {  // (offsets in row_off are multiples of 32 complex numbers per row)
     const int tiles = (B + 31) / 32;
     const dim3 grid(static_cast<unsigned>(std::max(1, std::min((tiles + 3) / 4, 16))), F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(sum_clse_bwd_tile32, grid, block, 0, s, reinterpret_cast<const ck::c32*>(arena_c), reinterpret_cast<ck::c32*>(garena_c),
-                             row_off, w, reinterpret_cast<const ck::c32*>(out_c), reinterpret_cast<const ck::c32*>(gout_c), dw, H, B);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(sum_clse_bwd_tile32, grid, block, 0, stream, reinterpret_cast<const ck::c32*>(arena_c),
+                      reinterpret_cast<ck::c32*>(garena_c), row_off, w, reinterpret_cast<const ck::c32*>(out_c),
+                      reinterpret_cast<const ck::c32*>(gout_c), dw, H, B);
   }
   int64_t N = Ki;
   if (mode == CK_SUM_CAT) N = static_cast<int64_t>(H) * Ki;

@@ -420,15 +420,8 @@ int ck_clin_table(const float* w, int w_is_complex, float* table, int32_t* table
   CK_REQUIRE(F > 0 && C > 0, "ck_clin_table: non-positive size");
   const size_t lds = static_cast<size_t>(w_is_complex ? 2 : 1) * 32 * (C + 1) * sizeof(float);
   if (lds > 150 * 1024) return ck::fail(CK_ERR_UNSUPPORTED, "ck_clin_table: %d categories do not fit in LDS", C);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        if (w_is_complex)
-          hipLaunchKernelGGL(clin_table_kernel<true>, dim3(F), dim3(256), lds, s, w, table, table_e, C);
-        else
-          hipLaunchKernelGGL(clin_table_kernel<false>, dim3(F), dim3(256), lds, s, w, table, table_e, C);
-        return hipGetLastError();
-      },
-      stream);
+  auto kern = w_is_complex ? clin_table_kernel<true> : clin_table_kernel<false>;
+  return ck::launch(kern, dim3(F), dim3(256), lds, stream, w, table, table_e, C);
 }
 
 int ck_clin_leaf_fwd(const float* table, const int32_t* table_e, const int32_t* xt, const int64_t* x_rows, int x_input, int n_vars,
@@ -492,15 +485,8 @@ int ck_clin_layer_fwd(const float* lin, const int32_t* lin_e, const int64_t* chi
   CK_REQUIRE(F > 0 && B > 0 && H >= 1 && Ko >= 1 && Ko <= 32, "ck_clin_layer_fwd: bad sizes (H >= 1, 1 <= Ko <= 32)");
   LayerArgs a{lin, lin_e, child_off, child_eoff, w, out, out_e, out_log, F, H, Ko, B, (B + 31) / 32};
   const dim3 grid(static_cast<unsigned>(((a.tiles + 3) / 4) * ((F + 7) / 8 * 8))), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        if (w_is_complex)
-          hipLaunchKernelGGL(clin_layer_kernel<WCplx>, grid, block, 0, s, a);
-        else
-          hipLaunchKernelGGL(clin_layer_kernel<WReal>, grid, block, 0, s, a);
-        return hipGetLastError();
-      },
-      stream);
+  auto kern = w_is_complex ? clin_layer_kernel<WCplx> : clin_layer_kernel<WReal>;
+  return ck::launch(kern, grid, block, 0, stream, a);
 }
 
 int ck_clin_tail_fwd(float* lin, int32_t* lin_e, const void* folds, const int32_t* level_off, int n_levels, int w_is_complex, int B,
@@ -510,15 +496,8 @@ int ck_clin_tail_fwd(float* lin, int32_t* lin_e, const void* folds, const int32_
   static_assert(sizeof(TailFold) == 72, "ck_clin_tail_fold of include/cirkit_hip.h");
   TailArgs a{lin, lin_e, static_cast<const TailFold*>(folds), level_off, n_levels, B, (B + 31) / 32};
   const dim3 grid(a.tiles), block(kTailWaves * 64);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        if (w_is_complex)
-          hipLaunchKernelGGL(clin_tail_kernel<WCplx>, grid, block, 0, s, a);
-        else
-          hipLaunchKernelGGL(clin_tail_kernel<WReal>, grid, block, 0, s, a);
-        return hipGetLastError();
-      },
-      stream);
+  auto kern = w_is_complex ? clin_tail_kernel<WCplx> : clin_tail_kernel<WReal>;
+  return ck::launch(kern, grid, block, 0, stream, a);
 }
 
 }  // extern "C"

@@ -1059,15 +1059,8 @@ int cat_dense(const float* arena, const int64_t* row_off, const float* w, float*
     }
   }
   dim3 grid((tiles + WAVES - 1) / WAVES, F), block(WAVES * 64);  // (exact fp32 whatever `contraction` says)
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        if (K == 64)
-          hipLaunchKernelGGL((cat_lse_kernel<2, WAVES>), grid, block, 0, s, arena, row_off, w, out, H, B);
-        else
-          hipLaunchKernelGGL((cat_lse_kernel<1, WAVES>), grid, block, 0, s, arena, row_off, w, out, H, B);
-        return hipGetLastError();
-      },
-      stream);
+  auto kern = K == 64 ? cat_lse_kernel<2, WAVES> : cat_lse_kernel<1, WAVES>;
+  return ck::launch(kern, grid, block, 0, stream, arena, row_off, w, out, H, B);
 }
 
 // K = 64 dense / CP-T layers of ck_sum_lse_fwd (one slot, contiguous (F, K, K) weights).

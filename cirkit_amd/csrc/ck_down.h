@@ -205,17 +205,9 @@ int launch_down_sum(const char* fn, int type, int diag, const int32_t* child, co
     const int64_t row_tiles = (B + 31) / 32;
     const int64_t blocks = blocks_of(F * row_tiles, kWaves);
     CK_REQUIRE(blocks <= 0x7fffffff, "%s: grid too large", fn);
-    return dispatch(
-        [=](hipStream_t s) {
-          if (Ko == 32)
-            hipLaunchKernelGGL((down_sum_mfma<P, 32>), dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, type, child, w,
-                               F, H, Ki, M, vals, arena, val_off, fold_off, B, row_tiles, msg);
-          else
-            hipLaunchKernelGGL((down_sum_mfma<P, 64>), dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, type, child, w,
-                               F, H, Ki, M, vals, arena, val_off, fold_off, B, row_tiles, msg);
-          return hipGetLastError();
-        },
-        stream);
+    auto kern = Ko == 32 ? down_sum_mfma<P, 32> : down_sum_mfma<P, 64>;
+    return launch(kern, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, type, child, w, F, H, Ki, M, vals, arena,
+                  val_off, fold_off, B, row_tiles, msg);
   }
   const int64_t per_row = static_cast<int64_t>(Ko) + 1 + (type == CK_SAMPLE_TUCKER ? M : 0);
   int TR = 16;
@@ -224,13 +216,8 @@ int launch_down_sum(const char* fn, int type, int diag, const int32_t* child, co
   const int64_t row_tiles = (B + TR - 1) / TR;
   CK_REQUIRE(F * row_tiles <= 0x7fffffff, "%s: grid too large", fn);
   const size_t lds = static_cast<size_t>(TR * per_row * 4);
-  return dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(down_sum_generic<P>, dim3(static_cast<unsigned>(F * row_tiles)), dim3(kThreads), lds, s, type, diag,
-                           child, w, F, H, Ki, Ko, M, vals, arena, val_off, fold_off, B, TR, row_tiles, msg);
-        return hipGetLastError();
-      },
-      stream);
+  return launch(down_sum_generic<P>, dim3(static_cast<unsigned>(F * row_tiles)), dim3(kThreads), lds, stream, type, diag, child,
+                w, F, H, Ki, Ko, M, vals, arena, val_off, fold_off, B, TR, row_tiles, msg);
 }
 
 template <class P>
@@ -243,13 +230,8 @@ int launch_segment(const char* fn, const float* src, int src_is_arena, const int
   CK_REQUIRE(n_child > 0 && Ki > 0 && B > 0, "%s: non-positive size", fn);
   const int64_t blocks = blocks_of(n_child * B * Ki, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "%s: too many entries", fn);
-  return dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(segment_combine<P>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, src, src_is_arena, cstart,
-                           cfold, cfirst, items, arena, val_off, n_child, Ki, B);
-        return hipGetLastError();
-      },
-      stream);
+  return launch(segment_combine<P>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, src, src_is_arena, cstart,
+                cfold, cfirst, items, arena, val_off, n_child, Ki, B);
 }
 
 // The unit counts of a product layer: Hadamard Ko = Ki, Kronecker Ko = Ki^H.

@@ -109,10 +109,5 @@ extern "C" int ck_param_einsum(const ck_einsum_desc* d, void* stream) {
   CK_REQUIRE(!any_complex || d->out_complex, "ck_param_einsum: complex operands need a complex output");
   a.total = a.per_fold_out * d->F;
   const dim3 grid(static_cast<unsigned>((a.total + 255) / 256)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(einsum_kernel, grid, block, 0, s, a);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(einsum_kernel, grid, block, 0, stream, a);
 }

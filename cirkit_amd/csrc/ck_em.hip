@@ -196,13 +196,8 @@ int ck_em_update(const ck_em_job* jobs, const ck_em_job* device_jobs, int njobs,
     blocks += job_blocks(j.kind, j.rows, j.len);
     CK_REQUIRE(blocks <= 0x7fffffff, "ck_em_update: grid too large");
   }
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(em_update_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, device_jobs, njobs, step_size,
-                           pseudocount);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(em_update_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, device_jobs, njobs,
+                    step_size, pseudocount);
 }
 
 }  // extern "C"

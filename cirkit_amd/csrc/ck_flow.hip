@@ -260,13 +260,8 @@ int ck_flow_down_product(int type, const int32_t* cstart, const int32_t* cfold, 
                                         B, stream);
   const int64_t blocks = blocks_of(n_child * B * Ki, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_flow_down_product: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(flow_kron_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, cstart, cfold, cfirst,
-                           items, flow, val_off, n_child, H, Ki, Ko, B);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(flow_kron_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, cstart, cfold, cfirst,
+                    items, flow, val_off, n_child, H, Ki, Ko, B);
 }
 
 // The (B,) log evidence behind a leaf launch (logev may be NULL).
@@ -274,13 +269,8 @@ static int launch_logev(const float* vals, const int64_t* val_off, int root_fold
                         float* logev, void* stream) {
   if (logev == nullptr) return 0;
   const int64_t blocks = blocks_of(B, kThreads);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(flow_logev_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, vals, val_off, root_fold,
-                           root_ko, bad, B, logev);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(flow_logev_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, vals, val_off, root_fold,
+                    root_ko, bad, B, logev);
 }
 
 int ck_flow_check_evidence(const void* ev, int x_float, const int32_t* states, int64_t B, int D, void* clean, int32_t* bad,
@@ -289,13 +279,8 @@ int ck_flow_check_evidence(const void* ev, int x_float, const int32_t* states, i
   CK_REQUIRE(B > 0 && D > 0, "ck_flow_check_evidence: non-positive size");
   const int64_t blocks = blocks_of(B * D, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_flow_check_evidence: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(flow_check_evidence_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, ev, x_float,
-                           states, B, D, clean, bad, flag);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(flow_check_evidence_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, ev, x_float,
+                    states, B, D, clean, bad, flag);
 }
 
 int ck_flow_leaf_categorical(const int64_t* entries, const int32_t* qstart, int Q, int Cout, int K_uniform, const float* ntab,
@@ -312,27 +297,14 @@ int ck_flow_leaf_categorical(const int64_t* entries, const int32_t* qstart, int 
     const int64_t row_tiles = (B + 31) / 32;
     CK_REQUIRE(Q * row_tiles <= 0x7fffffff, "ck_flow_leaf_categorical: grid too large");
     const dim3 grid(static_cast<unsigned>(Q * row_tiles));
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          if (K_uniform == 32)
-            hipLaunchKernelGGL(flow_leaf_cat_mfma<32>, grid, dim3(kThreads), 0, s, ent, qstart, Q, Cout, ntab, flow, vals, val_off,
-                               root_fold, root_ko, bad, B, row_tiles, out);
-          else
-            hipLaunchKernelGGL(flow_leaf_cat_mfma<64>, grid, dim3(kThreads), 0, s, ent, qstart, Q, Cout, ntab, flow, vals, val_off,
-                               root_fold, root_ko, bad, B, row_tiles, out);
-          return hipGetLastError();
-        },
-        stream);
+    auto kern = K_uniform == 32 ? flow_leaf_cat_mfma<32> : flow_leaf_cat_mfma<64>;
+    return ck::launch(kern, grid, dim3(kThreads), 0, stream, ent, qstart, Q, Cout, ntab, flow, vals, val_off, root_fold, root_ko,
+                      bad, B, row_tiles, out);
   }
   const int64_t blocks = blocks_of(B * Q * Cout, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_flow_leaf_categorical: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(flow_leaf_cat_generic, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, ent, qstart, Q, Cout,
-                           ntab, flow, vals, val_off, root_fold, root_ko, bad, B, out);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(flow_leaf_cat_generic, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, ent, qstart, Q, Cout,
+                    ntab, flow, vals, val_off, root_fold, root_ko, bad, B, out);
 }
 
 int ck_flow_leaf_gaussian(const int64_t* entries, const int32_t* qstart, int Q, const float* mean, const float* stddev,
@@ -345,12 +317,7 @@ int ck_flow_leaf_gaussian(const int64_t* entries, const int32_t* qstart, int Q, 
   if (int st = launch_logev(vals, val_off, root_fold, root_ko, bad, B, logev, stream)) return st;
   const int64_t blocks = blocks_of(B * Q, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_flow_leaf_gaussian: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(flow_leaf_gauss_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s,
-                           reinterpret_cast<const LeafEntry*>(entries), qstart, Q, mean, stddev, flow, vals, val_off, root_fold,
-                           root_ko, bad, B, out);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(flow_leaf_gauss_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream,
+                    reinterpret_cast<const LeafEntry*>(entries), qstart, Q, mean, stddev, flow, vals, val_off, root_fold, root_ko,
+                    bad, B, out);
 }

@@ -80,12 +80,7 @@ int transpose_impl(const TI* x, TO* xt, int B, int D, void* stream, const char* 
   CK_REQUIRE(x != nullptr && xt != nullptr, "%s: null pointer", who);
   CK_REQUIRE(B > 0 && D > 0, "%s: B=%d D=%d must be positive", who, B, D);
   dim3 grid((D + kTile - 1) / kTile, (B + kTile - 1) / kTile), block(kTile, 8);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL((transpose_kernel<TI, TO>), grid, block, 0, s, x, xt, B, D);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch((transpose_kernel<TI, TO>), grid, block, 0, stream, x, xt, B, D);
 }
 
 // ---- gather-type input layers ------------------------------------------------------------------
@@ -195,22 +190,11 @@ int gather_impl(const float* table, const int32_t* xt, const int64_t* scope, flo
   if (vec) {
     const int rows_per_block = 256;
     dim3 grid((B + rows_per_block - 1) / rows_per_block, F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL((gather_rows_vec<MODE>), grid, block, 0, s, table, xt, scope, out, B, K,
-                             C, rows_per_block);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch((gather_rows_vec<MODE>), grid, block, 0, stream, table, xt, scope, out, B, K, C, rows_per_block);
   }
   const int64_t n = static_cast<int64_t>(B) * K;
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096)), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL((gather_rows_scalar<MODE>), grid, block, 0, s, table, xt, scope, out, B, K, C);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch((gather_rows_scalar<MODE>), grid, block, 0, stream, table, xt, scope, out, B, K, C);
 }
 
 // ---- Gaussian ----------------------------------------------------------------------------------
@@ -393,34 +377,19 @@ int ck_stage_categories(const int64_t* x, int32_t* xt, int B, int D, const int32
   CK_REQUIRE(x && xt && num_states && flag, "ck_stage_categories: null pointer");
   CK_REQUIRE(B > 0 && D > 0, "ck_stage_categories: B=%d D=%d must be positive", B, D);
   dim3 grid((D + kTile - 1) / kTile, (B + kTile - 1) / kTile), block(kTile, 8);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(stage_categories_kernel, grid, block, 0, s, x, xt, B, D, num_states, flag, clamp, x_copy);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(stage_categories_kernel, grid, block, 0, stream, x, xt, B, D, num_states, flag, clamp, x_copy);
 }
 
 int ck_poison_outputs(float* out, int64_t n, const int32_t* flag, void* stream) {
   CK_REQUIRE(out && flag && n > 0, "ck_poison_outputs: null pointer or empty output");
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 256))), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(poison_kernel, grid, block, 0, s, out, n, flag);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(poison_kernel, grid, block, 0, stream, out, n, flag);
 }
 
 int ck_zero_if_flag(float* p, int64_t n, const int32_t* flag, void* stream) {
   CK_REQUIRE(p && flag && n > 0, "ck_zero_if_flag: null pointer or empty buffer");
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 1024))), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(zero_if_flag_kernel, grid, block, 0, s, p, n, flag);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(zero_if_flag_kernel, grid, block, 0, stream, p, n, flag);
 }
 
 int ck_transpose_f32(const float* x, float* xt, int B, int D, void* stream) {
@@ -440,12 +409,7 @@ int ck_categorical_clog_fwd(const float* table, const int32_t* xt, const int64_t
 int ck_lse_to_clse(const float* in, float* out_c, int64_t n, void* stream) {
   CK_REQUIRE(in && out_c && n > 0, "ck_lse_to_clse: null pointer or empty input");
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 8192))), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(lse_to_clse_kernel, grid, block, 0, s, in, reinterpret_cast<float2*>(out_c), n);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(lse_to_clse_kernel, grid, block, 0, stream, in, reinterpret_cast<float2*>(out_c), n);
 }
 
 int ck_embedding_log_fwd(const float* table, const int32_t* xt, const int64_t* scope, float* out,
@@ -477,13 +441,7 @@ int ck_gaussian_fwd(const float* mean, const float* stddev, const float* log_par
     });
   const int rows_per_block = 256;
   dim3 grid((B + rows_per_block - 1) / rows_per_block, F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gaussian_kernel, grid, block, 0, s, mean, stddev, log_partition, xt, scope,
-                           out, B, K, rows_per_block);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gaussian_kernel, grid, block, 0, stream, mean, stddev, log_partition, xt, scope, out, B, K, rows_per_block);
 }
 
 int ck_gaussian_prod_fwd(const float* mean, const float* stddev, const float* log_partition, const float* xt,
@@ -495,25 +453,16 @@ int ck_gaussian_prod_fwd(const float* mean, const float* stddev, const float* lo
   if ((K == 32 || K == 64 || K == 128 || K == 256) && B % 4 == 0 && (reinterpret_cast<uintptr_t>(xt) & 15u) == 0) {
     const int rows_per_block = (256 / K) * 16;
     dim3 grid16((B + rows_per_block - 1) / rows_per_block, F), block16(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(gaussian_prod_rows16_kernel, grid16, block16, 0, s, mean, stddev, log_partition, xt, scope, gfold, out, H, B, K);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(gaussian_prod_rows16_kernel, grid16, block16, 0, stream, mean, stddev, log_partition, xt, scope, gfold, out,
+                      H, B, K);
   }
   constexpr int RPT = 8;
   const int lanes_rows = 256 / (K <= 256 ? K : 256);
   CK_REQUIRE(lanes_rows >= 1, "ck_gaussian_prod_fwd: unsupported K=%d", K);
   const int rows_per_block = lanes_rows * RPT;
   dim3 grid((B + rows_per_block - 1) / rows_per_block, F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gaussian_prod_kernel<RPT>, grid, block, 0, s, mean, stddev, log_partition, xt, scope,
-                           gfold, out, H, B, K);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gaussian_prod_kernel<RPT>, grid, block, 0, stream, mean, stddev, log_partition, xt, scope, gfold, out, H, B,
+                    K);
 }
 
 int ck_constant_fwd(const float* value, float* out, int F, int B, int K, int log_space,
@@ -529,13 +478,7 @@ int ck_constant_fwd(const float* value, float* out, int F, int B, int K, int log
     });
   const int64_t n = static_cast<int64_t>(B) * K;
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 1024)), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(constant_kernel, grid, block, 0, s, value, out, B, K, log_space,
-                           value_is_complex, complex_out);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(constant_kernel, grid, block, 0, stream, value, out, B, K, log_space, value_is_complex, complex_out);
 }
 
 }  // extern "C"

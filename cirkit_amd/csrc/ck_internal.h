@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <functional>
+#include <tuple>
 
 #include "../../include/cirkit_hip.h"
 #include "../../include/cirkit_hip_internal.h"
@@ -18,6 +19,19 @@ int fail(ck_status st, const char* fmt, ...) __attribute__((format(printf, 2, 3)
 
 // Runs `fn` on `stream` now, or appends it to the program being recorded on this thread.
 int dispatch(Launch fn, void* stream);
+
+// One kernel launch through dispatch(): the arguments are converted to the kernel's parameter types here and now
+// and travel by value with the recorded launch.
+template <class... P, class... A>
+inline int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, void* stream, A... args) {
+  static_assert(sizeof...(P) == sizeof...(A), "ck::launch: as many arguments as the kernel has parameters");
+  return dispatch(
+      [kernel, grid, block, lds, params = std::tuple<P...>(static_cast<P>(args)...)](hipStream_t s) {
+        std::apply([&](const P&... p) { hipLaunchKernelGGL(kernel, grid, block, lds, s, p...); }, params);
+        return hipGetLastError();
+      },
+      stream);
+}
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

@@ -299,12 +299,7 @@ int ck_interval_block_sums(const float* table, float* side, int F, int C, int K,
   const int nblk = (C + kBlk - 1) / kBlk;
   const int64_t n = static_cast<int64_t>(F) * nblk * K;
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 8192))), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(block_sums_kernel, grid, block, 0, s, table, side, n, C, K, nblk);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(block_sums_kernel, grid, block, 0, stream, table, side, n, C, K, nblk);
 }
 
 int ck_categorical_interval_fwd(const float* table, const float* side, const int32_t* lo, const int32_t* hi,
@@ -322,21 +317,11 @@ int ck_categorical_interval_fwd(const float* table, const float* side, const int
   if (vec) {
     const int rows_per_block = 256;
     dim3 grid((B + rows_per_block - 1) / rows_per_block, F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(cat_interval_vec, grid, block, 0, s, table, side, lo, hi, scope, out, B, K, C, nblk, rows_per_block);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(cat_interval_vec, grid, block, 0, stream, table, side, lo, hi, scope, out, B, K, C, nblk, rows_per_block);
   }
   const int64_t n = static_cast<int64_t>(B) * K;
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096)), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(cat_interval_scalar, grid, block, 0, s, table, side, lo, hi, scope, out, B, K, C, nblk);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(cat_interval_scalar, grid, block, 0, stream, table, side, lo, hi, scope, out, B, K, C, nblk);
 }
 
 int ck_gaussian_interval_fwd(const float* mean, const float* stddev, const float* log_partition, const float* lo,
@@ -353,13 +338,8 @@ int ck_gaussian_interval_fwd(const float* mean, const float* stddev, const float
   //  the point kernel, whose rows cost a handful of fp32 instructions each)
   const int rows_per_block = std::max(32, 256 / std::min(K, 256));
   dim3 grid((B + rows_per_block - 1) / rows_per_block, F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gauss_interval_kernel, grid, block, 0, s, mean, stddev, log_partition, lo, hi, scope, out, B, K,
-                           rows_per_block);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gauss_interval_kernel, grid, block, 0, stream, mean, stddev, log_partition, lo, hi, scope, out, B, K,
+                    rows_per_block);
 }
 
 }  // extern "C"

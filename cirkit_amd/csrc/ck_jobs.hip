@@ -1249,12 +1249,7 @@ extern "C" {
 
 int ck_jobs_sum64_fwd(const ck_sum_job* jobs, int n_units, const float* const* pool, void* stream) {
   CK_REQUIRE(jobs && pool && n_units > 0, "ck_jobs_sum64_fwd: bad arguments");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(jobs_sum64_fwd_kernel<4>, dim3(n_units), dim3(256), 0, s, jobs, pool);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(jobs_sum64_fwd_kernel<4>, dim3(n_units), dim3(256), 0, stream, jobs, pool);
 }
 
 int ck_jobs_sum64_bwd(const ck_sum_job* jobs, int n_units, const float* const* pool, const ck_opt_state* opt, int waves, void* stream) {
@@ -1275,52 +1270,30 @@ int ck_jobs_sum64_bwd(const ck_sum_job* jobs, int n_units, const float* const* p
 int ck_jobs_mix_fwd(const ck_mix_job* jobs, int n_units, const float* const* pool, int h_max, void* stream) {
   CK_REQUIRE(jobs && pool && n_units > 0, "ck_jobs_mix_fwd: bad arguments");
   CK_REQUIRE(h_max >= 1 && h_max <= 16, "ck_jobs_mix_fwd: at most 16 slots per mixing job");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(jobs_mix_fwd_kernel, dim3(n_units), dim3(256), 0, s, jobs, pool);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(jobs_mix_fwd_kernel, dim3(n_units), dim3(256), 0, stream, jobs, pool);
 }
 
 int ck_jobs_mix_params(const ck_mix_job* jobs, int n_jobs, const ck_opt_state* opt, void* stream) {
   CK_REQUIRE(jobs && n_jobs > 0, "ck_jobs_mix_params: bad arguments");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(jobs_mix_params_kernel, dim3(n_jobs), dim3(64), 0, s, jobs, opt);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(jobs_mix_params_kernel, dim3(n_jobs), dim3(64), 0, stream, jobs, opt);
 }
 
 int ck_jobs_mix_bwd(const ck_mix_job* jobs, int n_units, const float* const* pool, int h_max, int64_t gx_stride,
                     const ck_opt_state* opt, void* stream) {
   CK_REQUIRE(jobs && pool && n_units > 0 && gx_stride > 0, "ck_jobs_mix_bwd: bad arguments");
   CK_REQUIRE(h_max >= 1 && h_max <= 16, "ck_jobs_mix_bwd: at most 16 slots per mixing job");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        if (h_max <= 2)
-          hipLaunchKernelGGL(jobs_mix_bwd_kernel<2>, dim3(n_units), dim3(256), 0, s, jobs, pool, opt, gx_stride);
-        else if (h_max <= 4)
-          hipLaunchKernelGGL(jobs_mix_bwd_kernel<4>, dim3(n_units), dim3(256), 0, s, jobs, pool, opt, gx_stride);
-        else if (h_max <= 8)
-          hipLaunchKernelGGL(jobs_mix_bwd_kernel<8>, dim3(n_units), dim3(256), 0, s, jobs, pool, opt, gx_stride);
-        else
-          hipLaunchKernelGGL(jobs_mix_bwd_kernel<16>, dim3(n_units), dim3(256), 0, s, jobs, pool, opt, gx_stride);
-        return hipGetLastError();
-      },
-      stream);
+  decltype(&jobs_mix_bwd_kernel<2>) kern;
+  if (h_max <= 2) kern = jobs_mix_bwd_kernel<2>;
+  else if (h_max <= 4) kern = jobs_mix_bwd_kernel<4>;
+  else if (h_max <= 8) kern = jobs_mix_bwd_kernel<8>;
+  else kern = jobs_mix_bwd_kernel<16>;
+  return ck::launch(kern, dim3(n_units), dim3(256), 0, stream, jobs, pool, opt, gx_stride);
 }
 
 int ck_jobs_nsum(const ck_nsum_job* jobs, int n_jobs, const float* const* pool, int64_t elems, void* stream) {
   CK_REQUIRE(jobs && pool && n_jobs > 0 && n_jobs <= 65535 && elems > 0 && elems % 4 == 0, "ck_jobs_nsum: bad arguments");
   const unsigned gx = static_cast<unsigned>(std::min<int64_t>((elems / 4 + 255) / 256, 64));
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(jobs_nsum_kernel, dim3(gx, n_jobs), dim3(256), 0, s, jobs, pool, elems);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(jobs_nsum_kernel, dim3(gx, n_jobs), dim3(256), 0, stream, jobs, pool, elems);
 }
 
 int ck_jobs_root(const ck_root_launch* a, void* stream) {
@@ -1331,12 +1304,7 @@ int ck_jobs_root(const ck_root_launch* a, void* stream) {
   CK_REQUIRE(a->S >= 1 && a->S <= 4, "ck_jobs_root: 1..4 blocks per scalar fold");
   CK_REQUIRE(a->gx == nullptr || a->mode == 0 || a->mode == 1 || (a->mode == 2 && a->opt), "ck_jobs_root: bad mode");
   const ck_root_launch v = *a;
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(jobs_root_kernel, dim3(v.n_wg), dim3(256), 0, s, v);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(jobs_root_kernel, dim3(v.n_wg), dim3(256), 0, stream, v);
 }
 
 int ck_jobs_cat_bwd(const ck_cat_job* jobs, int n_jobs, const float* const* pool, int B, int C, const ck_opt_state* opt, void* stream) {
@@ -1357,33 +1325,18 @@ int ck_jobs_cat_bwd(const ck_cat_job* jobs, int n_jobs, const float* const* pool
 
 int ck_jobs_gauss_bwd(const ck_gauss_job* jobs, int n_jobs, const float* const* pool, int B, const ck_opt_state* opt, void* stream) {
   CK_REQUIRE(jobs && pool && n_jobs > 0 && B > 0, "ck_jobs_gauss_bwd: bad arguments");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(jobs_gauss_bwd_kernel, dim3(n_jobs), dim3(256), 0, s, jobs, pool, opt, B);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(jobs_gauss_bwd_kernel, dim3(n_jobs), dim3(256), 0, stream, jobs, pool, opt, B);
 }
 
 int ck_opt_step_range(float* p, const float* g, const float* g2, float* m1, float* m2, int64_t n, const ck_opt_state* opt, void* stream) {
   CK_REQUIRE(p && g && opt && n > 0, "ck_opt_step_range: bad arguments");
   const unsigned grid = static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 2048));
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(opt_range_kernel, dim3(grid), dim3(256), 0, s, p, g, g2, m1, m2, n, opt);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(opt_range_kernel, dim3(grid), dim3(256), 0, stream, p, g, g2, m1, m2, n, opt);
 }
 
 int ck_opt_tick(ck_opt_state* state, int32_t* flag, int32_t* sticky, void* stream) {
   CK_REQUIRE(state, "ck_opt_tick: null state");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(1), 0, s, state, flag, sticky);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(opt_tick_kernel, dim3(1), dim3(1), 0, stream, state, flag, sticky);
 }
 
 }  // extern "C"

@@ -914,16 +914,9 @@ int ck_leaf_walk_bwd_redo(const float* table, const float* table_scale, const in
   a.gout1 = gout1;
   a.redo = redo;
   dim3 grid(static_cast<unsigned>(n_roots));
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        if (is_signed) {
-          if (depth == 2) hipLaunchKernelGGL((leaf_bwd_redo_kernel<2, true>), grid, dim3(256), 0, s, a);
-          else hipLaunchKernelGGL((leaf_bwd_redo_kernel<4, true>), grid, dim3(256), 0, s, a);
-        } else if (depth == 2) hipLaunchKernelGGL((leaf_bwd_redo_kernel<2, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((leaf_bwd_redo_kernel<4, false>), grid, dim3(256), 0, s, a);
-        return hipGetLastError();
-      },
-      stream);
+  auto kern = is_signed ? (depth == 2 ? leaf_bwd_redo_kernel<2, true> : leaf_bwd_redo_kernel<4, true>)
+                        : (depth == 2 ? leaf_bwd_redo_kernel<2, false> : leaf_bwd_redo_kernel<4, false>);
+  return ck::launch(kern, grid, dim3(256), 0, stream, a);
 }
 
 }  // extern "C"

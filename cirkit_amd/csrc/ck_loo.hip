@@ -320,13 +320,8 @@ int ck_loo_down_product(int type, const int32_t* cstart, const int32_t* cfold, c
   if (int st = ck::check_product_shape("ck_loo_down_product", type, H, Ki, Ko)) return st;
   const int64_t blocks = blocks_of(n_child * B * Ki, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_loo_down_product: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(loo_product_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, type, cstart, cfold,
-                           cfirst, items, child, layer_fold, vals, der, val_off, n_child, H, Ki, Ko, B);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(loo_product_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, type, cstart, cfold,
+                    cfirst, items, child, layer_fold, vals, der, val_off, n_child, H, Ki, Ko, B);
 }
 
 int ck_loo_leaf_categorical(const int64_t* entries, const int32_t* qstart, int Q, int Cout, int max_units, const float* ntab,
@@ -340,14 +335,8 @@ int ck_loo_leaf_categorical(const int64_t* entries, const int32_t* qstart, int Q
   CK_REQUIRE(lds <= kMaxLds, "ck_loo_leaf_categorical: %d input units over one variable exceed the LDS budget", max_units);
   const int64_t blocks = blocks_of(B * Q, kWaves);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_loo_leaf_categorical: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(loo_leaf_cat_generic, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), static_cast<size_t>(lds), s,
-                           reinterpret_cast<const LooEntry*>(entries), qstart, Q, Cout, max_units, ntab, lz, der, val_off, bad, B,
-                           out);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(loo_leaf_cat_generic, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), static_cast<size_t>(lds), stream,
+                    reinterpret_cast<const LooEntry*>(entries), qstart, Q, Cout, max_units, ntab, lz, der, val_off, bad, B, out);
 }
 
 int ck_loo_leaf_gaussian(const int64_t* entries, const int32_t* qstart, int Q, const float* mean, const float* stddev,
@@ -358,13 +347,8 @@ int ck_loo_leaf_gaussian(const int64_t* entries, const int32_t* qstart, int Q, c
   CK_REQUIRE(Q > 0 && B > 0, "ck_loo_leaf_gaussian: non-positive size");
   const int64_t blocks = blocks_of(B * Q, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_loo_leaf_gaussian: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(loo_leaf_gauss_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s,
-                           reinterpret_cast<const LooEntry*>(entries), qstart, Q, mean, stddev, der, val_off, bad, B, out);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(loo_leaf_gauss_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream,
+                    reinterpret_cast<const LooEntry*>(entries), qstart, Q, mean, stddev, der, val_off, bad, B, out);
 }
 
 int ck_loo_log_probs(const int64_t* entries, const int32_t* vstart, const int32_t* vkind, int D, const float* lz,
@@ -376,12 +360,7 @@ int ck_loo_log_probs(const int64_t* entries, const int32_t* vstart, const int32_
   CK_REQUIRE(D > 0 && B > 0, "ck_loo_log_probs: non-positive size");
   const int64_t blocks = blocks_of(B * D, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_loo_log_probs: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(loo_log_probs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s,
-                           reinterpret_cast<const LooEntry*>(entries), vstart, vkind, D, lz, der, vals, val_off, ev, x_float, bad,
-                           B, out);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(loo_log_probs_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream,
+                    reinterpret_cast<const LooEntry*>(entries), vstart, vkind, D, lz, der, vals, val_off, ev, x_float, bad, B,
+                    out);
 }

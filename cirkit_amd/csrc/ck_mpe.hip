@@ -231,13 +231,8 @@ int ck_mpe_input_max(int type, const float* tab, int64_t sf, int64_t sk, int64_t
   CK_REQUIRE(F > 0 && K > 0, "ck_mpe_input_max: non-positive size");
   const int64_t blocks = blocks_of(F * K, 256);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_mpe_input_max: too many units");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(mpe_input_max_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, type, tab, sf, sk, sc,
-                           t_log, C, mean, stddev, log_partition, F, K, vmax, amax);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(mpe_input_max_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, type, tab, sf, sk, sc, t_log,
+                    C, mean, stddev, log_partition, F, K, vmax, amax);
 }
 
 int ck_mpe_up_input(int type, const int64_t* scope, const float* tab, int64_t sf, int64_t sk, int64_t sc, int t_log, int C,
@@ -252,14 +247,8 @@ int ck_mpe_up_input(int type, const int64_t* scope, const float* tab, int64_t sf
   CK_REQUIRE(F > 0 && K > 0 && B > 0 && D > 0 && fold_off >= 0, "ck_mpe_up_input: non-positive size");
   const int64_t blocks = blocks_of(F * B * K, 256);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_mpe_up_input: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(mpe_up_input_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, type, scope, tab, sf, sk,
-                           sc, t_log, C, mean, stddev, log_partition, vmax, F, K, ev, x_float, B, D, vals, val_off, fold_off,
-                           flag, bad);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(mpe_up_input_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, type, scope, tab, sf, sk, sc,
+                    t_log, C, mean, stddev, log_partition, vmax, F, K, ev, x_float, B, D, vals, val_off, fold_off, flag, bad);
 }
 
 int ck_mpe_up_sum(int type, const int32_t* child, const float* lw, int64_t F, int H, int Ki, int Ko, int M, float* vals,
@@ -274,20 +263,12 @@ int ck_mpe_up_sum(int type, const int32_t* child, const float* lw, int64_t F, in
   const int64_t row_tiles = (B + tr - 1) / tr, unit_tiles = (Ko + tk - 1) / tk;
   CK_REQUIRE(F * row_tiles <= 0x7fffffff && unit_tiles <= 65535, "ck_mpe_up_sum: grid too large");
   const dim3 grid(static_cast<unsigned>(F * row_tiles), static_cast<unsigned>(unit_tiles));
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        if (tk == 16)
-          hipLaunchKernelGGL(mpe_up_sum_kernel<16>, grid, dim3(kUpThreads), 0, s, type, child, lw, F, H, Ki, Ko, M, vals, val_off,
-                             fold_off, B, row_tiles);
-        else if (tk == 32)
-          hipLaunchKernelGGL(mpe_up_sum_kernel<32>, grid, dim3(kUpThreads), 0, s, type, child, lw, F, H, Ki, Ko, M, vals, val_off,
-                             fold_off, B, row_tiles);
-        else
-          hipLaunchKernelGGL(mpe_up_sum_kernel<64>, grid, dim3(kUpThreads), 0, s, type, child, lw, F, H, Ki, Ko, M, vals, val_off,
-                             fold_off, B, row_tiles);
-        return hipGetLastError();
-      },
-      stream);
+  decltype(&mpe_up_sum_kernel<16>) kern;
+  if (tk == 16) kern = mpe_up_sum_kernel<16>;
+  else if (tk == 32) kern = mpe_up_sum_kernel<32>;
+  else kern = mpe_up_sum_kernel<64>;
+  return ck::launch(kern, grid, dim3(kUpThreads), 0, stream, type, child, lw, F, H, Ki, Ko, M, vals, val_off, fold_off, B,
+                    row_tiles);
 }
 
 int ck_mpe_up_product(int type, const int32_t* child, int64_t F, int H, int Ki, int Ko, float* vals, const int64_t* val_off,
@@ -298,13 +279,8 @@ int ck_mpe_up_product(int type, const int32_t* child, int64_t F, int H, int Ki, 
   CK_REQUIRE(type == CK_SAMPLE_HADAMARD ? Ko == Ki : true, "ck_mpe_up_product: Hadamard with %d inputs, %d outputs", Ki, Ko);
   const int64_t blocks = blocks_of(F * B * Ko, 256);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_mpe_up_product: too many entries");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(mpe_up_product_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, s, type, child, F, H, Ki,
-                           Ko, vals, val_off, fold_off, B);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(mpe_up_product_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, stream, type, child, F, H, Ki, Ko,
+                    vals, val_off, fold_off, B);
 }
 
 int ck_mpe_walk(const ck_sample_layer* layers, const float* const* logw, const int32_t* const* amax, int n_layers,

@@ -1315,19 +1315,12 @@ int launch_long_rows(const ck_softmax_job& j, void* stream) {
   float* out = j.out;
   const int64_t rows = j.rows;
   const int len = static_cast<int>(j.len);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        if (n4 <= 2)
-          hipLaunchKernelGGL(softmax_long_rows_kernel<2>, grid, block, 0, s, in, out, rows, len);
-        else if (n4 <= 4)
-          hipLaunchKernelGGL(softmax_long_rows_kernel<4>, grid, block, 0, s, in, out, rows, len);
-        else if (n4 <= 8)
-          hipLaunchKernelGGL(softmax_long_rows_kernel<8>, grid, block, 0, s, in, out, rows, len);
-        else
-          hipLaunchKernelGGL(softmax_long_rows_kernel<16>, grid, block, 0, s, in, out, rows, len);
-        return hipGetLastError();
-      },
-      stream);
+  decltype(&softmax_long_rows_kernel<2>) kern;
+  if (n4 <= 2) kern = softmax_long_rows_kernel<2>;
+  else if (n4 <= 4) kern = softmax_long_rows_kernel<4>;
+  else if (n4 <= 8) kern = softmax_long_rows_kernel<8>;
+  else kern = softmax_long_rows_kernel<16>;
+  return ck::launch(kern, grid, block, 0, stream, in, out, rows, len);
 }
 
 }  // namespace
@@ -1338,49 +1331,28 @@ int ck_param_reduce(int op, const float* x, float* y, int64_t outer, int len, in
   CK_REQUIRE(x && y && outer > 0 && len > 0 && inner > 0, "ck_param_reduce: bad arguments");
   CK_REQUIRE(op == 0 || op == 1, "ck_param_reduce: op %d (0 product, 1 log-sum-exp)", op);
   dim3 grid(static_cast<unsigned>((outer * inner + 255) / 256)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(reduce_axis_kernel<false>, grid, block, 0, s, op, x, static_cast<const float*>(nullptr), static_cast<const float*>(nullptr), y,
-                           outer, len, inner);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(reduce_axis_kernel<false>, grid, block, 0, stream, op, x, nullptr, nullptr, y, outer, len, inner);
 }
 
 int ck_param_reduce_bwd(int op, const float* x, const float* y, const float* dy, float* dx, int64_t outer, int len, int64_t inner, void* stream) {
   CK_REQUIRE(x && y && dy && dx && outer > 0 && len > 0 && inner > 0, "ck_param_reduce_bwd: bad arguments");
   CK_REQUIRE(op == 0 || op == 1, "ck_param_reduce_bwd: op %d (0 product, 1 log-sum-exp)", op);
   dim3 grid(static_cast<unsigned>((outer * inner + 255) / 256)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(reduce_axis_kernel<true>, grid, block, 0, s, op, x, y, dy, dx, outer, len, inner);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(reduce_axis_kernel<true>, grid, block, 0, stream, op, x, y, dy, dx, outer, len, inner);
 }
 
 int ck_param_outer_sum(const float* a, const float* b, float* out, int64_t outer, int n1, int n2, int64_t inner, void* stream) {
   CK_REQUIRE(a && b && out && outer > 0 && n1 > 0 && n2 > 0 && inner > 0, "ck_param_outer_sum: bad arguments");
   const int64_t n = outer * n1 * n2 * inner;
   dim3 grid(static_cast<unsigned>((n + 255) / 256)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(outer_sum_kernel, grid, block, 0, s, a, b, out, outer, n1, n2, inner);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(outer_sum_kernel, grid, block, 0, stream, a, b, out, outer, n1, n2, inner);
 }
 
 int ck_param_outer_sum_bwd(const float* dout, float* dx, int64_t outer, int n1, int n2, int64_t inner, int which, void* stream) {
   CK_REQUIRE(dout && dx && outer > 0 && n1 > 0 && n2 > 0 && inner > 0 && (which == 0 || which == 1), "ck_param_outer_sum_bwd: bad arguments");
   const int64_t n = outer * (which == 0 ? n1 : n2) * inner;
   dim3 grid(static_cast<unsigned>((n + 255) / 256)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(outer_sum_bwd_kernel, grid, block, 0, s, dout, dx, outer, n1, n2, inner, which);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(outer_sum_bwd_kernel, grid, block, 0, stream, dout, dx, outer, n1, n2, inner, which);
 }
 
 int ck_param_softmax(const float* in, float* out, int64_t outer, int len, int64_t inner,
@@ -1390,20 +1362,10 @@ int ck_param_softmax(const float* in, float* out, int64_t outer, int len, int64_
   if (inner == 1) {
     const int64_t rows = outer;
     dim3 grid(static_cast<unsigned>((rows + 3) / 4)), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(softmax_rows_kernel, grid, block, 0, s, in, out, rows, len, log_space);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(softmax_rows_kernel, grid, block, 0, stream, in, out, rows, len, log_space);
   }
   dim3 grid(static_cast<unsigned>((outer * inner + 255) / 256)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(softmax_strided_kernel, grid, block, 0, s, in, out, outer, len, inner, log_space);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(softmax_strided_kernel, grid, block, 0, stream, in, out, outer, len, inner, log_space);
 }
 
 int ck_param_unary(int op, const float* in, float* out, int64_t n, float a, float b, void* stream) {
@@ -1411,12 +1373,7 @@ int ck_param_unary(int op, const float* in, float* out, int64_t n, float a, floa
   CK_REQUIRE(n > 0, "ck_param_unary: n must be positive");
   CK_REQUIRE(op >= CK_UNARY_SIGMOID && op <= CK_UNARY_SOFTPLUS, "ck_param_unary: unknown op %d", op);
   dim3 grid(grid1d(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(unary_kernel, grid, block, 0, s, op, in, out, n, a, b);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(unary_kernel, grid, block, 0, stream, op, in, out, n, a, b);
 }
 
 int ck_param_gather_folds(const float* in, const int64_t* idx, float* out, int64_t F_out,
@@ -1425,24 +1382,14 @@ int ck_param_gather_folds(const float* in, const int64_t* idx, float* out, int64
   CK_REQUIRE(F_out > 0 && per_fold > 0, "ck_param_gather_folds: non-positive size");
   CK_REQUIRE(F_out <= 65535, "ck_param_gather_folds: F_out exceeds grid.y");
   dim3 grid(grid1d(per_fold, 64), static_cast<unsigned>(F_out)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gather_folds_kernel, grid, block, 0, s, in, idx, out, per_fold);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gather_folds_kernel, grid, block, 0, stream, in, idx, out, per_fold);
 }
 
 int ck_param_conj(const float* in_c, float* out_c, int64_t n, void* stream) {
   CK_REQUIRE(in_c && out_c, "ck_param_conj: null pointer");
   CK_REQUIRE(n > 0, "ck_param_conj: n must be positive");
   dim3 grid(grid1d(n)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(conj_kernel, grid, block, 0, s, in_c, out_c, n);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(conj_kernel, grid, block, 0, stream, in_c, out_c, n);
 }
 
 int ck_param_mixing_weight(const float* in, float* out, int F, int K, int H, void* stream) {
@@ -1450,12 +1397,7 @@ int ck_param_mixing_weight(const float* in, float* out, int F, int K, int H, voi
   CK_REQUIRE(F > 0 && K > 0 && H > 0, "ck_param_mixing_weight: non-positive size");
   CK_REQUIRE(F <= 65535, "ck_param_mixing_weight: F exceeds grid.y");
   dim3 grid(grid1d(static_cast<int64_t>(K) * H * K, 256), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(mixing_weight_kernel, grid, block, 0, s, in, out, K, H);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(mixing_weight_kernel, grid, block, 0, stream, in, out, K, H);
 }
 
 int ck_param_bmm(const float* a, const float* b, float* out, int F, int M, int N, int Kd, int trans_a, int trans_b, int accumulate,
@@ -1467,46 +1409,33 @@ int ck_param_bmm(const float* a, const float* b, float* out, int F, int M, int N
     return ck::fail(CK_ERR_UNSUPPORTED, "ck_param_bmm: the symmetrised form (trans_a = 2) needs M = Kd and extents that are multiples of 32");
   if ((M & 31) == 0 && (N & 31) == 0 && (Kd & 31) == 0 && ck::aligned16(a) && ck::aligned16(b) && N <= 65535 * 32 && M <= 65535 * 32) {
     dim3 grid(N / 32, M / 32, F), block(64);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, s, a, b, out, M, N, Kd, accumulate); };
-          if (trans_a == 2) trans_b ? go(bmm_mfma_kernel<2, true>) : go(bmm_mfma_kernel<2, false>);
-          else if (trans_a && trans_b) go(bmm_mfma_kernel<1, true>);
-          else if (trans_a) go(bmm_mfma_kernel<1, false>);
-          else if (trans_b) go(bmm_mfma_kernel<0, true>);
-          else go(bmm_mfma_kernel<0, false>);
-          return hipGetLastError();
-        },
-        stream);
+    decltype(&bmm_mfma_kernel<2, true>) kern;
+    if (trans_a == 2) kern = trans_b ? bmm_mfma_kernel<2, true> : bmm_mfma_kernel<2, false>;
+    else if (trans_a && trans_b) kern = bmm_mfma_kernel<1, true>;
+    else if (trans_a) kern = bmm_mfma_kernel<1, false>;
+    else if (trans_b) kern = bmm_mfma_kernel<0, true>;
+    else kern = bmm_mfma_kernel<0, false>;
+    return ck::launch(kern, grid, block, 0, stream, a, b, out, M, N, Kd, accumulate);
   }
   if (M * static_cast<int64_t>(N) >= 512 && ck::aligned16(out)) {  // (small products, e.g. a row of ones times a block: the 16 x 16 form)
     dim3 grid((N + kBT_N - 1) / kBT_N, (M + kBT_M - 1) / kBT_M, F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          const bool vec = (M & 3) == 0 && (N & 3) == 0 && (Kd & 3) == 0 && ck::aligned16(a) && ck::aligned16(b);
-          auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, s, a, b, out, M, N, Kd, accumulate); };
-          if (vec) {
-            if (trans_a && trans_b) go(bmm_tile_kernel<true, true, true>);
-            else if (trans_a) go(bmm_tile_kernel<true, false, true>);
-            else if (trans_b) go(bmm_tile_kernel<false, true, true>);
-            else go(bmm_tile_kernel<false, false, true>);
-          } else {
-            if (trans_a && trans_b) go(bmm_tile_kernel<true, true, false>);
-            else if (trans_a) go(bmm_tile_kernel<true, false, false>);
-            else if (trans_b) go(bmm_tile_kernel<false, true, false>);
-            else go(bmm_tile_kernel<false, false, false>);
-          }
-          return hipGetLastError();
-        },
-        stream);
+    const bool vec = (M & 3) == 0 && (N & 3) == 0 && (Kd & 3) == 0 && ck::aligned16(a) && ck::aligned16(b);
+    decltype(&bmm_tile_kernel<true, true, true>) kern;
+    if (vec) {
+      if (trans_a && trans_b) kern = bmm_tile_kernel<true, true, true>;
+      else if (trans_a) kern = bmm_tile_kernel<true, false, true>;
+      else if (trans_b) kern = bmm_tile_kernel<false, true, true>;
+      else kern = bmm_tile_kernel<false, false, true>;
+    } else {
+      if (trans_a && trans_b) kern = bmm_tile_kernel<true, true, false>;
+      else if (trans_a) kern = bmm_tile_kernel<true, false, false>;
+      else if (trans_b) kern = bmm_tile_kernel<false, true, false>;
+      else kern = bmm_tile_kernel<false, false, false>;
+    }
+    return ck::launch(kern, grid, block, 0, stream, a, b, out, M, N, Kd, accumulate);
   }
   dim3 grid((N + kMM - 1) / kMM, (M + kMM - 1) / kMM, F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(bmm_kernel, grid, block, 0, s, a, b, out, M, N, Kd, trans_a, trans_b, accumulate);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(bmm_kernel, grid, block, 0, stream, a, b, out, M, N, Kd, trans_a, trans_b, accumulate);
 }
 
 int ck_param_transpose_last2(const float* in, float* out, int64_t R, int A, int Bd, int take_log,
@@ -1516,12 +1445,7 @@ int ck_param_transpose_last2(const float* in, float* out, int64_t R, int A, int 
   CK_REQUIRE(out_rows >= Bd, "ck_param_transpose_last2: out_rows=%d < Bd=%d", out_rows, Bd);
   CK_REQUIRE(R <= 65535, "ck_param_transpose_last2: R exceeds grid.z");
   dim3 grid((Bd + 31) / 32, (A + 31) / 32, static_cast<unsigned>(R)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(transpose_last2_kernel<float>, grid, block, 0, s, in, out, A, Bd, take_log, out_rows);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(transpose_last2_kernel<float>, grid, block, 0, stream, in, out, A, Bd, take_log, out_rows);
 }
 
 int ck_param_transpose_last2_c(const float* in_c, float* out_c, int64_t R, int A, int Bd, int out_rows, void* stream) {
@@ -1530,25 +1454,15 @@ int ck_param_transpose_last2_c(const float* in_c, float* out_c, int64_t R, int A
   CK_REQUIRE(out_rows >= Bd, "ck_param_transpose_last2_c: out_rows=%d < Bd=%d", out_rows, Bd);
   CK_REQUIRE(R <= 65535, "ck_param_transpose_last2_c: R exceeds grid.z");
   dim3 grid((Bd + 31) / 32, (A + 31) / 32, static_cast<unsigned>(R)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(transpose_last2_kernel<float2>, grid, block, 0, s, reinterpret_cast<const float2*>(in_c),
-                           reinterpret_cast<float2*>(out_c), A, Bd, 0, out_rows);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(transpose_last2_kernel<float2>, grid, block, 0, stream, reinterpret_cast<const float2*>(in_c),
+                    reinterpret_cast<float2*>(out_c), A, Bd, 0, out_rows);
 }
 
 int ck_param_table_integral_row(float* table, int F, int C, int K, int mode, void* stream) {
   CK_REQUIRE(table != nullptr, "ck_param_table_integral_row: null pointer");
   CK_REQUIRE(F > 0 && C > 0 && K > 0 && mode >= 0 && mode <= 3, "ck_param_table_integral_row: bad arguments");
   dim3 grid(F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(table_integral_row_kernel, grid, block, 0, s, table, C, K, mode);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(table_integral_row_kernel, grid, block, 0, stream, table, C, K, mode);
 }
 
 int ck_param_softmax_batch(const ck_softmax_job* jobs, int njobs, void* stream) {
@@ -1618,12 +1532,7 @@ int ck_param_binomial_table(const float* p, int is_logits, float* table, int64_t
   CK_REQUIRE(p && table, "ck_param_binomial_table: null pointer");
   CK_REQUIRE(F > 0 && K > 0 && total_count >= 0, "ck_param_binomial_table: bad sizes");
   dim3 grid(grid1d(F * (total_count + 2) * K)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(binomial_table_kernel, grid, block, 0, s, p, is_logits, table, F, K, total_count);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(binomial_table_kernel, grid, block, 0, stream, p, is_logits, table, F, K, total_count);
 }
 
 int ck_param_gaussian_product_logz(const float* mean1, const float* stddev1, const float* mean2, const float* stddev2,
@@ -1631,12 +1540,7 @@ int ck_param_gaussian_product_logz(const float* mean1, const float* stddev1, con
   CK_REQUIRE(mean1 && stddev1 && mean2 && stddev2 && out, "ck_param_gaussian_product_logz: null pointer");
   CK_REQUIRE(F > 0 && K1 > 0 && K2 > 0, "ck_param_gaussian_product_logz: non-positive size");
   dim3 grid(grid1d(F * K1 * K2)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gaussian_product_logz_kernel, grid, block, 0, s, mean1, stddev1, mean2, stddev2, out, F, K1, K2);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gaussian_product_logz_kernel, grid, block, 0, stream, mean1, stddev1, mean2, stddev2, out, F, K1, K2);
 }
 
 int ck_param_gaussian_product_ms(int op, const float* mean1, const float* stddev1, const float* mean2, const float* stddev2, float* out,
@@ -1646,12 +1550,8 @@ int ck_param_gaussian_product_ms(int op, const float* mean1, const float* stddev
   CK_REQUIRE(F > 0 && K1 > 0 && K2 > 0, "ck_param_gaussian_product_ms: non-positive size");
   const int64_t n = static_cast<int64_t>(F) * K1 * K2;
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096))), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gaussian_product_ms_kernel, grid, block, 0, s, op, mean1, stddev1, mean2, stddev2, out, static_cast<int64_t>(F), K1, K2);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gaussian_product_ms_kernel, grid, block, 0, stream, op, mean1, stddev1, mean2, stddev2, out,
+                    static_cast<int64_t>(F), K1, K2);
 }
 
 int ck_param_gaussian_product_ms_bwd(int op, const float* mean1, const float* stddev1, const float* mean2, const float* stddev2,
@@ -1663,13 +1563,8 @@ int ck_param_gaussian_product_ms_bwd(int op, const float* mean1, const float* st
   CK_REQUIRE(F > 0 && K1 > 0 && K2 > 0, "ck_param_gaussian_product_ms_bwd: non-positive size");
   const int64_t n = static_cast<int64_t>(F) * (K1 + K2);
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 4096))), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gaussian_product_ms_bwd_kernel, grid, block, 0, s, op, mean1, stddev1, mean2, stddev2, dout, dmean1, dstddev1, dmean2,
-                           dstddev2, static_cast<int64_t>(F), K1, K2);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gaussian_product_ms_bwd_kernel, grid, block, 0, stream, op, mean1, stddev1, mean2, stddev2, dout, dmean1,
+                    dstddev1, dmean2, dstddev2, static_cast<int64_t>(F), K1, K2);
 }
 
 int ck_param_gaussian_product_logz_bwd(const float* mean1, const float* stddev1, const float* mean2, const float* stddev2,
@@ -1679,24 +1574,14 @@ int ck_param_gaussian_product_logz_bwd(const float* mean1, const float* stddev1,
              "ck_param_gaussian_product_logz_bwd: null pointer");
   CK_REQUIRE(F > 0 && K1 > 0 && K2 > 0, "ck_param_gaussian_product_logz_bwd: non-positive size");
   dim3 grid(grid1d(F * (K1 + K2))), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(gaussian_product_logz_bwd_kernel, grid, block, 0, s, mean1, stddev1, mean2, stddev2, dout, dmean1, dstddev1,
-                           dmean2, dstddev2, F, K1, K2);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(gaussian_product_logz_bwd_kernel, grid, block, 0, stream, mean1, stddev1, mean2, stddev2, dout, dmean1,
+                    dstddev1, dmean2, dstddev2, F, K1, K2);
 }
 
 int ck_ll_sum(const float* ll, int64_t B, int64_t stride, double* out_dev, void* stream) {
   CK_REQUIRE(ll && out_dev, "ck_ll_sum: null pointer");
   CK_REQUIRE(B > 0 && stride > 0, "ck_ll_sum: non-positive size");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(ll_sum_kernel, dim3(1), dim3(1024), 0, s, ll, B, stride, out_dev);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(ll_sum_kernel, dim3(1), dim3(1024), 0, stream, ll, B, stride, out_dev);
 }
 
 }  // extern "C"

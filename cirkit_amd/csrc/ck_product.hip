@@ -86,20 +86,10 @@ int ck_hadamard_fwd(const float* arena, const int64_t* row_off, float* out, int 
   const bool vec = (words % 4 == 0) && ck::aligned16(arena) && ck::aligned16(out);
   if (vec) {
     dim3 grid(static_cast<unsigned>(std::min<int64_t>((words / 4 + 255) / 256, 2048)), F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(hadamard_vec, grid, block, 0, s, arena, row_off, out, H, words, esize);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(hadamard_vec, grid, block, 0, stream, arena, row_off, out, H, words, esize);
   }
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((words + 255) / 256, 2048)), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(hadamard_scalar, grid, block, 0, s, arena, row_off, out, H, words, esize);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(hadamard_scalar, grid, block, 0, stream, arena, row_off, out, H, words, esize);
 }
 
 int ck_kronecker_fwd(const float* arena, const int64_t* row_off, float* out, int F, int H, int B, int K,
@@ -119,12 +109,7 @@ int ck_kronecker_fwd(const float* arena, const int64_t* row_off, float* out, int
     });
   const int64_t n = static_cast<int64_t>(B) * kk;
   dim3 grid(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, 2048)), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(kronecker_kernel, grid, block, 0, s, arena, row_off, out, H, B, K, kk, esize);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(kronecker_kernel, grid, block, 0, stream, arena, row_off, out, H, B, K, kk, esize);
 }
 
 }  // extern "C"

@@ -110,13 +110,8 @@ int ck_sample_cdf(const float* w, int64_t w_sf, int64_t w_sk, int64_t w_sm, int 
   const int64_t rows = F * R;
   const int64_t blocks = (rows + kCdfRowsPerBlock - 1) / kCdfRowsPerBlock;
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_sample_cdf: too many rows");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(sample_cdf_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kCdfRowsPerBlock * ck::kWave), 0, s,
-                           w, w_sf, w_sk, w_sm, w_log, lz, R, M, rows, cdf, flag);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(sample_cdf_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kCdfRowsPerBlock * ck::kWave), 0, stream, w,
+                    w_sf, w_sk, w_sm, w_log, lz, R, M, rows, cdf, flag);
 }
 
 int ck_sample_walk(const ck_sample_layer* layers, int n_layers, int root_fold, int root_unit, int total_folds, int S,
@@ -126,11 +121,6 @@ int ck_sample_walk(const ck_sample_layer* layers, int n_layers, int root_fold, i
   unsigned blocks;
   if (int st = ck::walk_grid("ck_sample_walk", n_layers, root_fold, root_unit, total_folds, S, N, D, lds, blocks)) return st;
   const uint32_t k0 = static_cast<uint32_t>(seed), k1 = static_cast<uint32_t>(seed >> 32);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(sample_walk_kernel, dim3(blocks), dim3(kWalkThreads), lds, s, layers, n_layers, root_fold,
-                           root_unit, total_folds, S, N, D, k0, k1, x, x_float);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(sample_walk_kernel, dim3(blocks), dim3(kWalkThreads), lds, stream, layers, n_layers, root_fold, root_unit,
+                    total_folds, S, N, D, k0, k1, x, x_float);
 }

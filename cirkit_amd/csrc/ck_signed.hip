@@ -375,12 +375,7 @@ int check(const void* arena, const void* signs, const int64_t* row_off, const fl
 extern "C" int ck_slse_table(const float* table, float* log_table, uint32_t* table_signs, int64_t rows, void* stream) {
   CK_REQUIRE(table && log_table && table_signs && rows > 0, "ck_slse_table: bad arguments");
   const dim3 grid(static_cast<unsigned>((rows * 32 + 255) / 256)), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(slse_table_kernel, grid, block, 0, s, table, log_table, table_signs, rows);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(slse_table_kernel, grid, block, 0, stream, table, log_table, table_signs, rows);
 }
 
 extern "C" int ck_slse_tables(const float* weight, float* table, float* log_table, uint32_t* table_signs, int F, int C, void* stream) {
@@ -411,21 +406,11 @@ extern "C" int ck_slse_fwd(const float* arena, const uint32_t* signs, const int6
     while (tpw < 4 && static_cast<int64_t>(F) * ((tiles + 4 * tpw * 2 - 1) / (4 * tpw * 2)) >= 2048) tpw *= 2;
     const int nx = (tiles + 4 * tpw - 1) / (4 * tpw);
     const dim3 grid(static_cast<unsigned>((F + 7) / 8 * 8 * nx)), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(slse_tile32_fwd, grid, block, 0, s, arena, signs, row_off, w, out, sout, H, B, tpw, ga, F, nx);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(slse_tile32_fwd, grid, block, 0, stream, arena, signs, row_off, w, out, sout, H, B, tpw, ga, F, nx);
   }
   const dim3 grid(static_cast<unsigned>(std::max(1, std::min((B + 7) / 8, 1024))), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(slse_few_kernel<false>, grid, block, 0, s, arena, signs, static_cast<float*>(nullptr), row_off, w, out, sout,
-                           static_cast<const float*>(nullptr), static_cast<float*>(nullptr), H, B, Ko);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(slse_few_kernel<false>, grid, block, 0, stream, arena, signs, nullptr, row_off, w, out, sout, nullptr,
+                    nullptr, H, B, Ko);
 }
 
 extern "C" int ck_slse_bwd(const float* arena, const uint32_t* signs, const int64_t* row_off, const float* w, const float* out,
@@ -441,25 +426,12 @@ extern "C" int ck_slse_bwd(const float* arena, const uint32_t* signs, const int6
     const dim3 grid(static_cast<unsigned>((F + 7) / 8 * 8 * nx)), block(256);
     const char* env = getenv("CK_SLSE_READ_Y");
     const bool read_y = env != nullptr && atoi(env) != 0;
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          if (read_y)
-            hipLaunchKernelGGL(slse_tile32_bwd<true>, grid, block, 0, s, arena, signs, gx, row_off, w, out, sout, gout, gout_off, dw, H, B, ga, F,
-                               nx, ga.table != nullptr ? 1 : 0);
-          else
-            hipLaunchKernelGGL(slse_tile32_bwd<false>, grid, block, 0, s, arena, signs, gx, row_off, w, out, sout, gout, gout_off, dw, H, B, ga, F,
-                               nx, ga.table != nullptr ? 1 : 0);
-          return hipGetLastError();
-        },
-        stream);
+    auto kern = read_y ? slse_tile32_bwd<true> : slse_tile32_bwd<false>;
+    return ck::launch(kern, grid, block, 0, stream, arena, signs, gx, row_off, w, out, sout, gout, gout_off, dw, H, B, ga, F, nx,
+                      ga.table != nullptr ? 1 : 0);
   }
   CK_REQUIRE(gout_off == nullptr, "ck_slse_bwd: gout_off is read by 32-output layers only");
   const dim3 grid(static_cast<unsigned>(std::max(1, std::min((B + 7) / 8, 256))), F), block(256);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(slse_few_kernel<true>, grid, block, 0, s, arena, signs, gx, row_off, w, const_cast<float*>(out),
-                           const_cast<uint32_t*>(sout), gout, dw, H, B, Ko);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(slse_few_kernel<true>, grid, block, 0, stream, arena, signs, gx, row_off, w, const_cast<float*>(out),
+                    const_cast<uint32_t*>(sout), gout, dw, H, B, Ko);
 }

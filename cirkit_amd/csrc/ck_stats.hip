@@ -425,13 +425,8 @@ int ck_stats_leaf_categorical(const int64_t* scope, const float* ntab, int64_t F
   const int64_t blocks = F * ((K + KU - 1) / KU);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_stats_leaf_categorical: grid too large");
   const size_t lds = static_cast<size_t>(KU) * (C + 1) * 4;
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(stats_leaf_cat_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), lds, s, scope, ntab, K, C, KU,
-                           CG, ev, x_float, D, flow, val_off, fold_off, live, B, leaf);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(stats_leaf_cat_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), lds, stream, scope, ntab, K, C,
+                    KU, CG, ev, x_float, D, flow, val_off, fold_off, live, B, leaf);
 }
 
 int ck_stats_leaf_gaussian(const int64_t* scope, const float* mean, const float* stddev, int64_t F, int K, const float* ev, int D,
@@ -443,13 +438,8 @@ int ck_stats_leaf_gaussian(const int64_t* scope, const float* mean, const float*
   CK_REQUIRE(F > 0 && K > 0 && D > 0 && B > 0 && fold_off >= 0, "ck_stats_leaf_gaussian: non-positive size");
   const int64_t blocks = blocks_of(F * K, kThreads);
   CK_REQUIRE(blocks <= 0x7fffffff, "ck_stats_leaf_gaussian: grid too large");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(stats_leaf_gauss_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, scope, mean, stddev, F,
-                           K, ev, D, flow, val_off, fold_off, live, B, leaf);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(stats_leaf_gauss_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, stream, scope, mean, stddev,
+                    F, K, ev, D, flow, val_off, fold_off, live, B, leaf);
 }
 
 int ck_stats_unit_sum(const float* flow, const int64_t* val_off, const int32_t* fold_ko, const int64_t* unit_off,
@@ -459,11 +449,6 @@ int ck_stats_unit_sum(const float* flow, const int64_t* val_off, const int32_t* 
              "ck_stats_unit_sum: null pointer");
   CK_REQUIRE(total_folds > 0 && B > 0, "ck_stats_unit_sum: non-positive size");
   CK_REQUIRE(total_folds <= 0x7fffffff, "ck_stats_unit_sum: grid too large");
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(stats_unit_kernel, dim3(static_cast<unsigned>(total_folds)), dim3(kThreads), 0, s, flow, val_off, fold_ko,
-                           unit_off, live, B, unit);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(stats_unit_kernel, dim3(static_cast<unsigned>(total_folds)), dim3(kThreads), 0, stream, flow, val_off,
+                    fold_ko, unit_off, live, B, unit);
 }

@@ -642,15 +642,8 @@ int ck_sum_lse_fwd_v(const float* arena, const int64_t* row_off, const float* w,
     int tpw = 1;
     while (tpw < 4 && static_cast<int64_t>(F) * ((tiles + 4 * tpw * 2 - 1) / (4 * tpw * 2)) >= 2048) tpw *= 2;
     dim3 grid((tiles + 4 * tpw - 1) / (4 * tpw), F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          if (w_layout == CK_W_ROWMAJOR)
-            hipLaunchKernelGGL(sum_lse_tile32<CK_W_ROWMAJOR>, grid, block, 0, s, arena, row_off, w, out, H, B, tpw);
-          else
-            hipLaunchKernelGGL(sum_lse_tile32<CK_W_TILED_F32>, grid, block, 0, s, arena, row_off, w, out, H, B, tpw);
-          return hipGetLastError();
-        },
-        stream);
+    auto kern = w_layout == CK_W_ROWMAJOR ? sum_lse_tile32<CK_W_ROWMAJOR> : sum_lse_tile32<CK_W_TILED_F32>;
+    return ck::launch(kern, grid, block, 0, stream, arena, row_off, w, out, H, B, tpw);
   }
   const bool mfma_ok = !g_force_generic && prod_like && Ki == Ko && Ki == 64 &&
                        ck::aligned16(arena) && ck::aligned16(w) && ck::aligned16(out);
@@ -660,13 +653,8 @@ int ck_sum_lse_fwd_v(const float* arena, const int64_t* row_off, const float* w,
   if (!g_force_generic && prod_like && Ko <= 4 && (Ki == 32 || Ki == 64)) {
     const int rows_per_block = 4 * (64 / Ki);
     dim3 grid(static_cast<unsigned>(std::min((B + rows_per_block - 1) / rows_per_block, 1024)), F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          if (Ki == 32) hipLaunchKernelGGL(sum_lse_few_outputs_kernel<32>, grid, block, 0, s, arena, row_off, w, out, H, B, Ko);
-          else hipLaunchKernelGGL(sum_lse_few_outputs_kernel<64>, grid, block, 0, s, arena, row_off, w, out, H, B, Ko);
-          return hipGetLastError();
-        },
-        stream);
+    auto kern = Ki == 32 ? sum_lse_few_outputs_kernel<32> : sum_lse_few_outputs_kernel<64>;
+    return ck::launch(kern, grid, block, 0, stream, arena, row_off, w, out, H, B, Ko);
   }
   if (!g_force_generic && mode == CK_SUM_CAT && H > 1 && Ki == Ko && (Ki == 32 || Ki == 64) && ck::aligned16(arena) &&
       ck::aligned16(w) && ck::aligned16(out))
@@ -725,14 +713,8 @@ int ck_sum_lse_fwd_c(const float* arena_c, const int64_t* row_off, const float* 
     int tpw = 1;
     while (tpw < 4 && static_cast<int64_t>(F) * ((tiles + 4 * tpw * 2 - 1) / (4 * tpw * 2)) >= 2048) tpw *= 2;
     dim3 grid((tiles + 4 * tpw - 1) / (4 * tpw), F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(sum_clse_tile32, grid, block, 0, s, a, row_off, w, o, H, B, tpw, static_cast<const float*>(nullptr),
-                             static_cast<const int32_t*>(nullptr), static_cast<const int32_t*>(nullptr),
-                             static_cast<const int32_t*>(nullptr), 0);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(sum_clse_tile32, grid, block, 0, stream, a, row_off, w, o, H, B, tpw, nullptr, nullptr, nullptr, nullptr,
+                      0);
   }
   return launch_generic<c32, float>(a, row_off, w, o, F, H, B, Ki, Ko, mode, stream);
 }
@@ -748,13 +730,8 @@ int ck_sum_clse_gather_fwd(const float* table, const int32_t* xt, const int32_t*
   while (tpw < 4 && static_cast<int64_t>(F) * ((tiles + 4 * tpw * 2 - 1) / (4 * tpw * 2)) >= 2048) tpw *= 2;
   dim3 grid((tiles + 4 * tpw - 1) / (4 * tpw), F), block(256);
   c32* o = reinterpret_cast<c32*>(out_c);
-  return ck::dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(sum_clse_tile32, grid, block, 0, s, static_cast<const c32*>(nullptr),
-                           static_cast<const int64_t*>(nullptr), w, o, H, B, tpw, table, child_fold, child_var, xt, C);
-        return hipGetLastError();
-      },
-      stream);
+  return ck::launch(sum_clse_tile32, grid, block, 0, stream, nullptr, nullptr, w, o, H, B, tpw, table, child_fold, child_var, xt,
+                    C);
 }
 
 int ck_mixing_lse_fwd(const float* arena, const int64_t* row_off, const float* mw, float* out,
@@ -768,12 +745,7 @@ int ck_mixing_lse_fwd(const float* arena, const int64_t* row_off, const float* m
     });
   if (K <= 3 && H <= 16) {  // (K % 4 != 0 and tiny: the scalar root)
     dim3 grid(static_cast<unsigned>((static_cast<int64_t>(B) * K + 255) / 256), F), block(256);
-    return ck::dispatch(
-        [=](hipStream_t s) {
-          hipLaunchKernelGGL(mixing_lse_small<16>, grid, block, 0, s, arena, row_off, mw, out, H, B, K);
-          return hipGetLastError();
-        },
-        stream);
+    return ck::launch(mixing_lse_small<16>, grid, block, 0, stream, arena, row_off, mw, out, H, B, K);
   }
   const int lpr = K / 4;
   const bool vec = (K % 4 == 0) && lpr >= 1 && lpr <= 64 && (lpr & (lpr - 1)) == 0 && ck::aligned16(arena) &&

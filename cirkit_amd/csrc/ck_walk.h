@@ -273,13 +273,8 @@ int evidence_walk(const char* fn, const ck_sample_layer* layers, const float* co
   size_t lds;
   unsigned blocks;
   if (int st = walk_grid(fn, n_layers, root_fold, root_unit, total_folds, S, B, D, lds, blocks)) return st;
-  return dispatch(
-      [=](hipStream_t s) {
-        hipLaunchKernelGGL(evidence_walk_kernel<P>, dim3(blocks), dim3(kEvidenceWalkThreads), lds, s, layers, tabs, n_layers,
-                           root_fold, root_unit, total_folds, S, vals, val_off, row0, B, N, D, ev, x, x_float, p);
-        return hipGetLastError();
-      },
-      stream);
+  return launch(evidence_walk_kernel<P>, dim3(blocks), dim3(kEvidenceWalkThreads), lds, stream, layers, tabs, n_layers, root_fold,
+                root_unit, total_folds, S, vals, val_off, row0, B, N, D, ev, x, x_float, p);
 }
 
 }  // namespace ck
