@@ -25,8 +25,8 @@ import torch
 
 from . import _capi as capi
 from . import padding
-from .fusion import (CPBlock, RegionBlock, SubtreeGroup, find_cp_blocks, find_input_products, find_region_blocks,
-                     find_subtree_groups, find_table_dense, find_tail)
+from .fusion import (NO_LAUNCH, CPBlock, RegionBlock, SubtreeGroup, find_cp_blocks, find_input_products, find_region_blocks,
+                     find_subtree_groups, find_table_dense, find_tail, launch_roles, layer_readers)
 from .layers import HipConstantValueLayer, HipEmbeddingLayer, HipInputLayer, HipLayer, HipTensorDotLayer, layer_from_spec
 from .parameters import ParamBatch, TensorStore
 from .circuit_launch import _LaunchMixin
@@ -34,6 +34,7 @@ from .circuit_profile import _ProfilingMixin
 from .plan import Plan, resolve_fold_index
 
 _ALIGN = 64  # arena alignment of every layer block, in activation elements (>= 256 B)
+_CONTRACTIONS = {"f32": 0, "bf16x3": 3, "bf16x6": 6}  # `contraction` -> bf16 pieces products per contraction (0: exact fp32)
 
 
 class _Binding:
@@ -167,6 +168,10 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         keep_levels: bool = False,
         complex_linear: bool = True,
     ) -> None:
+        if contraction not in _CONTRACTIONS:
+            raise ValueError(f"unknown contraction {contraction!r} ('f32' = exact fp32, the product; 'bf16x3' / 'bf16x6' = labelled variants)")
+        self.contraction = contraction
+        self._ct = _CONTRACTIONS[contraction]
         if plan.semiring not in ("lse-sum", "complex-lse-sum"):
             raise ValueError(f"semiring {plan.semiring!r} is not evaluated by the HIP backend")
         self.device = torch.device(device)
@@ -235,7 +240,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             if hasattr(l, "_logits_ok"):
                 l._logits_ok = bool(fused_weight_softmax)
             if hasattr(l, "_contraction"):  # (sum layers: the launches that have a bf16-piece variant)
-                l._contraction = {"f32": 0, "bf16x3": 3, "bf16x6": 6}[contraction]
+                l._contraction = self._ct
         self._folds = [l.num_folds for l in self.layers]
         self._complex = plan.semiring == "complex-lse-sum"
         self._act_dtype = torch.complex64 if self._complex else torch.float32
@@ -249,6 +254,8 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
                     f"fold index of a {s.type} layer has shape {ch.shape[:2]}, expected {(l.num_folds, l.arity)}"
                 )
         self._out_pairs = resolve_fold_index(plan.output, self._folds).reshape(-1, 2)
+        readers = layer_readers(self._children)
+        outs = {int(p) for p in self._out_pairs[:, 0]}
         data_inputs = [l for l in self.layers if isinstance(l, HipInputLayer) and not isinstance(l, HipConstantValueLayer)]
         self._float_input = any(l.wants_float_input for l in data_inputs)
         self._int_input = any(not l.wants_float_input for l in data_inputs)
@@ -283,9 +290,13 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         if self._clin is not None:
             self._virtual = self._clin.virtual_layers()
         self._group_dev: dict[int, tuple] = {}
-        self._tail: list[int] = (
-            find_tail(plan, self.layers, self._virtual | set(self._group_of_root), signed=self._signed) if fuse is not False else []
-        )
+        self._tail: list[int] = []
+
+        def busy(*more) -> set[int]:  # the layers a fusion found so far owns: the later ones leave them alone
+            return self._virtual.union(self._group_of_root, self._tail, *more)
+
+        if fuse is not False:
+            self._tail = find_tail(plan, self.layers, busy(), signed=self._signed)
         # dense sum layers evaluated inside the Hadamard layer that multiplies them (ck_cp.hip)
         self._table_fused: set[int] = set()  # group roots whose table + dense layer are one prologue job
         self._cp_blocks: dict[int, CPBlock] = {}
@@ -300,12 +311,6 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         self._emb_gather_dev: dict[int, tuple] = {}
         # (the gather launch reads a REAL weight table: circuits with a complex parameter anywhere evaluate the Embedding layer)
         if fuse is not False and self._complex and not any(self.store[n].is_complex() for n in self.store.names()):
-            readers: dict[int, set[int]] = {}
-            for j, ch in enumerate(self._children):
-                if ch is not None:
-                    for p in np.unique(ch[..., 0]):
-                        readers.setdefault(int(p), set()).add(j)
-            outs = {int(p) for p in self._out_pairs[:, 0]}
             for j, (sp, l) in enumerate(zip(plan.layers, self.layers)):
                 ch = self._children[j]
                 if ch is None or sp.type not in ("cpt", "sum") or (sp.type == "sum" and l.arity != 1):
@@ -329,15 +334,13 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
                 and not any(self.store[n].is_complex() for n in self.store.names()):
             from .fusion import tensordot_lists
 
-            busy = self._virtual | set(self._group_of_root) | set(self._tail) | set(self._emb_gather)
-            self._td_had, self._td_pair = tensordot_lists(self.layers, self._children, {int(p) for p in self._out_pairs[:, 0]}, busy)
+            self._td_had, self._td_pair = tensordot_lists(self.layers, self._children, outs, busy(self._emb_gather))
             self._virtual |= set(self._td_had.values())
         self._td_first = set(self._td_pair.values())  # (launched together with the layer above them)
         self._tdense: dict[int, int] = {}  # dense layer -> the Categorical layer it is tabulated over
         self._tdense_dev: dict[int, tuple] = {}  # dense layer -> (T' (F, C+1, 32), scope (F) int64, variables (F) numpy)
         if fuse is not False and dense_on_table and batch_params:
-            busy = self._virtual | set(self._group_of_root) | set(self._tail)
-            cand = find_table_dense(plan, self.layers, self._children, busy)
+            cand = find_table_dense(plan, self.layers, self._children, busy())
             def fits(d: int, c: int) -> bool:  # one fold's (K, C) block + statistics + weights in LDS
                 return capi.table_job_fits(4, self.layers[c].num_categories, self.layers[d].num_output_units)
 
@@ -353,29 +356,19 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             if len(counts) > 1:
                 keep = max(counts, key=lambda k: (counts[k], k))
                 self._tdense = {d: c for d, c in self._tdense.items() if self.layers[c].num_categories == keep}
-            readers: dict[int, set[int]] = {}
-            for j, ch in enumerate(self._children):
-                if ch is not None:
-                    for p in np.unique(ch[..., 0]):
-                        readers.setdefault(int(p), set()).add(j)
-            outs = {int(p) for p in self._out_pairs[:, 0]}
             for c in set(self._tdense.values()):  # a Categorical layer only read through tables is never evaluated
                 if c not in outs and readers.get(c, set()) <= set(self._tdense):
                     self._virtual.add(c)
         if fuse is not False:
-            self._input_prod = find_input_products(
-                plan, self.layers, self._children, self._out_pairs, self._virtual | set(self._group_of_root) | set(self._tail))
+            self._input_prod = find_input_products(plan, self.layers, self._children, self._out_pairs, busy())
             self._virtual |= set(self._input_prod.values())
-            blocks, leftover, virt = find_cp_blocks(
-                plan, self.layers, self._children, self._out_pairs,
-                self._virtual | set(self._group_of_root) | set(self._tail) | set(self._input_prod))
+            blocks, leftover, virt = find_cp_blocks(plan, self.layers, self._children, self._out_pairs, busy(self._input_prod))
             self._cp_blocks = {b.layer: b for b in blocks}
             self._cp_leftover = leftover
             self._virtual |= virt
             # mixing layers that take over the CP blocks they combine (ck_cp.hip: region_lse_kernel)
-            regions, absorbed = find_region_blocks(
-                plan, self.layers, self._children, self._out_pairs, self._cp_blocks,
-                self._virtual | set(self._group_of_root) | set(self._tail) | set(self._input_prod)) if fuse_regions else ([], {})
+            regions, absorbed = find_region_blocks(plan, self.layers, self._children, self._out_pairs, self._cp_blocks,
+                                                   busy(self._input_prod)) if fuse_regions else ([], {})
             self._regions = {r.layer: r for r in regions}
             for h, mask in absorbed.items():
                 if mask.all():
@@ -385,15 +378,18 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         self.batch_params = batch_params
         self._batch: ParamBatch | None = None
         self._batch_version = -1
-        if contraction not in ("f32", "bf16x3", "bf16x6"):
-            raise ValueError(f"unknown contraction {contraction!r} ('f32' = exact fp32, the product; 'bf16x3' / 'bf16x6' = labelled variants)")
-        self.contraction = contraction
-        self._ct = {"f32": 0, "bf16x3": 3, "bf16x6": 6}[contraction]
         self.dense_on_table = bool(dense_on_table)
         self.tiled_weights = bool(tiled_weights)
         self._assign_weight_layouts()
         if self._signed and self._tail and not self._tail16_ok():
             self._tail = []  # (only the 16-row tail walks signed values; the layers then take the complex kernels)
+        # which launch of a forward evaluates each layer (fusion.launch_roles): what the dispatch, the profiler and `_bind` read
+        self._roles = launch_roles(
+            tail=self._tail, virtual=self._virtual, td_first=self._td_first, td_had=self._td_had, td_pair=self._td_pair,
+            group_roots=self._group_of_root, tdense=self._tdense, emb_gather=self._emb_gather, cp_leftover=self._cp_leftover,
+            cp_blocks=self._cp_blocks, regions=self._regions, input_prod=self._input_prod,
+            is_const=[isinstance(l, HipConstantValueLayer) for l in self.layers],
+            is_input=[isinstance(l, HipInputLayer) for l in self.layers], real=not self._complex)
 
     def _is_real_valued(self) -> bool:
         """Every data input an Embedding layer and every parameter a plain real tensor (no parameter graph beyond the
@@ -489,7 +485,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         # children offset tables: element offsets into the arena (replaces circuits.py:42-47)
         bd.row_off = []
         for i, (ch, l) in enumerate(zip(self._children, self.layers)):
-            if ch is None or (i in self._virtual and i not in self._td_had.values()) or i in self._group_of_root:
+            if ch is None or self._roles[i] in ("skip", "group"):
                 bd.row_off.append(None)  # (a Hadamard layer read as a list by its TensorDot layer keeps its children's offsets)
                 continue
             if i in self._cp_blocks:  # slots read the dense folds' own inputs
@@ -506,11 +502,8 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             shape = (self.plan.num_variables, B)
             bd.xt = torch.empty(shape, dtype=torch.float32, device=self.device) if self._float_input else None
             bd.xt_i = torch.empty(shape, dtype=torch.int32, device=self.device) if self._int_input else None
-        for h, folds in self._cp_subset.items():
-            K = self.layers[h].num_output_units
-            bd.leftover[h] = (bd.row_off[h][torch.from_numpy(folds).to(self.device)].contiguous(),
-                              torch.from_numpy(bases[h] + folds * (B * K)).to(self.device))
-        for d, folds in self._cp_leftover.items():  # (row offsets, output offsets) of the folds still materialised
+        # (row offsets, output offsets) of the folds still materialised: of CP blocks that regions took over in part, of dense layers
+        for d, folds in (*self._cp_subset.items(), *self._cp_leftover.items()):
             K = self.layers[d].num_output_units
             bd.leftover[d] = (bd.row_off[d][torch.from_numpy(folds).to(self.device)].contiguous(),
                               torch.from_numpy(bases[d] + folds * (B * K)).to(self.device))
@@ -547,19 +540,15 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             return False
         if self.plan.num_variables * B * 8 >= 2**32:
             return False
-        for i, l in enumerate(self.layers):
-            if i in self._virtual or (self._tail and i in self._tail):
-                continue
-            if i in self._group_of_root:
+        for i, (l, role) in enumerate(zip(self.layers, self._roles)):  # does any launch but a persistent leaf read the batch?
+            if role == "group":
                 if not (self._signed or self._leaf_is_persistent(self._group_of_root[i], B)):
                     return False
-            elif i in self._tdense or i in self._emb_gather:
+            elif role in ("table_dense", "emb_gather") or (role == "input" and not l.wants_float_input):
                 return False
-            elif i in self._cp_blocks and self._block_gathers(self._cp_blocks[i].slot_dense):
+            elif role == "cp" and i in self._cp_blocks and self._block_gathers(self._cp_blocks[i].slot_dense):
                 return False
-            elif i in self._regions and self._block_gathers(self._regions[i].slot_dense):
-                return False
-            elif isinstance(l, HipInputLayer) and not isinstance(l, HipConstantValueLayer) and not l.wants_float_input:
+            elif role == "region" and self._block_gathers(self._regions[i].slot_dense):
                 return False
         return True
 
@@ -583,6 +572,12 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
                 self._recording = False
 
         return capi.Program.record(body)
+
+    def _program_ll(self, bd: _Binding) -> capi.Program:
+        """The launch list of `log_likelihood_sum` for this binding, recorded on first use."""
+        if bd.program_ll is None:
+            bd.program_ll = self._record(bd, with_ll=True)
+        return bd.program_ll
 
     def _raw_batch_args(self, bd: _Binding) -> tuple[int | None, int]:
         """(x_rows, x_input) of a launch that reads the caller's batch: program input cell 0 while recording, the batch of
@@ -617,23 +612,22 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         launched here."""
         if self._clin is not None:
             return  # (plain tensors everywhere; the one derived parameter, the linear table, is the path's own first launch)
-        if at_end:
-            self._ensure_param_batch()
-            if self._tailp["rest"] is not None:
-                self._tailp["rest"].launch(stream)
-        else:
-            self._launch_param_batch(stream)
+        self._enqueue_params_batch_only(stream, at_end)
         for l in self.layers:
             l.prepare(stream, batched=self.batch_params)
         for g in self._groups:
             self._group_table(g, stream)
 
+    def _tucker_stream_layers(self) -> list[HipLayer]:
+        """The Tucker layers that can take the stream-K launch (`ck_tucker_fwd`)."""
+        return [l for s, l in zip(self.plan.layers, self.layers)
+                if s.type == "tucker" and l.arity == 2 and l.num_input_units in (32, 64) and not self._complex]
+
     def _scratch(self) -> torch.Tensor | None:
         """The workspace lent to the stream-K Tucker launches (`ck_set_workspace`): ticket counters (zero between
         launches) + two 16 KiB partial-tile slots per persistent workgroup.  None when no layer can use it."""
         if self._scratch_buf is None:
-            tuck = [l for s, l in zip(self.plan.layers, self.layers)
-                    if s.type == "tucker" and l.arity == 2 and l.num_input_units in (32, 64) and not self._complex]
+            tuck = self._tucker_stream_layers()
             if not tuck:
                 self._scratch_buf = False
             else:
@@ -656,11 +650,9 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             return None
         need = (B + 127) // 128
         if need > self._scratch_rows:
-            tuck = [l for s, l in zip(self.plan.layers, self.layers)
-                    if s.type == "tucker" and l.arity == 2 and l.num_input_units in (32, 64) and not self._complex]
             self._scratch_old.append(self._scratch_buf)
             self._scratch_rows = need
-            self._scratch_buf = self._new_scratch(tuck, need)
+            self._scratch_buf = self._new_scratch(self._tucker_stream_layers(), need)
         return self._scratch_buf
 
     def _enqueue_layers(self, bd: _Binding, stream: int, *, with_ll: bool = False, inputs: bool = True) -> None:
@@ -700,50 +692,28 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
                   bd.arena.data_ptr(), None, None, None, 0, int(ro.numel()), 1, 1, bd.B, K, stream)
 
     def _enqueue_layers_(self, bd: _Binding, stream: int, *, with_ll: bool = False, inputs: bool = True) -> None:
-        B = bd.B
         if self._clin is not None:
             self._clin.enqueue(bd, stream)
             return
         pending: list[int] = []  # leftover dense folds (`_cp_leftover`) not launched yet: they wait for their first reader
-        for i, (l, view, ro) in enumerate(zip(self.layers, bd.views, bd.row_off)):
-            if pending and self._children[i] is not None and set(int(p) for p in np.unique(self._children[i][..., 0])) & set(pending):
+
+        def flush() -> None:
+            if pending:
                 self._flush_leftover(pending, bd, stream)
-                pending = []
-            if self._tail and i in self._tail:
-                if i == self._tail[0]:
-                    if pending:
-                        self._flush_leftover(pending, bd, stream)
-                        pending = []
-                    self._launch_tail(bd, stream, with_ll=with_ll)
-                continue
-            if i in self._virtual or i in self._td_first:
-                continue
-            if i in self._td_had or i in self._td_pair:
-                self._launch_tensordot(i, bd, stream)
-            elif i in self._group_of_root:
-                self._launch_group(self._group_of_root[i], bd, view, stream)
-            elif i in self._tdense:
-                self._launch_table_dense(i, bd, stream)
-            elif i in self._emb_gather:
-                self._launch_emb_gather(i, bd, stream)
-            elif i in self._cp_leftover and i not in self._cp_blocks and not self._complex and (
-                    not pending or self.layers[pending[0]].num_output_units == l.num_output_units):
+                pending.clear()
+
+        for i, role in enumerate(self._roles):
+            ch = self._children[i]
+            if pending and ch is not None and set(int(p) for p in np.unique(ch[..., 0])) & set(pending):
+                flush()
+            if role == "tail_first":
+                flush()
+                self._launch_tail(bd, stream, with_ll=with_ll)
+            elif role == "leftover" and (not pending or self.layers[pending[0]].num_output_units == self.layers[i].num_output_units):
                 pending.append(i)  # (launched together with the other leftovers, before the first layer that reads one)
-            elif i in self._cp_blocks or i in self._cp_leftover:
-                self._launch_cp(i, bd, stream)
-            elif i in self._regions:
-                self._launch_region(i, bd, stream)
-            elif i in self._input_prod:
-                self._launch_input_prod(i, bd, stream)
-            elif isinstance(l, HipConstantValueLayer):
-                l.launch_const(view, B, stream)
-            elif isinstance(l, HipInputLayer):
-                if inputs:
-                    l.launch_input(bd.xt if l.wants_float_input else bd.xt_i, self.plan.num_variables, view, B, stream)
-            else:
-                l.launch(bd.arena, ro, view, B, stream)
-        if pending:
-            self._flush_leftover(pending, bd, stream)
+            elif role not in NO_LAUNCH:
+                self._launch_layer(i, bd, stream, inputs=inputs)
+        flush()
 
     # -- evaluation ------------------------------------------------------------------------------
     def _prepare_input(self, x: torch.Tensor) -> tuple[torch.Tensor | None, torch.Tensor | None]:
@@ -867,9 +837,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             xf, xi = self._prepare_input(x) if self.plan.num_variables else (None, None)
             cur = torch.cuda.current_stream(self.device)
             run = cur
-            if with_ll and bd.program_ll is None:
-                bd.program_ll = self._record(bd, with_ll=True)
-            prog = bd.program_ll if with_ll else bd.program
+            prog = self._program_ll(bd) if with_ll else bd.program
             as_graph = bool(self.use_graph) and prog.num_ops > self.graph_min_launches
             state = self.store.state() if (self.cache_params or bd.params_at_end) else None
             refresh = self.cache_params and self._pprog_data_version != state
@@ -913,9 +881,7 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         """Whether a forward of batch size B is replayed as a hipGraph (long launch lists) or eagerly by the native
         executor (short ones, see `use_graph`)."""
         bd = self._bind(B)
-        if with_ll and bd.program_ll is None:
-            bd.program_ll = self._record(bd, with_ll=True)
-        prog = bd.program_ll if with_ll else bd.program
+        prog = self._program_ll(bd) if with_ll else bd.program
         return bool(self.use_graph) and prog.num_ops > self.graph_min_launches
 
     def forward(self, x: torch.Tensor | None = None, *, integrate_vars=None) -> torch.Tensor:
@@ -1164,13 +1130,8 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
             index = self.device.index if self.device.index is not None else torch.cuda.current_device()
             if out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous() or not out.is_cuda or out.device.index != index:
                 raise ValueError(f"out must be a contiguous float64 tensor of 2 elements on {self.device}")
-            self._run(x, with_ll=True, ll_out=out)
-            if reduce:
-                from .distributed import all_reduce_sum
-
-                all_reduce_sum(out)
-            return out
-        ll = self._run(x, with_ll=True).ll
+        bd = self._run(x, with_ll=True, ll_out=out)
+        ll = bd.ll if out is None else out
         if reduce:
             from .distributed import all_reduce_sum
 
@@ -1189,10 +1150,8 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         """Launches of one `log_likelihood_sum` step: the recorded program plus the staging of the batch in front of it
         (none when the leaf launches read the caller's batch, `direct_input`)."""
         bd = self._bind(B)
-        if bd.program_ll is None:
-            bd.program_ll = self._record(bd, with_ll=True)
         staging = 0 if bd.direct else int(self._float_input) + int(self._int_input)
-        return bd.program_ll.num_ops + (staging if self.plan.num_variables else 0)
+        return self._program_ll(bd).num_ops + (staging if self.plan.num_variables else 0)
 
     def reads_batch_directly(self, B: int) -> bool:
         return self._bind(B).direct

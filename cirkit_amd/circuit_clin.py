@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .fusion import find_subtree_groups
+from .fusion import find_subtree_groups, layer_readers
 from .layers import HipEmbeddingLayer
 
 if TYPE_CHECKING:
@@ -72,13 +72,14 @@ class ClinPath:
             return None
         outs = {int(p) for p in c._out_pairs[:, 0]}
         inner = [i for i in range(len(c.layers)) if i != e]
+        readers = layer_readers(c._children)
         for i in inner:
             s, l = plan.layers[i], c.layers[i]
             if not (s.type == "cpt" or (s.type == "sum" and l.arity == 1)) or getattr(l, "_mixing", False):
                 return None
             if l.num_input_units != 32 or l.num_output_units > 32 or getattr(l, "weight", None) is None or _plain_tensor(l.weight) is None:
                 return None
-            if l.num_output_units < 32 and any(i in {int(p) for p in np.unique(ch[..., 0])} for ch in c._children if ch is not None):
+            if l.num_output_units < 32 and i in readers:
                 return None  # (fewer than 32 units: only the layer the circuit outputs)
             if l.num_folds > 65535:
                 return None
@@ -170,7 +171,8 @@ class ClinPath:
         """The tile blocks of a batch size: the leaf group's root and every remaining layer that somebody reads."""
         c, B = self.c, bd.B
         tiles = (B + 31) // 32
-        mat = [self.group.root] + [i for i in self.rest if i not in self.outs or self._is_read(i)]
+        readers = layer_readers(c._children)
+        mat = [self.group.root] + [i for i in self.rest if i not in self.outs or i in readers]
         base, ebase, off, eoff = {}, {}, 0, 0
         for i in mat:
             base[i], ebase[i] = off, eoff
@@ -189,9 +191,6 @@ class ClinPath:
             bd.clin["child"][i] = (torch.from_numpy(np.ascontiguousarray(co)).to(c.device),
                                    torch.from_numpy(np.ascontiguousarray(ce)).to(c.device))
             bd.clin.setdefault("child_np", {})[i] = (co, ce)
-
-    def _is_read(self, i: int) -> bool:
-        return any(ch is not None and i in {int(p) for p in np.unique(ch[..., 0])} for ch in self.c._children)
 
     # ------------------------------------------------------------------------------------------------------------------
     def launches(self, bd: "_Binding") -> list[tuple[int, str, object]]:

@@ -25,9 +25,29 @@ if TYPE_CHECKING:
 _TAIL16_FOLD = np.dtype([("w", "<u8"), ("out", "<u8"), ("child", "<u8", (4,)), ("child_src", "<i4", (4,)), ("H", "<i4"),
                          ("Ko", "<i4"), ("skip_store", "<i4"), ("slot", "<i4")])
 assert _TAIL16_FOLD.itemsize == 80
+# the fused launches that take (layer, binding, stream), by role (fusion.launch_roles)
+_LAUNCH_OF_ROLE = {"tensordot": "_launch_tensordot", "table_dense": "_launch_table_dense", "emb_gather": "_launch_emb_gather",
+                   "leftover": "_launch_cp", "cp": "_launch_cp", "region": "_launch_region", "input_prod": "_launch_input_prod"}
 
 
 class _LaunchMixin:
+    def _launch_layer(self, i: int, bd: _Binding, stream: int, *, inputs: bool = True) -> None:
+        """The launch of layer i by its role (`fusion.launch_roles`; the tail and the roles without a launch are the caller's).
+        `inputs=False`: the caller has filled the arena views of the data input layers itself."""
+        l, role = self.layers[i], self._roles[i]
+        if role in _LAUNCH_OF_ROLE:
+            getattr(self, _LAUNCH_OF_ROLE[role])(i, bd, stream)
+        elif role == "group":
+            self._launch_group(self._group_of_root[i], bd, bd.views[i], stream)
+        elif role == "const":
+            l.launch_const(bd.views[i], bd.B, stream)
+        elif role == "layer":
+            l.launch(bd.arena, bd.row_off[i], bd.views[i], bd.B, stream)
+        elif role != "input":
+            raise ValueError(f"layer {i} ({role}) has no launch of its own")
+        elif inputs:  # (else the caller has filled the layer's view)
+            l.launch_input(bd.xt if l.wants_float_input else bd.xt_i, self.plan.num_variables, bd.views[i], bd.B, stream)
+
     def _launch_tensordot(self, i: int, bd: _Binding, stream: int) -> None:
         """TensorDot layer i with what it absorbed (`_td_had`, `_td_pair`): `ck_tensordot_lse_fwd_h` / `ck_tensordot2_lse_fwd`."""
         l = self.layers[i]
@@ -76,7 +96,7 @@ class _LaunchMixin:
 
     def _gather_tables(self, slot_dense: np.ndarray, key, bd: _Binding):
         """(g_addr, g_var, C) device tables for the slots of `slot_dense` whose dense layer is tabulated, or Nones."""
-        if not any(int(d) in self._tdense for d in np.unique(slot_dense[..., 0]) if d >= 0):
+        if not self._block_gathers(slot_dense):
             return None, None, 0
         tabs = bd.cp_tabs.get((key, "gather"))
         Cn = 0
@@ -183,9 +203,9 @@ class _LaunchMixin:
         capi.call("ck_cp_lse_fwd", bd.arena.data_ptr(), ro.data_ptr(), tab.data_ptr(), None, oo.data_ptr(),
                   bd.arena.data_ptr(), None, None, None, 0, len(folds), 1, 1, bd.B, K, stream)
 
-    def _enqueue_params_batch_only(self, stream: int, bd: _Binding) -> None:
-        """The prologue launch of a forward of this binding (profiling): all jobs, or what the leaf launch leaves."""
-        if bd.params_at_end:
+    def _enqueue_params_batch_only(self, stream: int, at_end: bool) -> None:
+        """The prologue launch of a forward: all jobs, or -- `at_end` -- what the tail launch of the previous forward left."""
+        if at_end:
             self._ensure_param_batch()
             if self._tailp["rest"] is not None:
                 self._tailp["rest"].launch(stream)
@@ -385,15 +405,16 @@ class _LaunchMixin:
     def _launch_tail(self, bd: _Binding, stream: int, *, with_ll: bool = False) -> None:
         """One launch for the trailing few-fold layers (cirkit_amd/csrc/ck_tail16.hip, ck_tailp.hip)."""
         n = len(self._tail)
-        ls = [self.layers[j] for j in self._tail]
-        for l in ls:
-            if l._w.is_complex():
-                raise ValueError("complex weights in the fused tail")
-        lay = next((l._w_layout for l in ls if l.num_output_units == 32), capi.CK_W_ROWMAJOR)
-        if self._tail16_ok() and bd.params_at_end:
-            keep = self.keep_layer_outputs and (not with_ll or self.keep_levels)  # (a training forward keeps them for the backward)
-            desc_dev, levels_dev, n_folds, scratch, ticket, lay = self._tail16_tables(bd, keep=keep, slots=True)
-            fuse_ll = with_ll and self._tail_fuses_ll()
+        if any(self.layers[j]._w.is_complex() for j in self._tail):
+            raise ValueError("complex weights in the fused tail")
+        if not self._tail16_ok():
+            raise capi.HipExtensionError("a fused tail that does not fit the 16-row walk (cirkit_amd/fusion.py find_tail only proposes tails that do)")
+        # `log_likelihood_sum` returns [sum, count] only: the tail's inner folds stay in LDS; `forward` keeps the layer outputs
+        # (`layer_outputs()` reads them) unless the caller opted out; a training forward keeps them for the backward
+        keep = self.keep_layer_outputs and (not with_ll or self.keep_levels)
+        desc_dev, levels_dev, n_folds, scratch, ticket, lay = self._tail16_tables(bd, keep=keep, slots=bd.params_at_end)
+        fuse_ll = with_ll and self._tail_fuses_ll()
+        if bd.params_at_end:
             il = self._tailp
             d = capi.TailParamsLaunch()
             d.folds, d.level_begin, d.n_folds, d.n_levels = desc_dev.data_ptr(), levels_dev.data_ptr(), n_folds, n
@@ -413,21 +434,13 @@ class _LaunchMixin:
             d.rows, d.n_rows = il["rows_all"].data_ptr(), il["n_rows_all"]
             capi.call("ck_tail_params_fwd", C.byref(d), stream)
             return
-        if self._tail16_ok():
-            # `log_likelihood_sum` returns [sum, count] only: the tail's inner folds stay in LDS; `forward` keeps the layer
-            # outputs (`layer_outputs()` reads them) unless the caller opted out
-            keep = self.keep_layer_outputs and (not with_ll or self.keep_levels)  # (a training forward keeps them for the backward)
-            desc_dev, levels_dev, n_folds, scratch, ticket, lay = self._tail16_tables(bd, keep=keep)
-            fuse_ll = with_ll and self._tail_fuses_ll()
-            capi.call(
-                "ck_tail16_lse_fwd", desc_dev.data_ptr(), n_folds, levels_dev.data_ptr(), n, bd.B, 32, lay,
-                bd.ll.data_ptr() if fuse_ll else None, scratch.data_ptr() if fuse_ll else None,
-                ticket.data_ptr() if fuse_ll else None,
-                self._bad_input.data_ptr() if (self._poison_in_tail() and not bd.direct) else None,
-                1 if self._signed else 0, stream,
-            )
-            return
-        raise capi.HipExtensionError("a fused tail that does not fit the 16-row walk (cirkit_amd/fusion.py find_tail only proposes tails that do)")
+        capi.call(
+            "ck_tail16_lse_fwd", desc_dev.data_ptr(), n_folds, levels_dev.data_ptr(), n, bd.B, 32, lay,
+            bd.ll.data_ptr() if fuse_ll else None, scratch.data_ptr() if fuse_ll else None,
+            ticket.data_ptr() if fuse_ll else None,
+            self._bad_input.data_ptr() if (self._poison_in_tail() and not bd.direct) else None,
+            1 if self._signed else 0, stream,
+        )
 
     def _tail16_tables(self, bd: _Binding, *, keep: bool = True, slots: bool = False) -> tuple:
         """(fold descriptors, level table, number of folds, per-tile LL sums, LL ticket, weight layout) of the 16-row tail
@@ -631,7 +644,7 @@ class _LaunchMixin:
         d.w_levels, d.nodes, d.node_off, d.leaf_off = levels, nodes.data_ptr(), node_off, leaf_off
         d.out, d.work, d.n_seg, d.n_wg, d.waves, d.depth = out.data_ptr(), work.data_ptr(), int(work.shape[0]), self._n_cu, waves, depth
         d.B, d.K, d.C, d.w_layout = bd.B, K, Cn, w_layout
-        d.contraction = {"f32": 0, "bf16x3": 3, "bf16x6": 6}[self.contraction]
+        d.contraction = self._ct
         if d.contraction and not (bd.direct and depth == 4 and redo is None and keep is None):
             raise ValueError(f"contraction={self.contraction!r} is a variant of the depth-4 persistent leaf launch over the caller's batch "
                              "(unsigned values, inference forward); this circuit / batch does not take that launch")

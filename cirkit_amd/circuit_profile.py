@@ -11,48 +11,41 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .layers import HipConstantValueLayer, HipInputLayer
+from .fusion import NO_LAUNCH
 
 
 class _ProfilingMixin:
     # -- instrumentation -------------------------------------------------------------------------
     def kernel_label(self, i: int, B: int = 4096) -> str:
         """Name of the HIP kernel that evaluates layer i (as it appears in a rocprofv3 trace)."""
-        l, s = self.layers[i], self.plan.layers[i]
-        if i in self._input_prod:
+        l, s, role = self.layers[i], self.plan.layers[i], self._roles[i]
+        if role == "input_prod":
             return "gaussian_prod_rows16_kernel" if (B % 4 == 0 and l.num_output_units in (32, 64, 128, 256)) else "gaussian_prod_kernel<8>"
-        if i in self._tdense:
+        if role == "table_dense":
             return "gather_rows_vec (dense layer tabulated over its categories)"
-        if i in self._emb_gather:
+        if role == "emb_gather":
             return "sum_clse_tile32 (Embedding rows gathered from the table)"
-        def gathers(slot_dense) -> bool:  # some slot reads a tabulated dense layer
-            return any(int(d) in self._tdense for d in np.unique(slot_dense[..., 0]) if d >= 0)
-
         # (ck_cp.hip: region_dma_kernel<NK, WAVES, MINW, LINEAR, BLOCK, CT>; bf16x6 at K = 64: two workgroups per CU)
         dma = ("2, 4, 2" if self._ct == 6 else "2, 4, 3") if l.num_output_units == 64 else "1, 8, 2"
-        if i in self._regions:
-            if gathers(self._regions[i].slot_dense):
+        if role == "region":
+            if self._block_gathers(self._regions[i].slot_dense):
                 return "region_lse_kernel<2, 4, 3>" if l.num_output_units == 64 else "region_lse_kernel<1, 8, 4>"
             return f"region_dma_kernel<{dma}, {'true' if self.linear_levels else 'false'}, false, {self._ct}>"
-        if i in self._cp_blocks and self._cp_subset.get(i) is None and (
-                self._cp_blocks[i].slot_dense.shape[1] <= 8 or not gathers(self._cp_blocks[i].slot_dense)):
+        if role == "cp" and i in self._cp_blocks and self._cp_subset.get(i) is None and (
+                self._cp_blocks[i].slot_dense.shape[1] <= 8 or not self._block_gathers(self._cp_blocks[i].slot_dense)):
             return f"region_dma_kernel<{dma}, false, true, {self._ct}>"
-        if i in self._cp_blocks or i in self._cp_leftover:
+        if role in ("cp", "leftover"):
             return f"cp_lse_kernel<{l.num_output_units // 32}, 8, {'true' if i in self._cp_blocks else 'false'}>"
-        if i in self._group_of_root and self._signed:
-            raw = "true" if self._direct_input(B) else "false"
+        if role == "group":
             g = self._group_of_root[i]
+            raw = "true" if self._direct_input(B) else "false"  # (the persistent launches: over the caller's batch, by leaf pairs)
             xp = "true" if (raw == "true" and g.depth >= 2 and self._leaves_in_adjacent_pairs(g)) else "false"
-            return f"leaf_persistent_kernel<{g.depth}, 8, true, {raw}, {xp}, false, 0> (signed: real-valued complex circuit)"
-        if i in self._group_of_root:
-            g = self._group_of_root[i]
+            if self._signed:
+                return f"leaf_persistent_kernel<{g.depth}, 8, true, {raw}, {xp}, false, 0> (signed: real-valued complex circuit)"
             in_kernel_dense = g.dense_layer is not None and not (self.dense_on_table and g.depth > 0)
             if i in self._table_fused and self.linear_levels:
                 if self._leaf_is_persistent(g, B):
-                    raw = "true" if self._direct_input(B) else "false"
-                    xp = "true" if (raw == "true" and g.depth >= 2 and self._leaves_in_adjacent_pairs(g)) else "false"
-                    ct = {"f32": 0, "bf16x3": 3, "bf16x6": 6}[self.contraction]
-                    return f"leaf_persistent_kernel<{g.depth}, 8, false, {raw}, {xp}, {'true' if self.keep_levels else 'false'}, {ct}>"
+                    return f"leaf_persistent_kernel<{g.depth}, 8, false, {raw}, {xp}, {'true' if self.keep_levels else 'false'}, {self._ct}>"
                 return f"subtree_linear_kernel<{g.depth}, {self._group_layout(g)}>"
             return (f"subtree_cat_cpt_kernel<{g.depth}, {'true' if in_kernel_dense else 'false'}, "
                     f"{self._group_layout(g)}>")
@@ -144,47 +137,25 @@ class _ProfilingMixin:
                 self._stage_input(bd, xf_xi[0], None if bd.direct else xf_xi[1], stream)
                 s1.record(cur)
                 stage_ms.append((s0, s1))
-            for i, (l, view, ro) in enumerate(zip(self.layers, bd.views, bd.row_off)):
+            for i, (l, role) in enumerate(zip(self.layers, self._roles)):
                 e0 = torch.cuda.Event(enable_timing=True)
                 e1 = torch.cuda.Event(enable_timing=True)
                 e2 = torch.cuda.Event(enable_timing=True)
                 e0.record(cur)
                 if i == 0:
-                    self._enqueue_params_batch_only(stream, bd)
-                in_tail = bool(self._tail) and i in self._tail
-                if in_tail and i == self._tail[0]:
+                    self._enqueue_params_batch_only(stream, bd.params_at_end)
+                if role == "tail_first":
                     for j in self._tail:
                         self.layers[j].prepare(stream, batched=self.batch_params)
-                elif not in_tail:
+                elif role != "tail":
                     l.prepare(stream, batched=self.batch_params)
                 if i in self._group_of_root:  # the dense layer pushed through the table is parameter-side work
                     self._group_table(self._group_of_root[i], stream)
                 e1.record(cur)
-                if in_tail:
-                    if i == self._tail[0]:
-                        self._launch_tail(bd, stream)
-                elif i in self._virtual or i in self._td_first:
-                    pass
-                elif i in self._td_had or i in self._td_pair:
-                    self._launch_tensordot(i, bd, stream)
-                elif i in self._group_of_root:
-                    self._launch_group(self._group_of_root[i], bd, view, stream)
-                elif i in self._tdense:
-                    self._launch_table_dense(i, bd, stream)
-                elif i in self._emb_gather:
-                    self._launch_emb_gather(i, bd, stream)
-                elif i in self._cp_blocks or i in self._cp_leftover:
-                    self._launch_cp(i, bd, stream)
-                elif i in self._regions:
-                    self._launch_region(i, bd, stream)
-                elif i in self._input_prod:
-                    self._launch_input_prod(i, bd, stream)
-                elif isinstance(l, HipConstantValueLayer):
-                    l.launch_const(view, B, stream)
-                elif isinstance(l, HipInputLayer):
-                    l.launch_input(bd.xt if l.wants_float_input else bd.xt_i, self.plan.num_variables, view, B, stream)
-                else:
-                    l.launch(bd.arena, ro, view, B, stream)
+                if role == "tail_first":
+                    self._launch_tail(bd, stream)
+                elif role not in NO_LAUNCH:  # (leftover dense folds one layer at a time: a row per layer)
+                    self._launch_layer(i, bd, stream)
                 e2.record(cur)
                 evs.append((e0, e1, e2))
             torch.cuda.synchronize(self.device)
@@ -255,7 +226,7 @@ class _ProfilingMixin:
                 layer_flops[i] = 0.0
             if i in self._virtual:
                 continue
-            if self._tail and i in self._tail:
+            if self._roles[i] in ("tail_first", "tail"):
                 if i == self._tail[-1]:
                     tl = next((self.layers[j]._w_layout for j in self._tail
                                if self.layers[j].num_output_units == 32), 0)

@@ -44,15 +44,36 @@ class SubtreeGroup:
         return chain[:-1]
 
 
-def _consumers(children, out_pairs, n_layers):
-    cons = [set() for _ in range(n_layers)]
+def layer_readers(children) -> dict[int, set[int]]:
+    """{producer layer: the layers that read one of its folds}; a layer nobody reads has no entry."""
+    readers: dict[int, set[int]] = {}
     for j, ch in enumerate(children):
         if ch is not None:
             for p in np.unique(ch[..., 0]):
-                cons[int(p)].add(j)
+                readers.setdefault(int(p), set()).add(j)
+    return readers
+
+
+def _consumers(children, out_pairs, n_layers):
+    readers = layer_readers(children)
+    cons = [set(readers.get(i, ())) for i in range(n_layers)]
     for p in np.unique(out_pairs[:, 0]):
         cons[int(p)].add(-1)  # the circuit output
     return cons
+
+
+def _fold_uses(layers, children, out_pairs, counts=lambda j, p: True) -> list[np.ndarray]:
+    """Per layer, how often each of its folds is read: by the layers j with `counts(j, producer)` and as a circuit output."""
+    uses = [np.zeros(l.num_folds, dtype=np.int64) for l in layers]
+    for j, ch in enumerate(children):
+        if ch is not None:
+            flat = ch.reshape(-1, 2)
+            for p in np.unique(flat[:, 0]):
+                if counts(j, int(p)):
+                    uses[int(p)] += np.bincount(flat[flat[:, 0] == p, 1], minlength=layers[int(p)].num_folds)
+    for p, f in out_pairs:
+        uses[int(p)][int(f)] += 1
+    return uses
 
 
 def _uses_each_fold_once(ch: np.ndarray, producer: int, n_folds: int) -> bool:
@@ -203,20 +224,9 @@ def find_cp_blocks(plan, layers, children, out_pairs, skip: set[int]):
             return l.arity >= 2
         return s.type == "cpt" and l.num_output_units == l.num_input_units
 
-    # how often each (layer, fold) is read, and by whom
-    uses = [np.zeros(l.num_folds, dtype=np.int64) for l in layers]
-    by_prod = [np.zeros(l.num_folds, dtype=np.int64) for l in layers]
-    for j, ch in enumerate(children):
-        if ch is None:
-            continue
-        flat = ch.reshape(-1, 2)
-        for p in np.unique(flat[:, 0]):
-            cnt = np.bincount(flat[flat[:, 0] == p, 1], minlength=layers[int(p)].num_folds)
-            uses[int(p)] += cnt
-            if is_prod(j) and layers[j].num_input_units == layers[int(p)].num_output_units:
-                by_prod[int(p)] += cnt
-    for p, f in out_pairs:
-        uses[int(p)][int(f)] += 1
+    # how often each (layer, fold) is read, and how often by a product layer of its width
+    uses = _fold_uses(layers, children, out_pairs)
+    by_prod = _fold_uses(layers, children, (), lambda j, p: is_prod(j) and layers[j].num_input_units == layers[p].num_output_units)
     fusable = {d: (uses[d] == 1) & (by_prod[d] == 1) for d in range(n) if is_dense(d)}
     fusable = {d: m for d, m in fusable.items() if m.any()}
     if not fusable:
@@ -255,6 +265,7 @@ def find_input_products(plan, layers, children, out_pairs, skip: set[int]) -> di
         return {}
     found: dict[int, int] = {}
     outs = {int(p) for p in out_pairs[:, 0]}
+    readers = layer_readers(children)
     for j, (s, ch) in enumerate(zip(plan.layers, children)):
         if j in skip or s.type != "hadamard" or ch is None:
             continue
@@ -265,7 +276,7 @@ def find_input_products(plan, layers, children, out_pairs, skip: set[int]) -> di
         sg = plan.layers[g]
         if g in skip or g in outs or sg.type != "gaussian" or sg.scope_idx.shape[1] != 1:
             continue
-        if any(c is not None and k != j and (c[..., 0] == g).any() for k, c in enumerate(children)):
+        if readers.get(g) != {j}:
             continue
         if not _uses_each_fold_once(ch, g, layers[g].num_folds):
             continue
@@ -293,14 +304,7 @@ def find_region_blocks(plan, layers, children, out_pairs, cp_blocks: dict[int, C
     plain-slot blocks for bare Hadamard layers to `cp_blocks`."""
     if plan.semiring != "lse-sum":
         return [], {}
-    uses = [np.zeros(l.num_folds, dtype=np.int64) for l in layers]
-    for ch in children:
-        if ch is not None:
-            flat = ch.reshape(-1, 2)
-            for p in np.unique(flat[:, 0]):
-                uses[int(p)] += np.bincount(flat[flat[:, 0] == p, 1], minlength=layers[int(p)].num_folds)
-    for p, f in out_pairs:
-        uses[int(p)][int(f)] += 1
+    uses = _fold_uses(layers, children, out_pairs)
     regions: list[RegionBlock] = []
     absorbed: dict[int, np.ndarray] = {}
     for j, (s, l) in enumerate(zip(plan.layers, layers)):
@@ -474,11 +478,7 @@ def tensordot_lists(layers, children, out_layers: set[int], busy: set[int] = fro
     `out_layers`: layers that hold a circuit output (never absorbed); `busy`: layers another fusion already owns."""
     from .layers import HipHadamardLayer, HipTensorDotLayer
 
-    readers: dict[int, set[int]] = {}
-    for j, ch in enumerate(children):
-        if ch is not None:
-            for p in np.unique(ch[..., 0]):
-                readers.setdefault(int(p), set()).add(j)
+    readers = layer_readers(children)
 
     def one_to_one(j: int):
         ch = children[j]
@@ -504,3 +504,55 @@ def tensordot_lists(layers, children, out_layers: set[int], busy: set[int] = fro
               and l._num_batch_units == lp.num_output_units // lp._num_batch_units):
             pair_of[j] = p
     return had_of, pair_of
+
+
+# ---------------------------------------------------------------------------------------------
+# which launch evaluates a layer
+# ---------------------------------------------------------------------------------------------
+ROLES = ("tail_first", "tail", "skip", "td_part", "tensordot", "group", "table_dense", "emb_gather", "leftover", "cp", "region",
+         "input_prod", "const", "input", "layer")
+NO_LAUNCH = frozenset({"tail", "skip", "td_part"})  # evaluated by another layer's launch, or never
+
+
+def launch_roles(*, tail, virtual, td_first, td_had, td_pair, group_roots, tdense, emb_gather, cp_leftover, cp_blocks, regions,
+                 input_prod, is_const, is_input, real: bool) -> list[str]:
+    """One role per layer: which launch of a forward evaluates it, from what the fusions above found (the sets and dicts of
+    `HipCircuit`; `is_const[i]` / `is_input[i]`: a constant / an input layer; `real`: a real circuit).  A layer that several
+    fusions claim takes the first role in this order; none depends on the batch size.  ``tail_first`` launches the whole tail;
+    ``skip`` is fused away (no launch, no offset table); ``td_part`` is evaluated by the TensorDot launch above it, which reads
+    its offset table (the first layer of a pair, a Hadamard layer read as a list); ``leftover``: the folds of a dense layer
+    that CP blocks left over, which a forward launches together with other such layers (real circuits only); ``cp``: a CP
+    block, or leftovers on their own; ``const``, ``input``, ``layer``: the layer's own launch."""
+    had_lists = set(td_had.values())
+    roles = []
+    for i, (const, inp) in enumerate(zip(is_const, is_input)):
+        if i in tail:
+            role = "tail_first" if i == tail[0] else "tail"
+        elif i in virtual:
+            role = "td_part" if i in had_lists else "skip"
+        elif i in td_first:
+            role = "td_part"
+        elif i in td_had or i in td_pair:
+            role = "tensordot"
+        elif i in group_roots:
+            role = "group"
+        elif i in tdense:
+            role = "table_dense"
+        elif i in emb_gather:
+            role = "emb_gather"
+        elif real and i in cp_leftover and i not in cp_blocks:
+            role = "leftover"
+        elif i in cp_blocks or i in cp_leftover:
+            role = "cp"
+        elif i in regions:
+            role = "region"
+        elif i in input_prod:
+            role = "input_prod"
+        elif const:
+            role = "const"
+        elif inp:
+            role = "input"
+        else:
+            role = "layer"
+        roles.append(role)
+    return roles

@@ -193,3 +193,82 @@ def test_tensordot_lists_of_a_squared_circuits_partition_function():
     top = max(pair_of)
     h3, p3 = tensordot_lists(layers, children, out | {pair_of[top]})
     assert top not in p3 and len(p3) == n_sum - 1
+
+
+def _roles(n=3, **facts):
+    """`fusion.launch_roles` of n plain inner layers, with the given facts set."""
+    from cirkit_amd.fusion import launch_roles
+
+    base = dict(tail=[], virtual=set(), td_first=set(), td_had={}, td_pair={}, group_roots={}, tdense={}, emb_gather={},
+                cp_leftover={}, cp_blocks={}, regions={}, input_prod={}, is_const=[False] * n, is_input=[False] * n, real=True)
+    base.update(facts)
+    return launch_roles(**base)
+
+
+def test_every_layer_gets_exactly_one_launch_role():
+    from cirkit_amd.fusion import ROLES
+
+    roles = _roles(16, tail=[14, 15], virtual={1, 3}, td_first={4}, td_had={4: 3}, td_pair={5: 4}, group_roots={6: None}, tdense={7: 0},
+                   emb_gather={8: 1}, cp_leftover={9: None}, cp_blocks={10: None}, regions={11: None}, input_prod={12: 2},
+                   is_const=[False, False, True] + [False] * 13, is_input=[True, True, True] + [False] * 13)
+    assert roles == ["input", "skip", "const", "td_part", "td_part", "tensordot", "group", "table_dense", "emb_gather", "leftover",
+                     "cp", "region", "input_prod", "layer", "tail_first", "tail"]
+    assert len(roles) == 16 and set(roles) <= set(ROLES) and set(roles) == set(ROLES)
+
+
+def test_launch_roles_keep_the_precedence_of_the_dispatch_chain():
+    """A layer that is a member of two adjacent branches of the chain takes the earlier one (layer 1 of 3 is the member)."""
+    assert _roles(tail=[1, 2], virtual={1}) == ["layer", "tail_first", "tail"]
+    assert _roles(tail=[0, 1], virtual={1}, td_first={1})[1] == "tail"
+    assert _roles(virtual={1}, td_had={1: 0})[1] == "skip"
+    assert _roles(td_first={1}, td_pair={1: 0})[1] == "td_part"
+    assert _roles(virtual={1}, td_had={2: 1})[1] == "td_part"  # a Hadamard layer read as a list: no launch, offsets kept
+    assert _roles(virtual={1}, td_first={1})[1] == "skip"
+    assert _roles(td_pair={1: 0}, group_roots={1: None})[1] == "tensordot"
+    assert _roles(group_roots={1: None}, tdense={1: 0})[1] == "group"
+    assert _roles(tdense={1: 0}, emb_gather={1: 0})[1] == "table_dense"
+    assert _roles(emb_gather={1: 0}, cp_leftover={1: None})[1] == "emb_gather"
+    assert _roles(cp_leftover={1: None})[1] == "leftover"
+    assert _roles(cp_leftover={1: None}, real=False)[1] == "cp"  # only real circuits batch their leftovers
+    assert _roles(cp_leftover={1: None}, cp_blocks={1: None})[1] == "cp"
+    assert _roles(cp_blocks={1: None}, regions={1: None})[1] == "cp"
+    assert _roles(regions={1: None}, input_prod={1: 0})[1] == "region"
+    assert _roles(input_prod={1: 0}, is_const=[False, True, False], is_input=[False, True, False])[1] == "input_prod"
+    assert _roles(is_const=[False, True, False], is_input=[False, True, False])[1] == "const"
+    assert _roles(is_input=[False, True, False]) == ["layer", "input", "layer"]
+
+
+def test_launch_roles_of_the_quadtree_plan():
+    from cirkit_amd.fusion import find_tail, launch_roles
+    from cirkit_amd.layers import HipConstantValueLayer, HipInputLayer
+
+    plan, tensors, g, layers, children, out_pairs = _setup("cfg2_qt784")
+    (grp,) = find_subtree_groups(plan, layers, children, out_pairs, 4)
+    virtual = set(grp.virtual)
+    tail = find_tail(plan, layers, virtual | {grp.root})
+    assert len(tail) >= 2
+    roles = launch_roles(tail=tail, virtual=virtual, td_first=set(), td_had={}, td_pair={}, group_roots={grp.root: grp}, tdense={},
+                         emb_gather={}, cp_leftover={}, cp_blocks={}, regions={}, input_prod={},
+                         is_const=[isinstance(l, HipConstantValueLayer) for l in layers],
+                         is_input=[isinstance(l, HipInputLayer) for l in layers], real=True)
+    assert len(roles) == len(layers)
+    assert roles.count("group") == 1 and roles[grp.root] == "group"
+    assert [roles[i] for i in tail] == ["tail_first"] + ["tail"] * (len(tail) - 1)
+    assert all(roles[i] == "skip" for i in virtual) and roles.count("skip") == len(virtual)
+    assert roles.count("tail_first") + roles.count("tail") == len(tail)
+
+
+def test_layer_readers_lists_who_reads_each_layer():
+    from cirkit_amd.fusion import layer_readers
+
+    ch = [None, None, np.asarray([[[0, 0], [1, 0]], [[0, 1], [0, 1]]]), np.asarray([[[2, 0]], [[0, 0]]])]
+    assert layer_readers(ch) == {0: {2, 3}, 1: {2}, 2: {3}}
+
+
+def test_unknown_contraction_is_a_value_error_before_anything_else():
+    """Also for circuits whose layers carry a `_contraction` attribute (every sum layer), and without a device."""
+    from cirkit_amd.circuit import HipCircuit
+
+    plan, tensors, _ = load_case("cfg2_qt784")
+    with pytest.raises(ValueError, match="unknown contraction 'fp16'"):
+        HipCircuit(plan, tensors, device="cpu", contraction="fp16")
