@@ -787,6 +787,38 @@ __global__ void __launch_bounds__(1024)
 }
 
 // softmax backward over rows: dtheta = W * (dW - sum(W * dW));  W given row-major (rows, len).
+// The dot product and the difference dW - dot are formed in DOUBLE (a product of two floats is exact there): on a row whose
+// weight sits on one entry, dot is that entry's dW to within the row's other weights, and the whole row of dtheta is what the
+// subtraction leaves -- in fp32 the rounding of dot (one ulp of dW) is as large as the result (tests/test_gpu_param_backward.py,
+// the "spread" rows).  Two double operations per entry and one reduction in double per row.
+// (the sum over lanes without LDS, as ck::wave_sum: the same DPP / permlane steps on both words of the double.  HALF: over the
+//  32 lanes of each half-wave -- v_permlane16_swap pairs rows 0 / 1 and 2 / 3 -- instead of all 64.)
+template <int CTRL>
+__device__ __forceinline__ double mov_dpp_f64(double v) {
+  return __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xF, 0xF, true),
+                          __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true));
+}
+template <bool HALF>
+__device__ __forceinline__ double lanes_sum_f64(double v) {
+  v += mov_dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += mov_dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += mov_dpp_f64<0x141>(v);  // row_half_mirror
+  v += mov_dpp_f64<0x140>(v);  // row_mirror
+  {
+    const unsigned lo = __double2loint(v), hi = __double2hiint(v);
+    const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    v = __hiloint2double(rh[0], rl[0]) + __hiloint2double(rh[1], rl[1]);
+  }
+  if constexpr (!HALF) {
+    const unsigned lo = __double2loint(v), hi = __double2hiint(v);
+    const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    v = __hiloint2double(rh[0], rl[0]) + __hiloint2double(rh[1], rl[1]);
+  }
+  return v;
+}
+__device__ __forceinline__ float softmax_bwd_entry(float w, float dw, double dot) {
+  return w * static_cast<float>(static_cast<double>(dw) - dot);
+}
 __global__ void __launch_bounds__(256)
     softmax_bwd_rows_kernel(const float* __restrict__ w, const float* __restrict__ dw,
                             float* __restrict__ dtheta, int64_t rows, int len, int accumulate) {
@@ -795,11 +827,11 @@ __global__ void __launch_bounds__(256)
   if (row >= rows) return;
   const float* wr = w + row * len;
   const float* dr = dw + row * len;
-  float dot = 0.f;
-  for (int i = lane; i < len; i += 64) dot = fmaf(wr[i], dr[i], dot);
-  dot = ck::wave_sum(dot);
+  double dot = 0.0;
+  for (int i = lane; i < len; i += 64) dot = fma(static_cast<double>(wr[i]), static_cast<double>(dr[i]), dot);
+  dot = lanes_sum_f64<false>(dot);
   for (int i = lane; i < len; i += 64) {
-    const float g = wr[i] * (dr[i] - dot);
+    const float g = softmax_bwd_entry(wr[i], dr[i], dot);
     if (accumulate)
       dtheta[row * len + i] += g;
     else
@@ -894,10 +926,8 @@ __global__ void __launch_bounds__(256) softmax_bwd_batch_kernel(const SoftmaxBwd
     for (; p < j.n_part; p += 2) acc += dr[p * j.part_stride + i];
     acc += __shfl_xor(acc, 32, 64);
     const float w = wr[i];
-    float dot = w * acc;
-#pragma unroll
-    for (int s = 1; s < 32; s <<= 1) dot += __shfl_xor(dot, s, 64);
-    const float g = w * (acc - dot);
+    const double dot = lanes_sum_f64<true>(static_cast<double>(w) * static_cast<double>(acc));  // (over the 32 lanes of the row, in double)
+    const float g = softmax_bwd_entry(w, acc, dot);
     if (lane < 32) dth[row * j.len + i] = g;
     softmax_row_step(j, opt, ro, row * 32 + i, g, lane);
     return;
@@ -906,17 +936,16 @@ __global__ void __launch_bounds__(256) softmax_bwd_batch_kernel(const SoftmaxBwd
     const int i = lane & 31;
     const RowOpt ro = softmax_row_fetch(j, opt, row * 32 + i, lane);
     const float w = wr[i], dv = dr[i];
-    float dot = lane < 32 ? w * dv : 0.f;
-    dot = ck::wave_sum(dot);
-    const float g = w * (dv - dot);
+    const double dot = lanes_sum_f64<true>(static_cast<double>(w) * static_cast<double>(dv));  // (both halves hold the row: each sums its own)
+    const float g = softmax_bwd_entry(w, dv, dot);
     if (lane < 32) dth[row * 32 + i] = g;
     softmax_row_step(j, opt, ro, row * 32 + i, g, lane);
     return;
   }
-  float dot = 0.f;
-  for (int i = lane; i < j.len; i += 64) dot = fmaf(wr[i], dr[i], dot);
-  dot = ck::wave_sum(dot);
-  for (int i = lane; i < j.len; i += 64) dth[row * j.len + i] = wr[i] * (dr[i] - dot);
+  double dot = 0.0;
+  for (int i = lane; i < j.len; i += 64) dot = fma(static_cast<double>(wr[i]), static_cast<double>(dr[i]), dot);
+  dot = lanes_sum_f64<false>(dot);
+  for (int i = lane; i < j.len; i += 64) dth[row * j.len + i] = softmax_bwd_entry(wr[i], dr[i], dot);
 }
 
 // Categorical parameter backward: table (F, C+1, K) = log softmax_C(theta (F, K, C)) transposed.

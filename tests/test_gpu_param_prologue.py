@@ -22,17 +22,15 @@ which fp32 `out` underflows)."""
 import pytest
 import torch
 
+from guarded_buffers import GUARD, NAN_BITS, NEG_INF, _Guarded, _logits, _stream  # noqa: F401
 from prologue_restatement import (binomial_table, integral_row, log_table, softmax_rows, table_dense, to_tiled,
                                   transpose_last2)
 
 pytestmark = pytest.mark.gpu
 
-NAN_BITS = 0x7FC0DEAD
-GUARD = 64  # words: 256 bytes, so a guarded output keeps the 16-byte alignment of the allocation
 FLOOR = 1e-6
 LOG_CUT = -103.0
 DENSE_CUT = -85.0
-NEG_INF = float("-inf")
 FAMILIES = ["normal", "shift+", "shift-", "spread", "const", "neginf"]
 WORST: dict[str, tuple] = {}
 
@@ -43,57 +41,6 @@ def _summary():
     for kind in sorted(WORST):
         r, case, err, yard = WORST[kind]
         print(f"\nPROLOGUE-WORST {kind}: ratio {r:.3f} (err {err:.3e}, yardstick {yard:.3e}) at {case}")
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-class _Guarded:
-    """n fp32 words of output between two guard blocks (`lead` extra words in front shift it off 16-byte alignment)."""
-
-    def __init__(self, n, dev, lead=0):
-        self.n, self.lo = int(n), GUARD + lead
-        self.bits = torch.full((self.lo + self.n + GUARD,), NAN_BITS, dtype=torch.int32, device=dev)
-        self.out = self.bits[self.lo:self.lo + self.n].view(torch.float32)
-
-    def raw(self):
-        """The owned words as int32 on the host, guards checked."""
-        b = self.bits.cpu()
-        assert bool((b[:self.lo] == NAN_BITS).all()), "words BEFORE the output were overwritten"
-        assert bool((b[self.lo + self.n:] == NAN_BITS).all()), "words AFTER the output were overwritten"
-        return b[self.lo:self.lo + self.n]
-
-    def read(self, owned=None):
-        """The output on the host; `owned`: bool mask of the words the kernel must write (default all) -- the others must
-        still hold the fill pattern."""
-        b = self.raw()
-        written = b != NAN_BITS
-        if owned is None:
-            assert bool(written.all()), f"{int((~written).sum())} of {self.n} owned words were never written"
-        else:
-            owned = owned.reshape(-1)
-            assert bool(written[owned].all()), f"{int((~written[owned]).sum())} owned words were never written"
-            assert not bool(written[~owned].any()), f"{int(written[~owned].sum())} words the kernel does not own were written"
-        return b.view(torch.float32)
-
-
-def _logits(shape, fam, g):
-    """fp32 logits of a value family; the softmax axis is the last one.  'neginf' keeps one column finite in every row."""
-    x = torch.randn(shape, generator=g)
-    if fam == "shift+":
-        x = x + 1e4
-    elif fam == "shift-":
-        x = x - 1e4
-    elif fam == "spread":
-        x = torch.rand(shape, generator=g) * 200 - 100
-    elif fam == "const":
-        x = torch.full(shape, 0.75)
-    elif fam == "neginf" and shape[-1] > 1:
-        m = torch.rand(shape, generator=g) < 0.3
-        m[..., int(torch.randint(shape[-1], (1,), generator=g))] = False
-        x[m] = NEG_INF
-    return x.contiguous()
 
 
 def _report(kind, case, err, yard):
