@@ -15,743 +15,322 @@ orders them in levels (one launch per kind and level), and records the whole ste
 levels, root, backward levels, input-layer backward -- as ONE native launch list per batch size (`ck_program`).  Every gradient
 block has one writer; readers add the blocks of their list.  Parameter gradients leave the job epilogues as d theta (the softmax
 behind every weight is differentiated by the workgroup that holds dW).  `HipTrainer` owns the buffers, the optimizer and the
-collective; `JobStep.applies(trainer)` says why a plan does not take this form (then the layer-wise launch list runs)."""
+collective; `JobStep(trainer).why` says why a plan does not take this form (then the layer-wise launch list runs).
+
+The jobs, their lists and levels: cirkit_amd/job_graph.py (no device needed); how a level's jobs are cut into the units of a
+launch: cirkit_amd/job_layout.py; this module binds both to a batch size (`_Tables`) and issues the launches."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import _capi as capi
-from .layers import HipCategoricalLayer, HipCPTLayer, HipGaussianLayer, HipHadamardLayer, HipSumLayer, HipTuckerLayer
-from .plan import resolve_fold_index
-
-MAX_LIST = 4  # a product of more blocks than this is materialised by an NSUM job
-K = 64
-FOLD_MIX_BWD = os.environ.get("CK_JOBS_FOLD_MIX", "1") != "0"  # (lab switch: 0 keeps a backward launch per mixing level)
+from .job_graph import K, MixJob, SumJob, build_job_graph
+from .job_layout import mix_split, sum_layout
+from .layers import HipCategoricalLayer
 
 
-def _expr(g, j: int, f: int):
-    """The value of fold f of node j of a parameter graph as a nested tuple (op, node, fold, *operands)."""
-    n = g.nodes[j]
-    if n.op == "tensor":
-        return ("tensor", j, f, n.config["tensor"])
-    folds = [m.num_folds for m in g.nodes]
-    kids = []
-    for fi in n.inputs:
-        pr = resolve_fold_index(fi, [folds[i] if i in fi.ids else 0 for i in range(max(fi.ids) + 1)]).reshape(-1, 2)
-        kids.append(_expr(g, int(pr[f, 0]), int(pr[f, 1])))
-    return (n.op, j, f, *kids)
+@dataclass(slots=True)
+class Launch:
+    """One launch of a bound step, in issue order."""
+    kind: str  # nsum | sum_fwd | mix_fwd | root | sum_bwd | mix_bwd | mix_params | gauss_bwd | cat_bwd | input_bwd
+    tables: dict[int, torch.Tensor] | None = None  # mode -> the device job table (forward launches: mode 1 only)
+    n: int = 1  # units (rows of the table)
+    param: int = 0  # sum_bwd: waves per workgroup; mix_fwd / mix_bwd: the largest H; cat_bwd: the layer's categories
+    layer: int = -1  # the input layer of a gauss_bwd / cat_bwd / input_bwd launch
+
+    def table(self, mode: int) -> int:
+        return self.tables.get(mode, self.tables[1]).data_ptr()
 
 
-def _out_expr(g, f: int):
-    folds = [m.num_folds for m in g.nodes]
-    pr = resolve_fold_index(g.output, [folds[i] if i in g.output.ids else 0 for i in range(max(g.output.ids) + 1)]).reshape(-1, 2)
-    return _expr(g, int(pr[f, 0]), int(pr[f, 1]))
+class _Tables:
+    """The binding context of one batch size: block addresses, the pool of block lists, the device table of every launch."""
 
+    def __init__(self, js: JobStep, bd, B: int) -> None:
+        self.g, self.tr, self.c, self.bd, self.B = js.graph, js.tr, js.c, bd, B
+        self.dev, self.n_cu, self.tiles, self.blk = self.c.device, self.c._n_cu, (B + 31) // 32, B * K
+        self.keep: list[torch.Tensor] = []
+        self.extra = self.zeros(max(1, self.g.n_extra) * self.blk)
+        self.x0 = self.extra.data_ptr()
+        self.pool: list[int] = []
+        self.folded = [r for r in self.g.mix_jobs if r.folded]
+        offs = np.cumsum([0] + [K * r.H for r in self.folded])
+        mix_dw = self.zeros(max(1, int(offs[-1])))  # d w of the folded mixing folds, left by the sum jobs under them
+        self.mix_dw = {id(r): mix_dw.data_ptr() + 4 * int(o) for r, o in zip(self.folded, offs)}
 
-def _is_softmax_of_tensor(g, e) -> bool:
-    return (e[0] == "softmax" and e[3][0] == "tensor" and int(g.nodes[e[1]].config["dim"]) == len(g.nodes[e[1]].shape) - 1)
+    def zeros(self, n: int, dtype=torch.float32) -> torch.Tensor:
+        self.keep.append(torch.zeros(n, dtype=dtype, device=self.dev))
+        return self.keep[-1]
 
+    def addr(self, x) -> int:
+        if x[0] == "a":
+            v = self.bd.views[x[1]]
+            return v.data_ptr() + x[2] * self.B * v.shape[2] * 4
+        return self.x0 + x[1] * self.blk * 4
 
-class JobStep:
-    """Structure (independent of the batch size) + per-batch-size bindings of the job form of a training step."""
+    def put(self, blocks) -> tuple[int, int]:
+        off = len(self.pool)
+        self.pool.extend(self.addr(x) for x in blocks)
+        return off, len(blocks)
 
-    def __init__(self, trainer) -> None:
-        self.tr = trainer
-        self.c = trainer.circuit
-        self._bound: dict[int, dict] = {}
-        self._own_state = None  # the store's state after this object's last in-place update (fused optimizer)
-        self.why = self._analyse()
-
-    # ---- analysis -------------------------------------------------------------------------------------------------------
-    def _analyse(self) -> str | None:
-        tr, c = self.tr, self.c
-        plan = tr.plan
-        if c._complex or len(c._out_pairs) != 1:
-            return "needs a real circuit with one output"
-        po, fo = int(c._out_pairs[0, 0]), int(c._out_pairs[0, 1])
-        n_layers = len(c.layers)
-        vals: dict[tuple[int, int], list] = {}
-        self.sum_jobs: list[dict] = []
-        self.mix_jobs: list[dict] = []
-        self.nsum_jobs: list[dict] = []
-        self.inputs: list[int] = []
-        self.gauss: dict[int, list[dict]] = {}  # Gaussian layers whose folds are backward jobs
-        self.cat: set[int] = set()  # Categorical layers whose folds are backward jobs
-        self.n_extra = 0
-        gsrc: dict[tuple, list] = {}
-        producer: dict[tuple, dict] = {}  # block -> the job that writes it (forward)
-        used: dict[tuple[str, int], str] = {}  # (tensor, fold) -> who differentiates it
-        scalars: dict[tuple[int, int], dict] = {}
-
-        def extra(n: int = 1) -> int:
-            first = self.n_extra
-            self.n_extra += n
-            return first
-
-        def claim(name: str, fold: int, who: str) -> bool:
-            if (name, fold) in used:
-                return False
-            used[(name, fold)] = who
-            return True
-
-        def feed(blocks, gid) -> None:
-            for x in blocks:
-                gsrc.setdefault(x, []).append(gid)
-
-        def level_of(blocks) -> int:
-            return 1 + max((producer[x]["lf"] if x in producer else 0) for x in blocks)
-
-        def gather(ch_f) -> list:
-            lst: list = []
-            for p, q in ch_f:
-                lst += vals[(int(p), int(q))]
-            return lst
-
-        def shorten(lst: list) -> list:
-            """A list of more than MAX_LIST blocks: materialise its sum (one NSUM job); the gradient of every member is the
-            gradient of the sum."""
-            if len(lst) <= MAX_LIST:
-                return lst
-            out = ("x", extra())
-            job = {"ins": list(lst), "out": out, "lf": level_of(lst)}
-            self.nsum_jobs.append(job)
-            producer[out] = job
-            feed(lst, ("ref", out))
-            return [out]
-
-        final_mix = None
-        for i, (spec, l) in enumerate(zip(plan.layers, c.layers)):
-            ch = c._children[i]
-            F = l.num_folds
-            if isinstance(l, HipCategoricalLayer) and type(l) is HipCategoricalLayer:
-                if l.num_output_units != K or l.probs is None or l.probs.softmax_source() is None:
-                    return f"layer {i}: Categorical layers need 64 units and probs = softmax(tensor)"
-                name = l.probs.graph.nodes[0].config["tensor"]
-                for f in range(F):
-                    vals[(i, f)] = [("a", i, f)]
-                    if not claim(name, f, f"layer {i}"):
-                        return f"tensor {name} is shared"
-                self.inputs.append(i)
-                if l.scope_idx.shape[1] == 1 and ((l.num_categories + 1) * 65 + 1280) * 4 + (2 * 16 * ((l.num_categories + 16) // 16) + 4100) * 4 <= 160 * 1024:
-                    self.cat.add(i)  # its folds' backward (+ optimizer + next table) is one launch of jobs (`ck_jobs_cat_bwd`)
-            elif isinstance(l, HipGaussianLayer):
-                if l.num_output_units != K or l.log_partition is not None or (set(l.mean.ops) | set(l.stddev.ops)) - tr._PARAM_OPS:
-                    return f"layer {i}: Gaussian layers need 64 units, no log-partition and plain parameters"
-                for f in range(F):
-                    vals[(i, f)] = [("a", i, f)]
-                self.inputs.append(i)
-                # mean = a tensor, stddev = a tensor or its scaled sigmoid (what the templates build): the fold's backward is a
-                # job of its own (`ck_jobs_gauss_bwd`) reading its gradient list; anything else takes the layer-wise launches
-                recs = []
-                for f in range(F):
-                    em, es = _out_expr(l.mean.graph, f), _out_expr(l.stddev.graph, f)
-                    ss = es[0] == "scaled_sigmoid"
-                    et = es[3] if ss else es
-                    if em[0] != "tensor" or et[0] != "tensor" or l.scope_idx.shape[1] != 1:
-                        recs = None
-                        break
-                    cfg = l.stddev.graph.nodes[es[1]].config if ss else {}
-                    recs.append({"mean": (em[3], em[2]), "sd": (et[3], et[2]), "ss": ss, "vmin": float(cfg.get("vmin", 0.0)),
-                                 "vmax": float(cfg.get("vmax", 1.0))})
-                if recs is not None and all(claim(r["mean"][0], r["mean"][1], f"layer {i}") and claim(r["sd"][0], r["sd"][1], f"layer {i}")
-                                            for r in recs):
-                    self.gauss[i] = recs
-            elif isinstance(l, HipHadamardLayer):
-                for f in range(F):
-                    lst = gather(ch[f])
-                    if len(lst) <= MAX_LIST:
-                        vals[(i, f)] = lst  # virtual: the product is the list
-                    else:
-                        out = ("a", i, f)
-                        job = {"ins": lst, "out": out, "lf": level_of(lst)}
-                        self.nsum_jobs.append(job)
-                        producer[out] = job
-                        feed(lst, ("ref", out))
-                        vals[(i, f)] = [out]
-            elif isinstance(l, (HipSumLayer, HipCPTLayer)) and not isinstance(l, HipTuckerLayer):
-                Ki, Ko = l.num_input_units, l.num_output_units
-                prod = l._mode == capi.CK_SUM_PROD or l.arity == 1
-                if Ko == 1 and Ki == K and prod and l.weight.softmax_source() is not None:
-                    name = l.weight.graph.nodes[0].config["tensor"]
-                    for f in range(F):
-                        if not claim(name, f, f"layer {i}"):
-                            return f"tensor {name} is shared"
-                        scalars[(i, f)] = {"layer": i, "fold": f, "ins": shorten(gather(ch[f])), "theta": (name, f)}
-                elif Ko == 1 and Ki == 1 and l._mixing and l.weight.mixing_softmax_source() is not None and F == 1 and i == po:
-                    name = l.weight.graph.nodes[0].config["tensor"]
-                    if not claim(name, 0, f"layer {i}"):
-                        return f"tensor {name} is shared"
-                    kids = [(int(p), int(q)) for p, q in ch[0]]
-                    if any(k not in scalars for k in kids) or len(set(kids)) != len(kids):
-                        return "the final mixing layer must read distinct scalar sum folds"
-                    final_mix = {"layer": i, "kids": kids, "theta": (name, 0)}
-                elif Ki == K and Ko == K and l._mixing and l.weight.mixing_softmax_source() is not None:
-                    if l.arity > 16:
-                        return f"layer {i}: a mixing layer over more than 16 slots"
-                    name = l.weight.graph.nodes[0].config["tensor"]
-                    for f in range(F):
-                        if not claim(name, f, f"layer {i}"):
-                            return f"tensor {name} is shared"
-                        self._add_mix(i, f, [vals[(int(p), int(q))] for p, q in ch[f]], ("a", i, f), ("layer", i, f), (name, f),
-                                      shorten, level_of, producer, feed, extra)
-                        vals[(i, f)] = [("a", i, f)]
-                elif Ki == K and Ko == K and prod and l.weight.softmax_source() is not None:
-                    name = l.weight.graph.nodes[0].config["tensor"]
-                    for f in range(F):
-                        if not claim(name, f, f"layer {i}"):
-                            return f"tensor {name} is shared"
-                        ins = shorten(gather(ch[f]))
-                        job = {"layer": i, "fold": f, "ins": ins, "out": ("a", i, f), "gx": ("x", extra()), "w": ("layer", i, f),
-                               "theta": (name, f), "lf": level_of(ins)}
-                        self.sum_jobs.append(job)
-                        producer[job["out"]] = job
-                        feed(ins, job["gx"])
-                        vals[(i, f)] = [job["out"]]
-                elif Ki == K and Ko == K and l._mode == capi.CK_SUM_CAT and l.arity > 1 and not l._mixing:
-                    # per fold: a mixing weight, or a dense weight times a mixing weight (the collapsed pair)
-                    g = l.weight.graph
-                    if l.arity > 16:
-                        return f"layer {i}: more than 16 slots"
-                    for f in range(F):
-                        e = _out_expr(g, f)
-                        slots = [vals[(int(p), int(q))] for p, q in ch[f]]
-                        if e[0] == "mixing_weight" and _is_softmax_of_tensor(g, e[3]):
-                            sm = e[3]
-                            if not claim(sm[3][3], sm[3][2], f"layer {i}"):
-                                return f"tensor {sm[3][3]} is shared"
-                            self._add_mix(i, f, slots, ("a", i, f), ("node", i, sm[1], sm[2]), (sm[3][3], sm[3][2]),
-                                          shorten, level_of, producer, feed, extra)
-                        elif (e[0] == "matmul" and _is_softmax_of_tensor(g, e[3]) and e[4][0] == "mixing_weight"
-                              and _is_softmax_of_tensor(g, e[4][3])):
-                            sd, sm = e[3], e[4][3]
-                            if not claim(sd[3][3], sd[3][2], f"layer {i}") or not claim(sm[3][3], sm[3][2], f"layer {i}"):
-                                return f"tensors of layer {i} are shared"
-                            mid = ("x", extra())
-                            self._add_mix(i, f, slots, mid, ("node", i, sm[1], sm[2]), (sm[3][3], sm[3][2]),
-                                          shorten, level_of, producer, feed, extra)
-                            job = {"layer": i, "fold": f, "ins": [mid], "out": ("a", i, f), "gx": ("x", extra()),
-                                   "w": ("node", i, sd[1], sd[2]), "theta": (sd[3][3], sd[3][2]), "lf": level_of([mid])}
-                            self.sum_jobs.append(job)
-                            producer[job["out"]] = job
-                            feed([mid], job["gx"])
-                        else:
-                            return f"layer {i}: weight parameterisation {l.weight.ops}"
-                        vals[(i, f)] = [("a", i, f)]
-                else:
-                    return f"layer {i}: a {spec.type} layer of {Ki} -> {Ko} units, arity {l.arity}, weight {l.weight.ops}"
-            else:
-                return f"layer {i}: layer type {spec.type!r}"
-        # (tensor folds nobody reads keep a zero gradient: the flat gradient buffer starts as zeros and only claimed folds are written)
-        # the root: the scalar folds in the order the final mixing layer reads them
-        if final_mix is not None:
-            order = final_mix["kids"]
-            if set(order) != set(scalars):
-                return "scalar sum folds outside the final mixing layer"
-        else:
-            if len(scalars) != 1 or (po, fo) not in scalars:
-                return "the circuit must end in a scalar sum fold or a final mixing layer over scalar sum folds"
-            order = [(po, fo)]
-        if len(order) > 16:
-            return "more than 16 scalar folds under the final mixing layer"
-        g0 = extra(len(order))
-        self.root = {"folds": [scalars[k] for k in order], "mix": final_mix, "gx0": g0, "zero": extra()}  # (a block nobody writes)
-        for r, k in enumerate(order):
-            feed(scalars[k]["ins"], ("x", g0 + r))
-        if not self.sum_jobs:
-            return "no 64-unit sum layer"
-
-        # a Categorical layer whose folds are only read by sum jobs, each as the job's single input, is never evaluated: those jobs
-        # gather the rows of its log-probability table themselves
-        self.gathered: set[int] = set()
-        if self.cat:
-            seen: dict[int, bool] = {i: True for i in self.cat}
-            def note(blocks, ok: bool) -> None:
-                for x in blocks:
-                    if x[0] == "a" and x[1] in seen and not ok:
-                        seen[x[1]] = False
-            for j in self.sum_jobs:
-                note(j["ins"], len(j["ins"]) == 1)
-            for j in self.mix_jobs:
-                note([x for sl in j["slots"] for x in sl], False)
-            for j in self.nsum_jobs:
-                note(j["ins"], False)
-            for k in order:
-                note(scalars[k]["ins"], False)
-            self.gathered = {i for i, ok in seen.items() if ok and (po != i)}
-            for j in self.sum_jobs:
-                x = j["ins"][0]
-                if len(j["ins"]) == 1 and x[0] == "a" and x[1] in self.gathered:
-                    j["gather"] = (x[1], x[2])
-        # gradient lists: expand references to kept products, then materialise lists that several readers share
-        memo: dict[tuple, tuple] = {}
-
-        def sources(x) -> tuple:
-            if x in memo:
-                return memo[x]
-            out: list = []
-            for gsid in gsrc.get(x, []):
-                if gsid[0] == "ref":
-                    out += list(sources(gsid[1]))
-                else:
-                    out.append(gsid)
-            memo[x] = tuple(out)
-            return memo[x]
-
-        # a mixing fold whose every factor is the output of a sum job that nobody else reads has no backward launch: each of
-        # those sum jobs forms its own gradient from the MIXING fold's gradient list (ck_sum_job.mix_out), and one job per slot
-        # leaves d w[:, h]; the softmax behind the coefficients is differentiated by one launch for all such folds at the end
-        sum_of = {j["out"]: j for j in self.sum_jobs}
-        self.mix_fold_bwd = FOLD_MIX_BWD
-        for r in (self.mix_jobs if FOLD_MIX_BWD else []):
-            ok = True
-            for h, sl in enumerate(r["slots"]):
-                for x in sl:
-                    if x not in sum_of or gsrc.get(x) != [("x", r["gx0"] + h)] or "mix" in sum_of[x]:
-                        ok = False
-            if not ok or r["S"] > 4:
-                continue
-            r["folded"] = True
-            for h, sl in enumerate(r["slots"]):
-                for k, x in enumerate(sl):
-                    sum_of[x]["mix"] = {"job": r, "h": h, "partners": [y for y in sl if y is not x], "writer": k == 0}
-        for j in self.sum_jobs:
-            j["gof"] = j["mix"]["job"]["out"] if "mix" in j else j["out"]  # the block whose gradient list the job reads
-        live_mix = [r for r in self.mix_jobs if not r.get("folded")]
-        for r in live_mix:
-            r["gof"] = r["out"]
-        readers: dict[tuple, int] = {}
-        wanted = [j["gof"] for j in self.sum_jobs + live_mix] + [("a", i, f) for i in self.inputs for f in range(c.layers[i].num_folds)]
-        for x in wanted:
-            readers[sources(x)] = readers.get(sources(x), 0) + 1
-        self.gsum_jobs: list[dict] = []
-        shared: dict[tuple, tuple] = {}
-        for lst, n in readers.items():
-            if len(lst) >= 3 and n >= 2:
-                out = ("x", extra())
-                shared[lst] = out
-                self.gsum_jobs.append({"ins": list(lst), "out": out})
-        self._sources = lambda x: ((shared[sources(x)],) if sources(x) in shared else sources(x))
-        for j in self.sum_jobs + live_mix:
-            j["g"] = list(self._sources(j["gof"]))
-            if not j["g"]:
-                return f"layer {j['layer']} fold {j['fold']} feeds nothing"
-        # backward levels: the root is level 0; a job follows the writers of its gradient list
-        writer: dict[tuple, dict] = {}
-        for r in range(len(order)):
-            writer[("x", g0 + r)] = {"lb": 0}
-        for j in self.sum_jobs:
-            writer[j["gx"]] = j
-        for j in live_mix:
-            for h in range(j["H"]):
-                writer[("x", j["gx0"] + h)] = j
-        for j in self.gsum_jobs:
-            writer[j["out"]] = j
-
-        def lb(j: dict) -> int:
-            if "lb" not in j:
-                j["lb"] = 1 + max(lb(writer[gsid]) for gsid in (j["g"] if "g" in j else j["ins"]))
-            return j["lb"]
-
-        for j in self.sum_jobs + live_mix + self.gsum_jobs:
-            lb(j)
-        # the gradient of every input-layer fold, gathered into a contiguous (F, B, 64) block per layer for its backward
-        self.input_g: dict[int, dict] = {}
-        for i in self.inputs:
-            Fi = c.layers[i].num_folds
-            first = -1 if (i in self.gauss or i in self.cat) else extra(Fi)
-            lists = [list(self._sources(("a", i, f))) for f in range(Fi)]
-            if any(not lst for lst in lists):
-                return f"input layer {i} has a fold nobody reads"
-            self.input_g[i] = {"first": first, "lists": lists,
-                               "lb": 1 + max(lb(writer[gsid]) for lst in lists for gsid in lst)}
-        return None
-
-    def _add_mix(self, i, f, slots, out, w, theta, shorten, level_of, producer, feed, extra) -> None:
-        S = max(len(s) for s in slots)
-        if any(len(s) != S for s in slots):  # uniform slot length: longer products are kept
-            slots = [shorten(s) if len(s) > 1 else s for s in slots]
-            S = max(len(s) for s in slots)
-            if any(len(s) != S for s in slots):
-                raise NotImplementedError("mixing slots that are products of different numbers of blocks")
-        H = len(slots)
-        flat = [x for s in slots for x in s]
-        job = {"layer": i, "fold": f, "slots": slots, "H": H, "S": S, "out": out, "gx0": extra(H), "w": w, "theta": theta,
-               "lf": level_of(flat)}
-        self.mix_jobs.append(job)
-        producer[out] = job
-        for h, s in enumerate(slots):
-            feed(s, ("x", job["gx0"] + h))
-
-    # ---- binding ----------------------------------------------------------------------------------------------------------
-    def _weight_ptr(self, w) -> int:
-        c = self.c
+    def weight_ptr(self, w) -> int:
         if w[0] == "layer":
-            l = c.layers[w[1]]
-            return l._w.data_ptr() + w[2] * (l._w.numel() // l._w.shape[0]) * 4
-        _, i, node, fold = w  # the evaluated softmax node of a parameter graph that `prepare` evaluates node by node
-        t = c.layers[i].weight._last_outs[node]
+            t, fold = self.c.layers[w[1]]._w, w[2]
+        else:  # the evaluated softmax node of a parameter graph that `prepare` evaluates node by node
+            t, fold = self.c.layers[w[1]].weight._last_outs[w[2]], w[3]
         return t.data_ptr() + fold * (t.numel() // t.shape[0]) * 4
 
-    def _uncovered(self) -> list[int]:
-        """Input layers whose parameters no job epilogue updates (their gradients go to the flat buffer; the fused step runs
-        the optimizer on their tensors' ranges and re-evaluates their parameter graphs at its start)."""
-        return [i for i in self.inputs if i not in self.gauss and i not in self.cat]
+    def param_ptrs(self, theta) -> tuple[int, int, int, int]:
+        """(theta, m1, m2, d theta) of a tensor fold: what every table's parameter columns hold."""
+        name, fold = theta
+        m1, m2 = self.tr._moments.get(name, (None, None))
+        return tuple(0 if t is None else t.data_ptr() + fold * (t.numel() // t.shape[0]) * 4
+                     for t in (self.c.store[name], m1, m2, self.tr.grads[name]))
 
-    def opt_counters(self) -> tuple[int, int]:
-        """(steps taken, steps dropped) of the trainer's device clock, which the job epilogues advance (a device read)."""
-        return self.tr.opt_counters()
+    def weight_cols(self, j) -> dict:
+        """The weight and parameter columns of a sum / mixing table row."""
+        th, m1, m2, dth = self.param_ptrs(j.theta)
+        w = self.weight_ptr(j.w)
+        return dict(w=w, w_out=w, theta=th, m1=m1, m2=m2, dtheta=dth)
 
-    def bind(self, B: int) -> dict:
-        tr, c = self.tr, self.c
-        bd = c._bind(B)
-        st = self._bound.get(B)
-        if st is not None and st["serial"] == bd.serial and st["store_version"] == c.store.version:
-            return st
-        if st is not None:  # (a rebuilt circuit binding: the recorded lists point at its old staging copies and [sum, count] pair)
-            for pr in self._bound.pop(B)["prog"].values():
-                pr.close()
-        dev = c.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            c._enqueue_params(stream)  # (allocates every derived-parameter buffer the tables below point at)
-            torch.cuda.synchronize(dev)
-        n_cu = c._n_cu
-        blk = B * K
-        extra = torch.zeros(max(1, self.n_extra) * blk, dtype=torch.float32, device=dev)
-        x0 = extra.data_ptr()
+    def upload(self, kind: str, tab: np.ndarray, both_modes: bool, **kw) -> Launch:
+        """The launch over the DEVICE copy of a job table -- for the backward launches one copy per mode (1: d theta to the
+        flat gradient, 2: the optimizer's update in the epilogue)."""
+        out = {}
+        for mode in ((1, 2) if both_modes else (1,)):
+            if both_modes:
+                tab["mode"] = mode
+            out[mode] = torch.from_numpy(tab.view(np.uint8).reshape(len(tab), -1).copy()).to(self.dev)
+        self.keep.extend(out.values())
+        return Launch(kind, out, len(tab), **kw)
 
-        def addr(x) -> int:
-            if x[0] == "a":
-                v = bd.views[x[1]]
-                return v.data_ptr() + x[2] * B * v.shape[2] * 4
-            return x0 + x[1] * blk * 4
+    def fill_splits(self, rows: np.ndarray, rows_per: int, fields: dict) -> None:
+        """The table rows of one job: `fields` in each, the row range of its own."""
+        for k, v in fields.items():
+            rows[k] = v
+        rows["split"], rows["n_split"], rows["mode"] = np.arange(len(rows)), len(rows), 1
+        rows["row0"] = rows["split"] * rows_per
+        rows["row1"] = np.minimum(self.B, rows["row0"] + rows_per)
 
-        pool: list[int] = []
+    def sum_table(self, jobs: list[SumJob], backward: bool) -> Launch:
+        B = self.B
+        splits, waves = sum_layout(len(jobs), self.tiles, self.n_cu, backward)
+        rows_of = [-(-self.tiles // s) * 32 for s in splits]  # (a job's pieces: whole 32-row tiles, as equal as they come)
+        first_unit = np.cumsum([0] + [-(-B // rp) for rp in rows_of])
+        n_units = int(first_unit[-1])
+        tab = np.zeros(n_units, dtype=np.dtype(capi.SUM_JOB_DTYPE))
+        part = tick = None
+        if backward and n_units > len(jobs):
+            part, tick = self.zeros(n_units * 4096), self.zeros(len(jobs), torch.int32)
+        for n, j in enumerate(jobs):
+            u0, u1 = int(first_unit[n]), int(first_unit[n + 1])
+            f = self.weight_cols(j)
+            if j.gather is not None:  # the input is a Categorical fold: the pool entry is its table, rows picked by the batch column
+                gl, gf = self.c.layers[j.gather[0]], j.gather[1]
+                f["C"], f["xrow"] = gl.num_categories, self.bd.xt_i.data_ptr() + int(gl.scope_idx[gf, 0]) * B * 4
+                f["in_off"], f["n_in"] = len(self.pool), 1
+                self.pool.append(gl._table.data_ptr() + gf * (gl.num_categories + 1) * K * 4)
+            else:
+                f["in_off"], f["n_in"] = self.put(j.ins)
+            f["g_off"], f["n_g"] = self.put(j.g) if backward else (0, 0)
+            f["out"], f["gx"] = self.addr(j.out), self.addr(j.gx)
+            if backward and j.mix is not None:
+                mj = j.mix.job
+                f["partner_off"], f["n_partner"] = self.put(j.mix.partners)
+                f["mix_out"], f["mix_w"], f["mix_h"], f["mix_H"] = self.addr(mj.out), self.weight_ptr(mj.w), j.mix.h, mj.H
+                f["mix_dw"] = self.mix_dw[id(mj)] if j.mix.writer else 0
+            if part is not None and u1 - u0 > 1:
+                f["part"], f["ticket"] = part.data_ptr() + u0 * 4096 * 4, tick.data_ptr() + n * 4
+            self.fill_splits(tab[u0:u1], rows_of[n], f)
+        return self.upload("sum_bwd" if backward else "sum_fwd", tab, backward, param=waves)
 
-        def put(blocks) -> tuple[int, int]:
-            off = len(pool)
-            pool.extend(addr(x) for x in blocks)
-            return off, len(blocks)
+    def mix_table(self, jobs: list[MixJob], backward: bool) -> Launch:
+        hmax = max(j.H for j in jobs)
+        hpad = 2 if hmax <= 2 else 4 if hmax <= 4 else 8 if hmax <= 8 else 16
+        ns, rows_per = mix_split(len(jobs), self.B, self.n_cu, backward, int(os.environ.get("CK_MIX_FWD_WG", "8")))
+        tab = np.zeros(len(jobs) * ns, dtype=np.dtype(capi.MIX_JOB_DTYPE))
+        part = tick = None
+        if backward and ns > 1:
+            part, tick = self.zeros(len(jobs) * ns * K * hpad), self.zeros(len(jobs), torch.int32)
+        for n, j in enumerate(jobs):
+            f = self.weight_cols(j)
+            f["in_off"], _ = self.put([x for s in j.slots for x in s])
+            f["g_off"], f["n_g"] = self.put(j.g) if backward else (0, 0)
+            f["out"], f["gx"], f["H"], f["S"] = self.addr(j.out), self.addr(("x", j.gx0)), j.H, j.S
+            if part is not None:
+                f["part"], f["ticket"] = part.data_ptr() + n * ns * K * hpad * 4, tick.data_ptr() + n * 4
+            self.fill_splits(tab[n * ns:(n + 1) * ns], rows_per, f)
+        return self.upload("mix_bwd" if backward else "mix_fwd", tab, backward, param=hmax)
 
-        def fold_ptr(t: torch.Tensor | None, fold: int) -> int:
-            return 0 if t is None else t.data_ptr() + fold * (t.numel() // t.shape[0]) * 4
+    def mix_params_table(self) -> Launch:
+        """The coefficients of the mixing folds without a backward launch: one launch for all of them."""
+        tab = np.zeros(len(self.folded), dtype=np.dtype(capi.MIX_JOB_DTYPE))
+        for r, j in zip(tab, self.folded):
+            for k, v in self.weight_cols(j).items():
+                r[k] = v
+            r["part"], r["H"], r["mode"] = self.mix_dw[id(j)], j.H, 1
+        return self.upload("mix_params", tab, True)
 
-        def grad_ptr(theta) -> int:
-            return fold_ptr(tr.grads[theta[0]], theta[1])
+    def nsum_table(self, kind: str, items: list[tuple[list, int]], **kw) -> Launch:
+        tab = np.zeros(len(items), dtype=np.dtype(capi.NSUM_JOB_DTYPE))
+        for r, (ins, out) in zip(tab, items):
+            r["in_off"], r["n_in"] = self.put(ins)
+            r["out"] = out
+        return self.upload(kind, tab, False, **kw)
 
-        def theta_ptrs(theta) -> tuple[int, int, int]:
-            m1, m2 = tr._moments.get(theta[0], (None, None))
-            return fold_ptr(c.store[theta[0]], theta[1]), fold_ptr(m1, theta[1]), fold_ptr(m2, theta[1])
+    def gauss_table(self, i: int) -> Launch:
+        l = self.c.layers[i]
+        mean, stddev, _ = l._vals
+        tab = np.zeros(len(self.g.gauss[i]), dtype=np.dtype(capi.GAUSS_JOB_DTYPE))
+        for f, (r, rec, lst) in enumerate(zip(tab, self.g.gauss[i], self.g.input_g[i].lists)):
+            r["th_mean"], r["m1_mean"], r["m2_mean"], r["dmean"] = self.param_ptrs(rec.mean)
+            r["th_sd"], r["m1_sd"], r["m2_sd"], r["dsd"] = self.param_ptrs(rec.sd)
+            r["mean"], r["stddev"] = mean.data_ptr() + f * K * 4, stddev.data_ptr() + f * K * 4
+            r["x"] = self.bd.xt.data_ptr() + int(l.scope_idx[f, 0]) * self.B * 4
+            r["mean_out"] = 0 if r["mean"] == r["th_mean"] else r["mean"]
+            r["sd_out"] = r["stddev"]
+            r["g_off"], r["n_g"] = self.put(lst)
+            r["vmin"], r["vmax"], r["has_ss"], r["mode"] = rec.vmin, rec.vmax, 1 if rec.ss else 0, 1
+        return self.upload("gauss_bwd", tab, True, layer=i)
 
-        tiles = (B + 31) // 32
-        keep: list[torch.Tensor] = [extra]
+    def cat_table(self, i: int) -> Launch:
+        l = self.c.layers[i]
+        name = l.probs.graph.nodes[0].config["tensor"]
+        tab = np.zeros(l.num_folds, dtype=np.dtype(capi.CAT_JOB_DTYPE))
+        for f, (r, lst) in enumerate(zip(tab, self.g.input_g[i].lists)):
+            r["theta"], r["m1"], r["m2"], r["dtheta"] = self.param_ptrs((name, f))
+            r["table"] = l._table.data_ptr() + f * (l.num_categories + 1) * K * 4
+            r["x"] = self.bd.xt_i.data_ptr() + int(l.scope_idx[f, 0]) * self.B * 4
+            r["theta_out"], r["table_out"] = r["theta"], r["table"]
+            r["g_off"], r["n_g"] = self.put(lst)
+            r["mode"] = 1
+        return self.upload("cat_bwd", tab, True, layer=i, param=l.num_categories)
 
-        def upload(tab: np.ndarray, both_modes: bool) -> dict:
-            """The DEVICE copy of a job table -- for the backward launches one per mode (1: d theta to the flat gradient,
-            2: the optimizer's update in the epilogue)."""
-            out = {}
-            for mode in ((1, 2) if both_modes else (1,)):
-                if both_modes:
-                    tab["mode"] = mode
-                t = torch.from_numpy(tab.view(np.uint8).reshape(len(tab), -1).copy()).to(dev)
-                keep.append(t)
-                out[mode] = t
-            return out
+    def input_table(self, i: int) -> Launch:
+        ig = self.g.input_g[i]
+        if i in self.g.gauss or i in self.g.cat:
+            return self.gauss_table(i) if i in self.g.gauss else self.cat_table(i)
+        return self.nsum_table("input_bwd", [(lst, self.x0 + (ig.first + f) * self.blk * 4) for f, lst in enumerate(ig.lists)], layer=i)
 
-        def splits_for(n_jobs: int, max_split: int) -> int:
-            return int(max(1, min(max_split, -(-2 * n_cu // max(1, n_jobs)))))
+    def launches(self) -> list[Launch]:
+        """Every launch in issue order: per level the kept products / shared gradients, the sum jobs, the mixing jobs."""
+        g = self.g
 
-        def sum_config(n_jobs: int, backward: bool) -> tuple[int, int]:
-            """(row splits per job, waves per workgroup) of a sum launch.  The launch runs in ROUNDS of as many workgroups as the
-            chip holds (backward: 2 per CU with 4 waves, 1 with 8; forward: 4 per CU) and a round lasts as long as one unit, so
-            1040 jobs on 512 slots take three rounds where 2.03 would do -- finer units waste less of the last round, at a fixed
-            cost per unit.  Measured [MI355X, scripts/exp_jobs_fixed.py]: a backward unit costs ~10 us beside its tiles (launch,
-            weights staged, accumulators reduced, optimizer epilogue), ~10 us more when its partial sums of dW go through memory,
-            and a tile ~10 us of a wave that has its SIMD to itself, ~14 us when two waves share it; forward ~3 us + 6 us per
-            tile.  Eight waves halve a unit's chain of tiles (what the few-fold levels at the top of a circuit consist of)."""
-            best, best_t = (1, 4), None
-            for waves in ((4, 8) if backward else (4,)):
-                slots = n_cu * ((2 if waves == 4 else 1) if backward else 4)
-                for sp in (1, 2, 3, 4, 6, 8, 12, 16):
-                    if sp > 1 and -(-tiles // sp) < waves:  # (at least a tile per wave)
-                        break
-                    per_wave = -(-(-(-tiles // sp)) // waves)
-                    if backward:
-                        shared = waves == 8 or n_jobs * sp > n_cu
-                        unit = 10.0 + (10.0 if sp > 1 else 0.0) + (14.0 if shared else 10.0) * per_wave
-                    else:
-                        unit = 3.0 + 6.0 * per_wave
-                    t = -(-n_jobs * sp // slots) * unit
-                    if best_t is None or t < best_t - 1e-9:
-                        best, best_t = (sp, waves), t
-            return best
-
-        folded = [r for r in self.mix_jobs if r.get("folded")]
-        mix_dw = torch.zeros(max(1, sum(K * r["H"] for r in folded)), dtype=torch.float32, device=dev)
-        keep.append(mix_dw)
-        mix_dw_off: dict[int, int] = {}
-        off_f = 0
-        for r in folded:
-            mix_dw_off[id(r)] = off_f
-            off_f += K * r["H"]
-
-        def mix_dw_ptr(r: dict) -> int:
-            return mix_dw.data_ptr() + 4 * mix_dw_off[id(r)]
-
-        def sum_layout(n_jobs: int, backward: bool) -> tuple[list[int], int]:
-            """(row splits of every job, waves per workgroup): `sum_config`'s uniform answer, or -- a backward launch of more
-            jobs than the chip holds -- whole jobs for the full rounds and only the REMAINDER cut fine, issued last: 1060 jobs
-            on 512 slots are two rounds of whole jobs + 36 jobs in 8 pieces each instead of three rounds."""
-            sp, waves = sum_config(n_jobs, backward)
-            if not backward:
-                return [sp] * n_jobs, waves
-
-            def unit(s_: int, w_: int, shared: bool) -> float:
-                per_wave = -(-(-(-tiles // s_)) // w_)
-                return 10.0 + (10.0 if s_ > 1 else 0.0) + (14.0 if shared else 10.0) * per_wave
-
-            slots_u = n_cu * (2 if waves == 4 else 1)
-            t_uniform = -(-n_jobs * sp // slots_u) * unit(sp, waves, waves == 8 or n_jobs * sp > n_cu)
-            best = ([sp] * n_jobs, waves, t_uniform)
-            for w_ in (4, 8):
-                slots = n_cu * (2 if w_ == 4 else 1)
-                full = (n_jobs // slots) * slots
-                rem = n_jobs - full
-                if full == 0 or rem == 0:
-                    continue
-                for sr in (2, 3, 4, 6, 8, 12, 16):
-                    if -(-tiles // sr) < w_:
-                        break
-                    t = (full // slots) * unit(1, w_, True) + -(-rem * sr // slots) * unit(sr, w_, True)
-                    if t < best[2] - 1e-9:
-                        best = ([1] * full + [sr] * rem, w_, t)
-            return best[0], best[1]
-
-        def sum_table(jobs: list[dict], backward: bool) -> tuple[dict, int, int]:
-            splits, waves = sum_layout(len(jobs), backward)
-            rows_of, first_unit, n_units = [], [], 0
-            for ns_j in splits:  # (a job's pieces: whole 32-row tiles, as equal as they come)
-                rp = -(-tiles // ns_j) * 32
-                rows_of.append(rp)
-                first_unit.append(n_units)
-                n_units += -(-B // rp)
-            tab = np.zeros(n_units, dtype=np.dtype(capi.SUM_JOB_DTYPE))
-            part = tick = None
-            if backward and n_units > len(jobs):
-                part = torch.zeros(n_units * 4096, dtype=torch.float32, device=dev)
-                tick = torch.zeros(len(jobs), dtype=torch.int32, device=dev)
-                keep.extend([part, tick])
-            for n, j in enumerate(jobs):
-                rows_per = rows_of[n]
-                ns = -(-B // rows_per)
-                u0 = first_unit[n]
-                xrow = Cg = 0
-                if "gather" in j:  # the input is a Categorical fold: the pool entry is its table, rows picked by the batch column
-                    gi, gf = j["gather"]
-                    gl = c.layers[gi]
-                    Cg = gl.num_categories
-                    xrow = bd.xt_i.data_ptr() + int(gl.scope_idx[gf, 0]) * B * 4
-                    ioff, inum = len(pool), 1
-                    pool.append(gl._table.data_ptr() + gf * (Cg + 1) * K * 4)
-                else:
-                    ioff, inum = put(j["ins"])
-                goff, gnum = put(j["g"]) if backward else (0, 0)
-                th, m1, m2 = theta_ptrs(j["theta"])
-                w = self._weight_ptr(j["w"])
-                mx = j.get("mix") if backward else None
-                if mx is not None:
-                    mj = mx["job"]
-                    poff, pnum = put(mx["partners"])
-                    m_out, m_w = addr(mj["out"]), self._weight_ptr(mj["w"])
-                    m_dw = mix_dw_ptr(mj) if mx["writer"] else 0
-                for sp in range(ns):
-                    r = tab[u0 + sp]
-                    r["xrow"], r["C"] = xrow, Cg
-                    if mx is not None:
-                        r["mix_out"], r["mix_w"], r["mix_dw"] = m_out, m_w, m_dw
-                        r["partner_off"], r["n_partner"], r["mix_h"], r["mix_H"] = poff, pnum, mx["h"], mj["H"]
-                    r["w"], r["out"], r["gx"], r["dtheta"] = w, addr(j["out"]), addr(j["gx"]), grad_ptr(j["theta"])
-                    r["theta"], r["m1"], r["m2"], r["w_out"] = th, m1, m2, w
-                    r["in_off"], r["n_in"], r["g_off"], r["n_g"] = ioff, inum, goff, gnum
-                    r["row0"], r["row1"] = sp * rows_per, min(B, (sp + 1) * rows_per)
-                    r["split"], r["n_split"], r["mode"] = sp, ns, 1
-                    if part is not None and ns > 1:
-                        r["part"], r["ticket"] = part.data_ptr() + u0 * 4096 * 4, tick.data_ptr() + n * 4
-            return upload(tab, backward), len(tab), waves
-
-        def mix_table(jobs: list[dict], backward: bool) -> tuple[dict, int, int]:
-            hmax = max(j["H"] for j in jobs)
-            hpad = 2 if hmax <= 2 else 4 if hmax <= 4 else 8 if hmax <= 8 else 16
-            ns = splits_for(len(jobs), max(1, B // 64))
-            if not backward:
-                # the forward has no sums over the rows: eight workgroups per CU instead of two (a workgroup is a chain of one
-                # round trip per 16 rows, and 256 threads with 4 KB of LDS leave room for eight of them)
-                ns = int(max(1, min(max(1, B // 64), -(-int(os.environ.get("CK_MIX_FWD_WG", "8")) * n_cu // max(1, len(jobs))))))
-            rows_per = -(-(-(-B // ns)) // 16) * 16
-            ns = -(-B // rows_per)
-            tab = np.zeros(len(jobs) * ns, dtype=np.dtype(capi.MIX_JOB_DTYPE))
-            part = tick = None
-            if backward and ns > 1:
-                part = torch.zeros(len(jobs) * ns * K * hpad, dtype=torch.float32, device=dev)
-                tick = torch.zeros(len(jobs), dtype=torch.int32, device=dev)
-                keep.extend([part, tick])
-            for n, j in enumerate(jobs):
-                ioff, _ = put([x for s in j["slots"] for x in s])
-                goff, gnum = put(j["g"]) if backward else (0, 0)
-                th, m1, m2 = theta_ptrs(j["theta"])
-                w = self._weight_ptr(j["w"])
-                for sp in range(ns):
-                    r = tab[n * ns + sp]
-                    r["w"], r["out"], r["gx"], r["dtheta"] = w, addr(j["out"]), addr(("x", j["gx0"])), grad_ptr(j["theta"])
-                    r["theta"], r["m1"], r["m2"], r["w_out"] = th, m1, m2, w
-                    r["in_off"], r["H"], r["S"], r["g_off"], r["n_g"] = ioff, j["H"], j["S"], goff, gnum
-                    r["row0"], r["row1"] = sp * rows_per, min(B, (sp + 1) * rows_per)
-                    r["split"], r["n_split"], r["mode"] = sp, ns, 1
-                    if part is not None:
-                        r["part"], r["ticket"] = part.data_ptr() + n * ns * K * hpad * 4, tick.data_ptr() + n * 4
-            return upload(tab, backward), len(tab), hmax
-
-        def nsum_table(items: list[tuple[list, int]]) -> tuple[dict, int]:
-            tab = np.zeros(len(items), dtype=np.dtype(capi.NSUM_JOB_DTYPE))
-            for r, (ins, out) in zip(tab, items):
-                r["in_off"], r["n_in"] = put(ins)
-                r["out"] = out
-            return upload(tab, False), len(tab)
-
-        def gauss_table(i: int) -> tuple[dict, int]:
-            l = c.layers[i]
-            mean, stddev, _ = l._vals
-            recs = self.gauss[i]
-            tab = np.zeros(len(recs), dtype=np.dtype(capi.GAUSS_JOB_DTYPE))
-            for f, (r, rec, lst) in enumerate(zip(tab, recs, self.input_g[i]["lists"])):
-                thm, m1m, m2m = theta_ptrs(rec["mean"])
-                ths, m1s, m2s = theta_ptrs(rec["sd"])
-                mp, sp_ = mean.data_ptr() + f * K * 4, stddev.data_ptr() + f * K * 4
-                r["mean"], r["stddev"] = mp, sp_
-                r["x"] = bd.xt.data_ptr() + int(l.scope_idx[f, 0]) * B * 4
-                r["dmean"], r["dsd"] = grad_ptr(rec["mean"]), grad_ptr(rec["sd"])
-                r["th_mean"], r["m1_mean"], r["m2_mean"] = thm, m1m, m2m
-                r["th_sd"], r["m1_sd"], r["m2_sd"] = ths, m1s, m2s
-                r["mean_out"] = 0 if mp == thm else mp
-                r["sd_out"] = sp_
-                r["g_off"], r["n_g"] = put(lst)
-                r["vmin"], r["vmax"], r["has_ss"], r["mode"] = rec["vmin"], rec["vmax"], 1 if rec["ss"] else 0, 1
-            return upload(tab, True), len(tab)
-
-        def cat_table(i: int) -> tuple[dict, int]:
-            l = c.layers[i]
-            name = l.probs.graph.nodes[0].config["tensor"]
-            Cn = l.num_categories
-            tab = np.zeros(l.num_folds, dtype=np.dtype(capi.CAT_JOB_DTYPE))
-            for f, (r, lst) in enumerate(zip(tab, self.input_g[i]["lists"])):
-                th, m1, m2 = theta_ptrs((name, f))
-                tb = l._table.data_ptr() + f * (Cn + 1) * K * 4
-                r["x"] = bd.xt_i.data_ptr() + int(l.scope_idx[f, 0]) * B * 4
-                r["theta"], r["table"], r["dtheta"] = th, tb, grad_ptr((name, f))
-                r["theta_out"], r["m1"], r["m2"], r["table_out"] = th, m1, m2, tb
-                r["g_off"], r["n_g"] = put(lst)
-                r["mode"] = 1
-            return upload(tab, True), len(tab)
-
-        def by_level(jobs: list[dict], key: str) -> dict[int, list[dict]]:
-            out: dict[int, list[dict]] = {}
+        def by_level(jobs: list, key: str) -> dict[int, list]:
+            out: dict[int, list] = {}
             for j in jobs:
-                out.setdefault(j[key], []).append(j)
+                out.setdefault(getattr(j, key), []).append(j)
             return out
 
-        launches: list[tuple] = []  # (what, table(s), n, ...), in issue order
-        fs, fm, fn = by_level(self.sum_jobs, "lf"), by_level(self.mix_jobs, "lf"), by_level(self.nsum_jobs, "lf")
-        for lv in sorted(set(fs) | set(fm) | set(fn)):
-            if lv in fn:
-                launches.append(("nsum",) + nsum_table([(j["ins"], addr(j["out"])) for j in fn[lv]]))
-            if lv in fs:
-                launches.append(("sum_fwd",) + sum_table(fs[lv], False))
-            if lv in fm:
-                launches.append(("mix_fwd",) + mix_table(fm[lv], False))
-        launches.append(("root",))
-        bs, bm, bg = (by_level(self.sum_jobs, "lb"), by_level([r for r in self.mix_jobs if not r.get("folded")], "lb"),
-                      by_level(self.gsum_jobs, "lb"))
+        def level_launches(nsum: dict, sums: dict, mixes: dict, inputs: dict, backward: bool) -> list[Launch]:
+            out = []
+            for lv in sorted(set(nsum) | set(sums) | set(mixes) | set(inputs)):
+                if lv in nsum:
+                    out.append(self.nsum_table("nsum", [(j.ins, self.addr(j.out)) for j in nsum[lv]]))
+                if lv in sums:
+                    out.append(self.sum_table(sums[lv], backward))
+                if lv in mixes:
+                    out.append(self.mix_table(mixes[lv], backward))
+                out += [self.input_table(i) for i in inputs.get(lv, [])]
+            return out
+
         bi: dict[int, list[int]] = {}
-        for i, ig in self.input_g.items():
-            bi.setdefault(ig["lb"], []).append(i)
-        for lv in sorted(set(bs) | set(bm) | set(bg) | set(bi)):
-            if lv in bg:
-                launches.append(("nsum",) + nsum_table([(j["ins"], addr(j["out"])) for j in bg[lv]]))
-            if lv in bs:
-                launches.append(("sum_bwd",) + sum_table(bs[lv], True))
-            if lv in bm:
-                launches.append(("mix_bwd",) + mix_table(bm[lv], True))
-            for i in bi.get(lv, []):
-                ig = self.input_g[i]
-                if i in self.gauss:
-                    launches.append(("gauss_bwd", i) + gauss_table(i))
-                elif i in self.cat:
-                    launches.append(("cat_bwd", i) + cat_table(i))
-                else:
-                    launches.append(("input_bwd", i) + nsum_table([(lst, x0 + (ig["first"] + f) * blk * 4) for f, lst in enumerate(ig["lists"])]))
-        if folded:  # the coefficients of the mixing folds without a backward launch: one launch for all of them
-            tab = np.zeros(len(folded), dtype=np.dtype(capi.MIX_JOB_DTYPE))
-            for r, j in zip(tab, folded):
-                th, m1, m2 = theta_ptrs(j["theta"])
-                w = self._weight_ptr(j["w"])
-                r["w"], r["dtheta"], r["theta"], r["m1"], r["m2"], r["w_out"] = w, grad_ptr(j["theta"]), th, m1, m2, w
-                r["part"], r["H"], r["mode"] = mix_dw_ptr(j), j["H"], 1
-            launches.append(("mix_params",) + (upload(tab, True), len(tab)))
-        # the root launch
-        root = self.root
-        R = len(root["folds"])
+        for i, ig in g.input_g.items():
+            bi.setdefault(ig.lb, []).append(i)
+        out = level_launches(by_level(g.nsum_jobs, "lf"), by_level(g.sum_jobs, "lf"), by_level(g.mix_jobs, "lf"), {}, False)
+        out.append(Launch("root"))
+        out += level_launches(by_level(g.gsum_jobs, "lb"), by_level(g.sum_jobs, "lb"),
+                              by_level([r for r in g.mix_jobs if not r.folded], "lb"), bi, True)
+        return out + ([self.mix_params_table()] if self.folded else [])
+
+    def root(self, opt) -> dict[int, capi.RootLaunch]:
+        """The root launch's arguments per mode (after every table: its lists close the pool, which is uploaded here)."""
+        c, bd, B, root = self.c, self.bd, self.B, self.g.root
+        R = len(root.folds)
         rin = np.zeros((2, R), dtype=np.int32)
         ptrs = np.zeros((6, R), dtype=np.uint64)  # w, dtheta, theta, m1, m2, w_out
-        S_root = max(len(sc["ins"]) for sc in root["folds"])
-        for r, sc in enumerate(root["folds"]):  # (lists of one length: shorter ones are padded with the block of zeros)
-            rin[0, r], rin[1, r] = put(list(sc["ins"]) + [("x", root["zero"])] * (S_root - len(sc["ins"])))
-            l = c.layers[sc["layer"]]
-            w = l._w.data_ptr() + sc["fold"] * K * 4
-            th, m1, m2 = theta_ptrs(sc["theta"])
-            ptrs[:, r] = (w, grad_ptr(sc["theta"]), th, m1, m2, w)
-        rin_d = torch.from_numpy(rin).to(dev)
-        ptrs_d = torch.from_numpy(ptrs.view(np.int64)).to(dev)
+        S_root = max(len(sc.ins) for sc in root.folds)
+        for r, sc in enumerate(root.folds):  # (lists of one length: shorter ones are padded with the block of zeros)
+            rin[0, r], rin[1, r] = self.put(list(sc.ins) + [("x", root.zero)] * (S_root - len(sc.ins)))
+            w = c.layers[sc.layer]._w.data_ptr() + sc.fold * K * 4
+            th, m1, m2, dth = self.param_ptrs(sc.theta)
+            ptrs[:, r] = (w, dth, th, m1, m2, w)
+        rin_d = torch.from_numpy(rin).to(self.dev)
+        ptrs_d = torch.from_numpy(ptrs.view(np.int64)).to(self.dev)
         n_wg = int(max(1, min(64, B // 4)))  # (a row per wave up to 256 rows: the launch is a chain of row-long round trips)
-        rpart = torch.zeros(n_wg * 1042, dtype=torch.float32, device=dev)
-        rtick = torch.zeros(1, dtype=torch.int32, device=dev)
-        seed = torch.zeros(B, dtype=torch.float32, device=dev)
-        pool_d = torch.from_numpy(np.asarray(pool, dtype=np.uint64).view(np.int64)).to(dev)
-        keep.extend([rin_d, ptrs_d, rpart, rtick, seed, pool_d])
-        opt = tr._opt_state()
-
-        def root_args(mode: int):
-            ra = capi.RootLaunch()
-            ra.pool, ra.in_off, ra.n_in = pool_d.data_ptr(), rin_d[0].data_ptr(), rin_d[1].data_ptr()
+        rpart, rtick, self.seed = self.zeros(n_wg * 1042), self.zeros(1, torch.int32), self.zeros(B)
+        self.pool_d = torch.from_numpy(np.asarray(self.pool, dtype=np.uint64).view(np.int64)).to(self.dev)
+        self.keep.extend([rin_d, ptrs_d, self.pool_d])
+        po, fo = int(c._out_pairs[0, 0]), int(c._out_pairs[0, 1])
+        validate = c.validate_inputs and c._int_input
+        out = {}
+        for mode in (1, 2):
+            ra = out[mode] = capi.RootLaunch()
+            ra.pool, ra.in_off, ra.n_in = self.pool_d.data_ptr(), rin_d[0].data_ptr(), rin_d[1].data_ptr()
             ra.w, ra.dtheta_w, ra.theta_w = ptrs_d[0].data_ptr(), ptrs_d[1].data_ptr(), ptrs_d[2].data_ptr()
             ra.m1_w, ra.m2_w, ra.w_out = ptrs_d[3].data_ptr(), ptrs_d[4].data_ptr(), ptrs_d[5].data_ptr()
-            po, fo = int(c._out_pairs[0, 0]), int(c._out_pairs[0, 1])
             ra.out = bd.views[po][fo].data_ptr()
-            ra.gx, ra.seed, ra.ll = x0 + root["gx0"] * blk * 4, seed.data_ptr(), bd.ll.data_ptr()
+            ra.gx, ra.seed, ra.ll = self.x0 + root.gx0 * self.blk * 4, self.seed.data_ptr(), bd.ll.data_ptr()
             ra.part, ra.ticket = rpart.data_ptr(), rtick.data_ptr()
-            if root["mix"] is not None:
-                lm = c.layers[root["mix"]["layer"]]
-                th, m1, m2 = theta_ptrs(root["mix"]["theta"])
-                ra.c, ra.dtheta_c = lm._w.data_ptr(), grad_ptr(root["mix"]["theta"])
-                ra.theta_c, ra.m1_c, ra.m2_c, ra.c_out = th, m1, m2, lm._w.data_ptr()
-            validate = c.validate_inputs and c._int_input
+            if root.mix is not None:
+                ra.theta_c, ra.m1_c, ra.m2_c, ra.dtheta_c = self.param_ptrs(root.mix.theta)
+                ra.c = ra.c_out = c.layers[root.mix.layer]._w.data_ptr()
             # mode 1: the circuit's own flag (latched after the step by the trainer); mode 2: `ck_opt_tick` has moved it into
             # the optimizer state's skip_now by the time the root launch runs
             ra.opt = opt.ptr if mode == 2 else None
             ra.bad_flag = opt.skip_now_ptr if mode == 2 else (c._bad_input.data_ptr() if validate else None)
             ra.seed_const, ra.R, ra.B, ra.mode, ra.n_wg, ra.S = 0.0, R, B, mode, n_wg, S_root
-            return ra
+        return out
 
-        st = {"serial": bd.serial, "store_version": c.store.version, "keep": keep, "launches": launches,
-              "root": {1: root_args(1), 2: root_args(2)}, "pool": pool_d, "seed": seed, "seed_value": None, "extra": extra, "x0": x0,
-              "prog": {}, "dT": {}}
+
+class JobStep:
+    """Structure (independent of the batch size: `graph`) + per-batch-size bindings of the job form of a training step."""
+
+    def __init__(self, trainer) -> None:
+        self.tr = trainer
+        c = self.c = trainer.circuit
+        self._bound: dict[int, dict] = {}
+        self._own_state = None  # the store's state after this object's last in-place update (fused optimizer)
+        g = build_job_graph(trainer.plan, c.layers, c._children, c._out_pairs, c._complex, trainer._PARAM_OPS)
+        self.why, self.graph = (g, None) if isinstance(g, str) else (None, g)
+        self.sum_jobs, self.mix_jobs = ([], []) if self.graph is None else (self.graph.sum_jobs, self.graph.mix_jobs)
+
+    def _uncovered(self) -> list[int]:
+        """Input layers whose parameters no job epilogue updates (their gradients go to the flat buffer; the fused step runs
+        the optimizer on their tensors' ranges and re-evaluates their parameter graphs at its start)."""
+        return [i for i in self.graph.inputs if i not in self.graph.gauss and i not in self.graph.cat]
+
+    def opt_counters(self) -> tuple[int, int]:
+        """(steps taken, steps dropped) of the trainer's device clock, which the job epilogues advance (a device read)."""
+        return self.tr.opt_counters()
+
+    # ---- binding ----------------------------------------------------------------------------------------------------------
+    def _drop(self, B: int) -> None:  # (the recorded programs of a binding hold its pointers)
+        for pr in self._bound.pop(B)["prog"].values():
+            pr.close()
+
+    def bind(self, B: int) -> dict:
+        c = self.c
+        bd = c._bind(B)
+        st = self._bound.get(B)
+        if st is not None and st["serial"] == bd.serial and st["store_version"] == c.store.version:
+            return st
+        if st is not None:  # (a rebuilt circuit binding: the recorded lists point at its old staging copies and [sum, count] pair)
+            self._drop(B)
+        with torch.cuda.device(c.device):
+            c._enqueue_params(torch.cuda.current_stream(c.device).cuda_stream)  # (allocates every derived-parameter buffer the tables point at)
+            torch.cuda.synchronize(c.device)
+        t = _Tables(self, bd, B)
+        launches = t.launches()
+        root = t.root(self.tr._opt_state())  # (last: its lists close the pool)
+        st = {"serial": bd.serial, "store_version": c.store.version, "keep": t.keep, "launches": launches, "root": root,
+              "pool": t.pool_d, "seed": t.seed, "seed_value": None, "extra": t.extra, "x0": t.x0, "prog": {}, "dT": {}}
         while len(self._bound) >= 4:
-            old = self._bound.pop(next(iter(self._bound)))
-            for pr in old["prog"].values():
-                pr.close()
+            self._drop(next(iter(self._bound)))
         self._bound[B] = st
         return st
 
@@ -763,13 +342,29 @@ class JobStep:
             prog = st["prog"][mode] = capi.Program.record(lambda: self._enqueue(bd, st, B, mode, 0))
         return prog
 
+    def _issue(self, la: Launch, bd, st: dict, B: int, mode: int, stream: int) -> None:
+        """One launch of a binding: the one place that knows each kind's entry point and arguments (mode 2: the optimizer
+        state goes to the backward launches' epilogues)."""
+        if la.kind == "root":
+            return capi.call("ck_jobs_root", C.byref(st["root"][mode]), stream)
+        pool, blk = st["pool"].data_ptr(), B * K
+        opt = self.tr._opt_state().ptr if mode == 2 else None
+        entry, args = {
+            "nsum": ("ck_jobs_nsum", (pool, blk)), "input_bwd": ("ck_jobs_nsum", (pool, blk)),
+            "sum_fwd": ("ck_jobs_sum64_fwd", (pool,)), "sum_bwd": ("ck_jobs_sum64_bwd", (pool, opt, la.param)),
+            "mix_fwd": ("ck_jobs_mix_fwd", (pool, la.param)), "mix_bwd": ("ck_jobs_mix_bwd", (pool, la.param, blk, opt)),
+            "mix_params": ("ck_jobs_mix_params", (opt,)), "gauss_bwd": ("ck_jobs_gauss_bwd", (pool, B, opt)),
+            "cat_bwd": ("ck_jobs_cat_bwd", (pool, B, la.param, opt)),
+        }[la.kind]
+        capi.call(entry, la.table(mode), la.n, *args, stream)
+        if la.kind == "input_bwd":  # (its gathered gradient block goes through the layer-wise trainer's launches)
+            self._input_backward(la.layer, bd, st, B, stream)
+
     def _enqueue(self, bd, st: dict, B: int, mode: int, stream: int) -> None:
         """mode 1: parameters, forward, backward with d theta into the trainer's flat gradient (the optimizer launch and the
         collective follow outside).  mode 2 (one rank): the optimizer runs in the job epilogues -- `ck_opt_tick` first, the
         parameter graphs of the layers no epilogue covers re-evaluated, and the optimizer on their tensors at the end."""
         tr, c = self.tr, self.c
-        pool = st["pool"].data_ptr()
-        blk = B * K
         opt = tr._opt_state().ptr if mode == 2 else None
         validate = c.validate_inputs and c._int_input
         if mode == 2:
@@ -783,35 +378,13 @@ class JobStep:
         else:
             c._enqueue_params(stream)  # every parameter graph, once per step (parameters/parameter.py:180-188)
         D = c.plan.num_variables
-        for i in self.inputs:
-            if i in self.gathered:
+        for i in self.graph.inputs:
+            if i in self.graph.gathered:
                 continue  # (its consumers read the table)
             l = c.layers[i]
             l.launch_input(bd.xt if l.wants_float_input else bd.xt_i, D, bd.views[i], B, stream)
         for la in st["launches"]:
-            what = la[0]
-            if what == "nsum":
-                capi.call("ck_jobs_nsum", la[1][1].data_ptr(), la[2], pool, blk, stream)
-            elif what == "sum_fwd":
-                capi.call("ck_jobs_sum64_fwd", la[1][1].data_ptr(), la[2], pool, stream)
-            elif what == "mix_fwd":
-                capi.call("ck_jobs_mix_fwd", la[1][1].data_ptr(), la[2], pool, la[3], stream)
-            elif what == "root":
-                capi.call("ck_jobs_root", C.byref(st["root"][mode]), stream)
-            elif what == "sum_bwd":
-                capi.call("ck_jobs_sum64_bwd", la[1][mode].data_ptr(), la[2], pool, opt, la[3], stream)
-            elif what == "mix_bwd":
-                capi.call("ck_jobs_mix_bwd", la[1][mode].data_ptr(), la[2], pool, la[3], blk, opt, stream)
-            elif what == "mix_params":
-                capi.call("ck_jobs_mix_params", la[1][mode].data_ptr(), la[2], opt, stream)
-            elif what == "gauss_bwd":
-                capi.call("ck_jobs_gauss_bwd", la[2][mode].data_ptr(), la[3], pool, B, opt, stream)
-            elif what == "cat_bwd":
-                capi.call("ck_jobs_cat_bwd", la[2][mode].data_ptr(), la[3], pool, B, c.layers[la[1]].num_categories, opt, stream)
-            elif what == "input_bwd":
-                i = la[1]
-                capi.call("ck_jobs_nsum", la[2][1].data_ptr(), la[3], pool, blk, stream)
-                self._input_backward(i, bd, st, B, stream)
+            self._issue(la, bd, st, B, mode, stream)
         if mode == 2:  # the tensors of the layers no epilogue covers: the optimizer on their ranges of the flat buffers
             for i in self._uncovered():
                 for name in self._tensors_of(i):
@@ -833,7 +406,7 @@ class JobStep:
         """The backward of input layer i over its gathered (F, B, 64) gradient -- the launches of the layer-wise trainer."""
         tr, c = self.tr, self.c
         l = c.layers[i]
-        g = st["x0"] + self.input_g[i]["first"] * B * K * 4
+        g = st["x0"] + self.graph.input_g[i].first * B * K * 4
         dev = c.device
         if isinstance(l, HipCategoricalLayer):
             dT = st["dT"].get(i)

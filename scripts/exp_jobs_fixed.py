@@ -26,7 +26,7 @@ st = js.bind(B)
 pool = st["pool"].data_ptr()
 opt = tr._opt_state().ptr
 stream = torch.cuda.current_stream().cuda_stream
-la = max((l for l in st["launches"] if l[0] == "sum_bwd"), key=lambda l: l[2])
+la = max((l for l in st["launches"] if l.kind == "sum_bwd"), key=lambda l: l.n)
 dt = np.dtype(capi.SUM_JOB_DTYPE)
 
 
@@ -50,7 +50,7 @@ for units in (64, 512, 1024):
     for mode in (1, 2):
         for empty in (False, True):
             for split in (1, 2):
-                t = la[1][mode].cpu().numpy().view(dt).reshape(-1)[:units].copy()
+                t = la.tables[mode].cpu().numpy().view(dt).reshape(-1)[:units].copy()
                 part = tick = None
                 if split == 2:  # pairs of units become the two halves of one job
                     part = torch.zeros(units * 4096, dtype=torch.float32, device="cuda")

@@ -7,8 +7,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import ctypes as C  # noqa: E402
-
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -34,52 +32,33 @@ for _ in range(3):
     tr.step(x)
 torch.cuda.synchronize()
 st = js.bind(B)
+bd = tr.circuit._bind(B)
 MODE = int(os.environ.get("MODE", "2"))  # 2: the optimizer inside the epilogues (what `step` runs on one rank); 1: d theta only
-OPT = tr._opt_state().ptr if MODE == 2 else None
-pool = st["pool"].data_ptr()
-blk = B * 64
 stream = torch.cuda.current_stream().cuda_stream
+DTYPES = {"nsum": capi.NSUM_JOB_DTYPE, "input_bwd": capi.NSUM_JOB_DTYPE, "sum_fwd": capi.SUM_JOB_DTYPE, "sum_bwd": capi.SUM_JOB_DTYPE,
+          "mix_fwd": capi.MIX_JOB_DTYPE, "mix_bwd": capi.MIX_JOB_DTYPE, "gauss_bwd": capi.GAUSS_JOB_DTYPE, "cat_bwd": capi.CAT_JOB_DTYPE}
 total = 0.0
 print(f"{'launch':10s} {'units':>6s} {'jobs':>6s} {'split':>5s} {'n_in':>9s} {'n_g':>9s} {'us':>8s}")
-for la in st["launches"]:
-    what = la[0]
+for la in st["launches"]:  # (`Launch` records; `JobStep._issue` knows each kind's entry point -- an input_bwd launch includes its layer's backward)
+    what, n = la.kind, la.n
     if what == "mix_params":
         continue
+    fn = lambda la=la: js._issue(la, bd, st, B, MODE, stream)
     if what == "root":
-        fn = lambda: capi.call("ck_jobs_root", C.byref(st["root"][MODE]), stream)
         desc = (1, 1, 1, "", "")
     else:
-        tabs = la[2] if what in ("input_bwd", "gauss_bwd", "cat_bwd") else la[1]
-        n = la[3] if what in ("input_bwd", "gauss_bwd", "cat_bwd") else la[2]
-        tab = tabs.get(MODE, tabs[1])
-        raw = tab.cpu().numpy()
-        if what == "cat_bwd":
-            t = raw.view(np.dtype(capi.CAT_JOB_DTYPE)).reshape(-1)
-            desc = (n, n, 1, "", f"{t['n_g'].mean():.1f}/{t['n_g'].max()}")
-            fn = (lambda tab=tab, n=n, Cn=tr.circuit.layers[la[1]].num_categories: capi.call("ck_jobs_cat_bwd", tab.data_ptr(), n, pool, B, Cn, OPT, stream))
-        elif what == "gauss_bwd":
-            t = raw.view(np.dtype(capi.GAUSS_JOB_DTYPE)).reshape(-1)
-            desc = (n, n, 1, "", f"{t['n_g'].mean():.1f}/{t['n_g'].max()}")
-            fn = (lambda tab=tab, n=n: capi.call("ck_jobs_gauss_bwd", tab.data_ptr(), n, pool, B, OPT, stream))
+        t = la.tables.get(MODE, la.tables[1]).cpu().numpy().view(np.dtype(DTYPES[what])).reshape(-1)
+        n_g = f"{t['n_g'].mean():.1f}/{t['n_g'].max()}" if "n_g" in t.dtype.names else ""
+        if what in ("cat_bwd", "gauss_bwd"):
+            desc = (n, n, 1, "", n_g)
         elif what in ("nsum", "input_bwd"):
-            t = raw.view(np.dtype(capi.NSUM_JOB_DTYPE)).reshape(-1)
             desc = (n, n, 1, f"{t['n_in'].mean():.1f}/{t['n_in'].max()}", "")
-            fn = (lambda tab=tab, n=n: capi.call("ck_jobs_nsum", tab.data_ptr(), n, pool, blk, stream))
         elif what.startswith("sum"):
-            t = raw.view(np.dtype(capi.SUM_JOB_DTYPE)).reshape(-1)
-            ns = int(t["n_split"].max())
-            desc = (n, int((t["split"] == 0).sum()), ns, f"{t['n_in'].mean():.1f}/{t['n_in'].max()}", f"{t['n_g'].mean():.1f}/{t['n_g'].max()}")
-            name = "ck_jobs_sum64_fwd" if what == "sum_fwd" else "ck_jobs_sum64_bwd"
-            fn = ((lambda tab=tab, n=n: capi.call("ck_jobs_sum64_fwd", tab.data_ptr(), n, pool, stream)) if what == "sum_fwd" else
-                  (lambda tab=tab, n=n, wv=la[3]: capi.call("ck_jobs_sum64_bwd", tab.data_ptr(), n, pool, OPT, wv, stream)))
-            what = what + (f"/{la[3]}w" if what == "sum_bwd" else "")
+            desc = (n, int((t["split"] == 0).sum()), int(t["n_split"].max()), f"{t['n_in'].mean():.1f}/{t['n_in'].max()}", n_g)
+            what = what + (f"/{la.param}w" if what == "sum_bwd" else "")
         else:
-            t = raw.view(np.dtype(capi.MIX_JOB_DTYPE)).reshape(-1)
             ns = int(t["n_split"][0])
-            desc = (n, n // ns, ns, f"H{t['H'].mean():.1f}/{t['H'].max()} S{t['S'].max()}", f"{t['n_g'].mean():.1f}/{t['n_g'].max()}")
-            hm = la[3]
-            fn = ((lambda tab=tab, n=n, hm=hm: capi.call("ck_jobs_mix_fwd", tab.data_ptr(), n, pool, hm, stream)) if what == "mix_fwd" else
-                  (lambda tab=tab, n=n, hm=hm: capi.call("ck_jobs_mix_bwd", tab.data_ptr(), n, pool, hm, blk, OPT, stream)))
+            desc = (n, n // ns, ns, f"H{t['H'].mean():.1f}/{t['H'].max()} S{t['S'].max()}", n_g)
     for _ in range(3):
         fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
