@@ -465,6 +465,55 @@ def balanced_segments(num_roots: int, num_tiles: int, num_wg: int, waves: int = 
     return segs
 
 
+def leaf_bwd_unit_tables(group: SubtreeGroup, n_roots: int, var_of_leaf: np.ndarray, *, gin_block: np.ndarray | None = None,
+                         leaves_from_nodes: bool = True) -> list[tuple[np.ndarray, int]]:
+    """The unit tables of `ck_leaf_walk_bwd` over a leaf region of depth 2 or 4, top launch first: (table, level of P) pairs,
+    the tables (n_units, 16) int32 in the row layout of include/cirkit_hip.h (`ck_leaf_walk_bwd`).
+    `gin_block`: where the top launch finds the gradient of a root -- None: at the root's own fold; else `gin_block[root fold]`.
+    `var_of_leaf`: the variable of an input-layer fold, looked up at the leaf entry of `group.nodes` (`leaves_from_nodes`: the
+    input folds behind a dense layer) or at the level-0 fold itself."""
+    depth, kl = group.depth, 1 << group.depth
+    nodes = np.asarray(group.nodes).astype(np.int64)
+    off = [int(v) for v in group.node_off]
+
+    def lvl(l: int, t: int, j: int) -> int:  # fold of the j-th node of level l under root t (level 0: the region's input folds)
+        return int(nodes[off[l] + t * (kl >> l) + j])
+
+    tables = []
+    for top in range(depth, 0, -2):
+        per_root = kl >> top  # nodes of level `top` per root
+        tab = np.zeros((n_roots * per_root, 16), dtype=np.int32)
+        for t in range(n_roots):
+            for j in range(per_root):
+                r = tab[t * per_root + j]
+                if top == depth:
+                    r[0] = lvl(top, t, j) if gin_block is None else gin_block[lvl(top, t, j)]
+                else:
+                    r[0] = lvl(top + 1, t, j >> 1)
+                r[1] = lvl(top, t, j)
+                r[2], r[3] = lvl(top - 1, t, 2 * j), lvl(top - 1, t, 2 * j + 1)
+                for i in range(4):
+                    r[4 + i] = lvl(top - 2, t, 4 * j + i)
+                    if top == 2:
+                        r[8 + i] = var_of_leaf[int(nodes[group.leaf_off + t * kl + 4 * j + i]) if leaves_from_nodes else r[4 + i]]
+                r[12] = t
+        tables.append((tab, top))
+    return tables
+
+
+def interleave_8_apart(groups: list[list[int]]) -> list[int]:
+    """Workgroup order in which the members of a group run 8 workgroups apart (same XCD, about the same time: what they all
+    read is fetched once): 8 groups at a time, member m of the j-th group of a stretch at position 8 m + j of the stretch.  A
+    group shorter than the longest of its stretch leaves a hole, -1; what to do about holes, or a last stretch of fewer than 8
+    groups, is the caller's policy."""
+    order: list[int] = []
+    for i0 in range(0, len(groups), 8):
+        chunk = groups[i0 : i0 + 8]
+        for m in range(max(len(gr) for gr in chunk)):
+            order += [gr[m] if m < len(gr) else -1 for gr in chunk]
+    return order
+
+
 def tensordot_lists(layers, children, out_layers: set[int], busy: set[int] = frozenset()) -> tuple[dict[int, int], dict[int, int]]:
     """What the TensorDot launches of a squared circuit's partition function take over (`ck_tensordot_lse_fwd_h`,
     `ck_tensordot2_lse_fwd / _bwd`, cirkit_amd/csrc/ck_backward_c.hip; TorchTensorDotLayer, optimized.py:287-300, over

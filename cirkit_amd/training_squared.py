@@ -429,39 +429,21 @@ class _SignedCircuit:
 
     def _bind_leaf(self, st: dict, B: int, Bp: int, parent: dict) -> dict:
         """Descriptors and buffers of the leaf region's launches at batch size B."""
-        from .fusion import balanced_segments, leaf_segments
+        from .fusion import balanced_segments, leaf_bwd_unit_tables, leaf_segments
 
         c, g = self.c, self.leaf
         dev = c.device
         emb = c.layers[g.input_layer]
-        D, kl, tiles = g.depth, 1 << g.depth, Bp // 32
+        D, tiles = g.depth, Bp // 32
         n_wg = c._n_cu
         n_roots = c.layers[g.root].num_folds
-        nodes = np.asarray(g.nodes).astype(np.int64)
         noff = [int(v) for v in g.node_off]
-        var_of_leaf = emb.scope_idx[:, 0].astype(np.int64)
-
-        def lvl(l: int, t: int, j: int) -> int:  # fold of the j-th node of level l under root t (level 0: Embedding folds)
-            return int(nodes[noff[l] + t * (kl >> l) + j])
-
+        root_of = np.asarray(g.nodes).astype(np.int64)[noff[D] : noff[D] + n_roots]  # root t's fold of the root layer
         # where a root finds the gradient of its output: the block of the fold that reads it, as a block index of the gradient arena
         gin_block = np.asarray([(st["off"][parent[(g.root, f)][0]] + parent[(g.root, f)][1] * Bp * 32) // (Bp * 32) for f in range(n_roots)],
                                dtype=np.int32)
         launches = []  # top first: (unit table, level of P, work segments)
-        for top in range(D, 0, -2):
-            per_root = kl >> top
-            tab = np.zeros((n_roots * per_root, 16), dtype=np.int32)
-            for t in range(n_roots):
-                for j in range(per_root):
-                    r = tab[t * per_root + j]
-                    r[0] = gin_block[lvl(D, t, 0)] if top == D else lvl(top + 1, t, j >> 1)
-                    r[1] = lvl(top, t, j)
-                    r[2], r[3] = lvl(top - 1, t, 2 * j), lvl(top - 1, t, 2 * j + 1)
-                    for i in range(4):
-                        r[4 + i] = lvl(top - 2, t, 4 * j + i)
-                        if top == 2:
-                            r[8 + i] = var_of_leaf[r[4 + i]]
-                    r[12] = t
+        for tab, top in leaf_bwd_unit_tables(g, n_roots, emb.scope_idx[:, 0].astype(np.int64), gin_block=gin_block, leaves_from_nodes=False):
             work = balanced_segments(int(tab.shape[0]), tiles, n_wg, waves=8)
             launches.append((torch.from_numpy(tab).to(dev), top, torch.from_numpy(work).to(dev)))
         nodes_dev = torch.from_numpy(np.ascontiguousarray(g.nodes)).to(dev)
@@ -479,11 +461,13 @@ class _SignedCircuit:
             "work": torch.from_numpy(leaf_segments(n_roots, tiles, n_wg)).to(dev), "n_wg": n_wg,
             "root_tab": c._leaf_root_table(nodes_dev, node_off_c, g.leaf_off, scope, D, n_roots),
             "x64": torch.zeros((B, max(1, c.plan.num_variables)), dtype=torch.int64, device=dev),
-            "gin_fold": torch.from_numpy(gin_block[[lvl(D, t, 0) for t in range(n_roots)]].copy()).to(dev),
+            "gin_fold": torch.from_numpy(gin_block[root_of].copy()).to(dev),
             "pairs": 1 if c._leaves_in_adjacent_pairs(g) else 0,
         }
 
     def bind(self, B: int) -> dict:
+        from .fusion import interleave_8_apart
+
         st = self._bound.get(B)
         if st is not None:
             return st
@@ -539,12 +523,9 @@ class _SignedCircuit:
                 by_block: dict[int, list[int]] = {}
                 for f in range(F):
                     by_block.setdefault(int(gfold[f]), []).append(f)
-                groups, order = list(by_block.values()), []
-                for i0 in range(0, len(groups), 8):
-                    chunk = groups[i0 : i0 + 8]
-                    for m in range(max(len(gr) for gr in chunk)):
-                        order += [gr[m] if m < len(gr) else -1 for gr in chunk]
-                if -1 in order or len(chunk) != 8:  # (ragged groups: the plain order)
+                groups = list(by_block.values())
+                order = interleave_8_apart(groups)
+                if -1 in order or len(groups) % 8 != 0:  # (ragged groups, a short last stretch: the plain order)
                     order = list(range(F))
                 assert sorted(order) == list(range(F))
                 st["gfold"][i] = (torch.from_numpy(gfold).to(dev), gather.pop(), torch.from_numpy(np.asarray(order, dtype=np.int32)).to(dev))

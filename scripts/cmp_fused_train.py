@@ -34,7 +34,7 @@ for k in plan.tensors:
     print(f"{k:12s} shape {tuple(ga.shape)!s:18s} max|g| {sc:.3e}  max diff {err:.3e}  rel {err / max(sc, 1e-30):.2e}  "
           f"norm a {float(ga.norm()):.6e} b {float(gb.norm()):.6e}")
 print("worst relative difference", worst)
-redo = b.circuit._bind(B).keep[b._fz["group"].root][1]
+redo = b.circuit._bind(B).keep[b._fused_step.tables.group.root][1]
 print("flagged tiles", int(redo.sum()))
 for name, tr in (("layer-wise", a), ("fused", b)):
     for _ in range(3):

@@ -7,7 +7,8 @@ bound and its program recorded; no step runs.  The fixture notes
 
 * the calls: every entry point issued through `cirkit_amd._capi.call` while the program is recorded, with its count arguments
   (the int / int64 arguments of its signature: units, waves, hmax, block size, B, C; of the root launch's struct R, B, mode,
-  n_wg, S) -- never an address;
+  n_wg, S; of a leaf backward launch's struct n_seg, n_wg, B, C, D, leaf, waves, gin_rowmajor, is_signed; whether a `TableOpt` was
+  passed: scripts/record_train_calls.py) -- never an address;
 * the tables: per job launch a sha256 over its device table read back to the host -- every field that is not a pointer byte for
   byte, every pointer (`<u8`) field reduced to zero / non-zero -- plus the pool's length and the number of extra blocks.
 
@@ -69,6 +70,11 @@ def tapped(calls: list):
             elif isinstance(getattr(a, "_obj", None), _capi.RootLaunch):
                 ra = a._obj
                 row += [int(ra.R), int(ra.B), int(ra.mode), int(ra.n_wg), int(ra.S)]
+            elif isinstance(getattr(a, "_obj", None), _capi.LeafBwdLaunch):
+                d = a._obj
+                row += [int(getattr(d, f)) for f in ("n_seg", "n_wg", "B", "C", "D", "leaf", "waves", "gin_rowmajor", "is_signed")]
+            elif ty == C.POINTER(_capi.TableOpt):  # (ck_table_dense_bwd: with or without the optimizer epilogue)
+                row.append(0 if a is None else 1)
         calls.append(row)
         return inner(name, *args)
 
