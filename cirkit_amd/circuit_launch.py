@@ -30,6 +30,26 @@ _LAUNCH_OF_ROLE = {"tensordot": "_launch_tensordot", "table_dense": "_launch_tab
                    "leftover": "_launch_cp", "cp": "_launch_cp", "region": "_launch_region", "input_prod": "_launch_input_prod"}
 
 
+def launch_tensordot(layers, i: int, bd: _Binding, td_had: dict[int, int], td_pair: dict[int, int], cplx: bool, stream: int) -> None:
+    """TensorDot layer i with what `fusion.tensordot_lists` let it absorb -- `td_pair`: the TensorDot layer beneath it (the W /
+    conj W pair in one launch), `td_had`: the Hadamard layer the first of them reads as a list of its children --:
+    `ck_tensordot_lse_fwd_h` / `ck_tensordot2_lse_fwd`."""
+    l = layers[i]
+    a = td_pair.get(i)
+    first = i if a is None else a
+    h = td_had.get(first)
+    ro, H = (bd.row_off[first], 1) if h is None else (bd.row_off[h], layers[h].arity)
+    cv = 1 if cplx else 0
+    if a is None:
+        capi.call("ck_tensordot_lse_fwd_h", bd.arena.data_ptr(), ro.data_ptr(), H, l._w.data_ptr(), bd.views[i].data_ptr(), l.num_folds,
+                  bd.B, l._num_contract_units, l._num_batch_units, l.num_output_units // l._num_batch_units, cv, stream)
+    else:
+        la = layers[a]
+        capi.call("ck_tensordot2_lse_fwd", bd.arena.data_ptr(), ro.data_ptr(), H, la._w.data_ptr(), bd.views[a].data_ptr(),
+                  l._w.data_ptr(), bd.views[i].data_ptr(), l.num_folds, bd.B, la._num_contract_units, la._num_batch_units,
+                  la.num_output_units // la._num_batch_units, l.num_output_units // l._num_batch_units, cv, stream)
+
+
 class _LaunchMixin:
     def _launch_layer(self, i: int, bd: _Binding, stream: int, *, inputs: bool = True) -> None:
         """The launch of layer i by its role (`fusion.launch_roles`; the tail and the roles without a launch are the caller's).
@@ -49,21 +69,8 @@ class _LaunchMixin:
             l.launch_input(bd.xt if l.wants_float_input else bd.xt_i, self.plan.num_variables, bd.views[i], bd.B, stream)
 
     def _launch_tensordot(self, i: int, bd: _Binding, stream: int) -> None:
-        """TensorDot layer i with what it absorbed (`_td_had`, `_td_pair`): `ck_tensordot_lse_fwd_h` / `ck_tensordot2_lse_fwd`."""
-        l = self.layers[i]
-        a = self._td_pair.get(i)
-        first = i if a is None else a
-        h = self._td_had.get(first)
-        ro, H = (bd.row_off[first], 1) if h is None else (bd.row_off[h], self.layers[h].arity)
-        cv = 1 if self._complex else 0
-        if a is None:
-            capi.call("ck_tensordot_lse_fwd_h", bd.arena.data_ptr(), ro.data_ptr(), H, l._w.data_ptr(), bd.views[i].data_ptr(), l.num_folds,
-                      bd.B, l._num_contract_units, l._num_batch_units, l.num_output_units // l._num_batch_units, cv, stream)
-        else:
-            la = self.layers[a]
-            capi.call("ck_tensordot2_lse_fwd", bd.arena.data_ptr(), ro.data_ptr(), H, la._w.data_ptr(), bd.views[a].data_ptr(),
-                      l._w.data_ptr(), bd.views[i].data_ptr(), l.num_folds, bd.B, la._num_contract_units, la._num_batch_units,
-                      la.num_output_units // la._num_batch_units, l.num_output_units // l._num_batch_units, cv, stream)
+        """TensorDot layer i with what it absorbed (`_td_had`, `_td_pair`)."""
+        launch_tensordot(self.layers, i, bd, self._td_had, self._td_pair, self._complex, stream)
 
     def _launch_emb_gather(self, i: int, bd: _Binding, stream: int) -> None:
         """`ck_sum_clse_gather_fwd`: a complex CP-T / dense layer reading its Embedding children from the table."""

@@ -17,6 +17,7 @@ from . import _capi as capi
 from .circuit import HipCircuit
 from .fusion import SubtreeGroup, balanced_segments, interleave_8_apart, leaf_bwd_unit_tables
 from .layers import HipCategoricalLayer, HipCPTLayer, HipSumLayer
+from .train_leaf import leaf_backward
 
 # one fold of `ck_tail_bwd` and one job of `ck_param_softmax_bwd_batch` (include/cirkit_hip.h)
 TAIL_FOLD_DTYPE = np.dtype([("w", "<u8"), ("gout", "<u8"), ("dw_part", "<u8"), ("child", "<u8", 4), ("gchild", "<u8", 4), ("H", "<i4"), ("Ko", "<i4")])
@@ -303,39 +304,20 @@ class FusedStep:
                 self.tr._bwd_sum_layer(i, bd, st, B, stream)
 
     def _leaf_levels(self, B: int, bd, st, fb: FusedBinding, stream: int) -> torch.Tensor:
-        """The leaf region, two levels per launch, top first, then the redo launch; returns the gradient tiles of level 1."""
+        """The leaf region (`train_leaf.leaf_backward`); returns the gradient tiles of level 1."""
         tr, c, g = self.tr, self.circuit, self.tables.group
         keep, redo = bd.keep[g.root]
         cat = c.layers[g.input_layer]
-        table = c._group_dev[g.root][1]
-        gin = st.gviews[g.root]
-        for k, (tab, top) in enumerate(self.tables.launches):
-            lp, lq = g.levels[top - 1], g.levels[top - 2]
-            d = capi.LeafBwdLaunch()
-            d.unit_tab, d.work = tab.data_ptr(), fb.work[k].data_ptr()
-            d.n_seg, d.n_wg, d.B, d.waves = int(fb.work[k].shape[0]), c._n_cu, B, self.waves
-            d.C, d.D, d.leaf = cat.num_categories, tr.plan.num_variables, 1 if top == 2 else 0
-            d.gin, d.gin_rowmajor = gin.data_ptr(), 1 if k == 0 else 0
-            d.y_p = keep[top - 1].data_ptr()  # (the level in between, top - 1, is recomputed by the launch)
-            if top == 2:
-                d.table, d.x_rows = table.data_ptr(), bd.x_last.data_ptr()
-            else:
-                d.y_c = keep[top - 3].data_ptr()
-            d.w_p, d.w_q = c.layers[lp]._w.data_ptr(), c.layers[lq]._w.data_ptr()
-            d.dw_p, d.dw_q = st.dws[lp].data_ptr(), st.dws[lq].data_ptr()
-            d.gout = fb.G[k].data_ptr()
-            d.redo = redo.data_ptr()
-            capi.call("ck_leaf_walk_bwd", C.byref(d), stream)
-            gin = fb.G[k]
-        # (root, tile) units whose forward walk left the linear range: in log space, by a launch in which every other wave exits
-        depth = g.depth
-        capi.call("ck_leaf_walk_bwd_redo", table.data_ptr(), c._group_dev[g.root][3].data_ptr(), bd.x_last.data_ptr(),
-                  B, cat.num_categories, tr.plan.num_variables, c._group_dev[g.root][0].data_ptr(),
-                  (C.c_int32 * (depth + 1))(*g.node_off), g.leaf_off, cat._scope(tr.device).data_ptr(), depth,
-                  (C.c_void_p * depth)(*[c.layers[j]._w.data_ptr() for j in g.levels]),
-                  (C.c_void_p * depth)(*[st.dws[j].data_ptr() for j in g.levels]),
-                  st.gviews[g.root].data_ptr(), gin.data_ptr(), redo.data_ptr(), c.layers[g.root].num_folds, None, 0, stream)
-        return gin
+        nodes, table, _, scale = c._group_dev[g.root][:4]
+        leaf_backward(g, unit_tabs=[tab.data_ptr() for tab, _ in self.tables.launches], tops=[top for _, top in self.tables.launches],
+                      works=[w.data_ptr() for w in fb.work], n_segs=[int(w.shape[0]) for w in fb.work],
+                      gouts=[G.data_ptr() for G in fb.G], w=[c.layers[j]._w.data_ptr() for j in g.levels],
+                      dw=[st.dws[j].data_ptr() for j in g.levels], keep=[None if t is None else t.data_ptr() for t in keep],
+                      redo=redo.data_ptr(), table=table.data_ptr(), scale=scale.data_ptr(), x_rows=bd.x_last.data_ptr(),
+                      nodes=nodes.data_ptr(), scope=cat._scope(tr.device).data_ptr(), B=B, Cn=cat.num_categories,
+                      D=tr.plan.num_variables, n_roots=c.layers[g.root].num_folds, n_wg=c._n_cu, waves=self.waves,
+                      gin=st.gviews[g.root].data_ptr(), gin_rowmajor=1, is_signed=0, gin_fold=None, stream=stream)
+        return fb.G[-1]
 
     def _scatter_and_table(self, B: int, bd, st, gin: torch.Tensor, state, stream: int) -> None:
         tr, c, fz = self.tr, self.circuit, self.tables

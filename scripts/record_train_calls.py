@@ -1,7 +1,8 @@
 """Record what the fused, the layer-wise and the signed squared training steps bind and issue, case by case, into
-tests/golden/train_step_calls.json (MI355X).
+tests/golden/train_step_calls.json, and what `HipSquaredTrainer` binds and issues on its other paths into
+tests/golden/squared_step_calls.json (MI355X).
 
-    python scripts/record_train_calls.py [--out tests/golden/train_step_calls.json]
+    python scripts/record_train_calls.py [--section all|train|squared] [--out ...] [--out-squared ...]
 
 Per case the fixture notes
 
@@ -13,6 +14,13 @@ Per case the fixture notes
   `fold_order`, the work segments, the tail fold table (96-byte rows) and its levels, both softmax-backward job tables (88-byte
   rows), the four tables of every shared-children entry -- every pointer (`<u8`) field reduced to zero / non-zero;
 * shapes (`G`, `dws`), `flags` and the sorted `need_zero`.
+
+The `squared` section (SQUARED_CASES) notes per case and batch size the calls of one `loss_and_grads` (the first case: also of
+one `step` and of one `loss_and_grads(global_batch=2 B)`), each the first -- eager -- call of its (part, B, global batch,
+optimizer) key on a fresh trainer, and for c and for Z the weight-pool layout (per layer: offset, shape, `direct`), the per-layer
+scratch shapes and digests of the `ro` tables of the Hadamard layers that have a backward launch of their own; for a signed c digests of `ro`, `gout_off`, the gather tables and
+`gfold` / order.  `squared_state` reads them from the records of cirkit_amd/train_reverse.py and cirkit_amd/train_signed.py or
+from the dicts and tuples of a commit from before them.
 
 `trainer_state` is the one place that knows where a `HipTrainer` keeps this: the records of cirkit_amd/train_fused.py and the
 binding dataclass of cirkit_amd/training.py, or the string-keyed dicts of a commit from before them, so that the script records
@@ -36,6 +44,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURE = os.path.join(GOLDEN, "train_step_calls.json")
+SQUARED_FIXTURE = os.path.join(GOLDEN, "squared_step_calls.json")
 
 _spec = importlib.util.spec_from_file_location("record_job_step_calls", os.path.join(ROOT, "scripts", "record_job_step_calls.py"))
 rjs = importlib.util.module_from_spec(_spec)
@@ -62,6 +71,15 @@ FUSED_CASES = {
 LAYERWISE_CASES = ("cfg1_rbt8", "quadgraph_6x6_k4", "pd_gauss_6x6_k4", "quadgraph_6x6_tucker_k4", "quadtree_4x4_kron_k3")
 LAYERWISE_BATCHES = (5, 64)
 SIGNED_ROWS = 300
+# squared: case -> (plan of c, plan of Z or None: built by `squared_partition_plan`, `signed`, seed of the tensors, CK_SLSE_LEAF,
+# batch sizes, whether a `step` and a `loss_and_grads` at twice the global batch are recorded too)
+SQUARED_CASES = {
+    "complex_emb_k4": ("sos_4x4_c_k4", "sos_4x4_z_k4", False, None, None, (5, 64), True),  # Embedding backward in two launches
+    "complex_emb_k32": ("cfg5_sos_c_k32", "cfg5_sos_z_k32", False, None, None, (33,), False),  # `ck_embedding_bwd` in one
+    "real_categorical": ("sq_cat_qt4x4_k5", None, None, 6, None, (5, 64), False),
+    "real_gaussian": ("sq_gauss_qt4x4_k4", None, None, 8, None, (5, 64), False),
+    "signed_layers": ("cfg5_sos_c_k32", "cfg5_sos_z_k32", True, None, "0", (33,), False),  # no leaf region
+}
 
 
 def digest(t, dtype=None) -> str:
@@ -136,6 +154,40 @@ def make_signed(device):
     return tr
 
 
+class _env:
+    """One environment variable set (None: left alone) for the length of a block."""
+
+    def __init__(self, name: str, value: str | None) -> None:
+        self.name, self.value = name, value
+
+    def __enter__(self):
+        self.old = os.environ.get(self.name)
+        if self.value is not None:
+            os.environ[self.name] = self.value
+
+    def __exit__(self, *exc):
+        if self.value is not None:
+            if self.old is None:
+                del os.environ[self.name]
+            else:
+                os.environ[self.name] = self.old
+
+
+def make_squared(case: str, device):
+    from cirkit_amd.initializers import init_plan_tensors
+    from cirkit_amd.training_squared import HipSquaredTrainer
+
+    src_c, src_z, signed, seed, leaf, _, _ = SQUARED_CASES[case]
+    plan_c = _plan(src_c)
+    tensors = init_plan_tensors(plan_c) if seed is None else init_plan_tensors(plan_c, seed=seed)
+    # (the counter-based generator emits a few exact zeros: log 0)
+    tensors = {k: np.where(v == 0, np.float32(1e-2), v).astype(np.float32) for k, v in tensors.items()}
+    with _env("CK_SLSE_LEAF", leaf):  # (read once, at construction)
+        tr = HipSquaredTrainer(plan_c, tensors, plan_z=None if src_z is None else _plan(src_z), device=device, signed=signed)
+    assert (tr._signed is not None) == bool(signed) and (tr._signed is None or tr._signed.leaf is None), case
+    return tr
+
+
 def _get(o, name):
     return o[name] if isinstance(o, dict) else getattr(o, name)
 
@@ -162,6 +214,44 @@ def trainer_state(tr, B: int | None) -> dict:
             jobs = {k: (None if getattr(fb, k) is None else getattr(fb, k).table) for k in ("sm_jobs", "sm_jobs_opt")}
         out.update(work=_get(fb, "work"), G=_get(fb, "G"), **jobs)
         out["tail"] = None if tail is None else (_get(tail, "folds"), _get(tail, "levels"))
+    return out
+
+
+def _fields(v, names: tuple) -> tuple:
+    """A positional tuple as it is, a record by the names of its fields."""
+    return tuple(v) if isinstance(v, tuple) else tuple(getattr(v, n) for n in names)
+
+
+def squared_state(tr, B: int) -> dict:
+    """What a `HipSquaredTrainer` holds at batch size B under one set of names: "c" / "z": the state of a layer-wise reverse list
+    (`pool`, per layer `scratch`: {name: tensor or flag}); "signed": the binding of the signed-log circuit (`ro`, `gout_off`,
+    `tabs`: (folds, variables, Embedding layer), `gfold`: (fold table, reader layer, order), `launches`: (unit table, top, work))."""
+    import dataclasses
+
+    def reverse(bwd, rows):
+        st = (getattr(bwd, "bind", None) or bwd._bind)(rows)
+        scratch = _get(st, "scratch")
+        per_layer = []
+        for i in range(len(bwd.c.layers)):
+            sc = scratch[i]
+            per_layer.append(dict(sc) if isinstance(sc, dict) else
+                             {f.name: getattr(sc, f.name) for f in dataclasses.fields(sc) if getattr(sc, f.name) is not None})
+        # (a layer whose reader's launch does its part -- an absorbed Hadamard layer, the first half of a TensorDot pair -- has no
+        #  scratch of its own beyond its slice of the pool)
+        return {"pool": _get(st, "pool"), "scratch": per_layer, "skip": set(bwd._skip)}
+
+    out: dict = {"z": reverse(tr._bwd_z, 1)}
+    if tr._signed is None:
+        out["c"] = reverse(tr._bwd_c, B)
+        return out
+    st = tr._signed.bind(B)
+    leaf = _get(st, "leaf") if (not isinstance(st, dict) or "leaf" in st) else None
+    out["signed"] = {
+        "ro": dict(_get(st, "ro")), "gout_off": dict(_get(st, "gout_off")),
+        "tabs": {i: _fields(v, ("folds", "variables", "emb")) for i, v in _get(st, "tabs").items()},
+        "gfold": {i: _fields(v, ("fold", "reader", "order")) for i, v in _get(st, "gfold").items()},
+        "launches": None if leaf is None else [_fields(v, ("unit_tab", "top", "work")) for v in _get(leaf, "launches")],
+    }
     return out
 
 
@@ -223,12 +313,78 @@ def record_signed(tr) -> dict:
     with tapped(calls):
         tr.loss_and_grads(x)
     torch.cuda.synchronize()
-    st = tr._signed.bind(SIGNED_ROWS)
+    st = squared_state(tr, SIGNED_ROWS)["signed"]
     return {
-        "calls": calls, "unit_tabs": [[int(top), digest(tab)] for tab, top, _ in st["leaf"]["launches"]],
-        "work": [digest(work) for _, _, work in st["leaf"]["launches"]],
+        "calls": calls, "unit_tabs": [[int(top), digest(tab)] for tab, top, _ in st["launches"]],
+        "work": [digest(work) for _, _, work in st["launches"]],
         "gfold": sorted([int(i), digest(gfold), digest(order)] for i, (gfold, _, order) in st["gfold"].items()),
     }
+
+
+def _squared_input(tr, B: int) -> torch.Tensor:
+    from cirkit_amd.layers import HipEmbeddingLayer, HipGaussianLayer
+
+    D, g = tr.plan_c.num_variables, torch.Generator().manual_seed(B)
+    if any(isinstance(l, HipGaussianLayer) for l in tr.c.layers):
+        return torch.rand((B, D), generator=g).to(tr.device)
+    states = min([l.num_states for l in tr.c.layers if isinstance(l, HipEmbeddingLayer)] or [2])
+    return torch.randint(0, states, (B, D), generator=g).to(tr.device)
+
+
+def _reverse_record(st: dict) -> dict:
+    """Pool layout, scratch shapes and `ro` digests of one layer-wise reverse list."""
+    pool = st["pool"]
+    layout, shapes, ro = [], [], []
+    for i, sc in enumerate(st["scratch"]):
+        if "direct" in sc and "dw" in sc:  # (a sum / TensorDot layer: a slice of the pool, or the tensor's own gradient)
+            off = None if sc["direct"] else (sc["dw"].data_ptr() - pool.data_ptr()) // 4
+            layout.append([i, off, list(sc["dw"].shape), bool(sc["direct"])])
+        if i in st["skip"]:
+            continue
+        shapes.append([i, sorted([k, list(v.shape)] for k, v in sc.items() if isinstance(v, torch.Tensor))])
+        if "ro" in sc:
+            ro.append([i, digest(sc["ro"])])
+    return {"pool": int(pool.numel()), "layout": layout, "scratch": shapes, "ro": ro}
+
+
+def record_squared(tr, case: str, B: int) -> dict:
+    """The first call of each (part, B, global batch, optimizer) key at batch size B, then the state they were issued over."""
+    x = _squared_input(tr, B)
+    calls: dict = {"loss_and_grads": []}
+    with tapped(calls["loss_and_grads"]):
+        tr.loss_and_grads(x)
+    if SQUARED_CASES[case][6]:
+        calls["step"], calls["loss_and_grads_2B"] = [], []
+        with tapped(calls["step"]):
+            tr.step(x)
+        with tapped(calls["loss_and_grads_2B"]):
+            tr.loss_and_grads(x, global_batch=2 * B)
+    torch.cuda.synchronize()
+    st = squared_state(tr, B)
+    out = {"calls": calls, "z": _reverse_record(st["z"])}
+    if "c" in st:
+        out["c"] = _reverse_record(st["c"])
+    else:
+        sg = st["signed"]
+        assert sg["launches"] is None
+        out["signed"] = {
+            "ro": sorted([int(i), digest(t)] for i, t in sg["ro"].items()),
+            "gout_off": sorted([int(i), digest(t)] for i, t in sg["gout_off"].items()),
+            "tabs": sorted([int(i), digest(folds), digest(variables), int(emb)] for i, (folds, variables, emb) in sg["tabs"].items()),
+            "gfold": sorted([int(i), digest(gfold), int(reader), digest(order)] for i, (gfold, reader, order) in sg["gfold"].items()),
+        }
+    return out
+
+
+def record_all_squared(device) -> dict:
+    cases, n_cu = {}, None
+    for case, cfg in SQUARED_CASES.items():
+        tr = make_squared(case, device)
+        n_cu = int(tr.c._n_cu)
+        for B in cfg[5]:
+            cases[f"{case}@{B}"] = record_squared(tr, case, B)
+        del tr
+    return {"n_cu": n_cu, "squared": cases}
 
 
 def record_all(device) -> dict:
@@ -249,20 +405,33 @@ def record_all(device) -> dict:
     return {"n_cu": n_cu, "unit_tabs": unit_tabs, "fused": fused, "layerwise": layerwise, "signed": record_signed(make_signed(device))}
 
 
+def _write(doc: dict, path: str) -> None:
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(doc, f, sort_keys=True, separators=(",", ":"))
+        f.write("\n")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--section", choices=("all", "train", "squared"), default="all")
     ap.add_argument("--out", default=FIXTURE)
+    ap.add_argument("--out-squared", default=SQUARED_FIXTURE)
     args = ap.parse_args()
+    if args.section in ("all", "squared"):
+        doc = record_all_squared(torch.device("cuda:0"))
+        for cid, c in doc["squared"].items():
+            print(f"squared {cid}: {sum(len(v) for v in c['calls'].values())} calls", flush=True)
+        _write(doc, args.out_squared)
+    if args.section == "squared":
+        return
     doc = record_all(torch.device("cuda:0"))
     for kind in ("fused", "layerwise"):
         for cid, c in doc[kind].items():
             calls = c["calls"]
             print(f"{kind} {cid}: {sum(len(v) for v in calls.values()) if isinstance(calls, dict) else len(calls)} calls", flush=True)
     print(f"signed: {len(doc['signed']['calls'])} calls", flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w", encoding="utf-8") as f:
-        json.dump(doc, f, sort_keys=True, separators=(",", ":"))
-        f.write("\n")
+    _write(doc, args.out)
 
 
 if __name__ == "__main__":

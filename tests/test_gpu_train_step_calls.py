@@ -2,7 +2,12 @@
 cirkit_amd/training.py, cirkit_amd/training_squared.py) against tests/golden/train_step_calls.json, recorded on an MI355X by
 scripts/record_train_calls.py from the code before the fused form moved out of `HipTrainer`: per case the entry points issued
 with their count arguments (those of every `LeafBwdLaunch`, whether `ck_table_dense_bwd` got a `TableOpt`), a sha256 of every
-host-built table (pointer fields reduced to zero / non-zero), shapes, flags.  No more runs than the recorder ran."""
+host-built table (pointer fields reduced to zero / non-zero), shapes, flags.  No more runs than the recorder ran.
+
+tests/golden/squared_step_calls.json holds the same for the other paths of `HipSquaredTrainer` (cirkit_amd/train_reverse.py,
+cirkit_amd/train_signed.py), recorded from the code before the trainer was split: the complex and the real layer-wise lists with
+both Embedding branches, Categorical and Gaussian inputs, the signed circuit without its leaf region, the `step` form and a second
+global batch; beside the calls the weight-pool layout, the scratch shapes and the table digests of c and of Z."""
 import importlib.util
 import json
 import os
@@ -18,6 +23,8 @@ _spec.loader.exec_module(rtc)
 
 with open(os.path.join(GOLDEN, "train_step_calls.json"), encoding="utf-8") as _f:
     FIXTURE = json.load(_f)
+with open(os.path.join(GOLDEN, "squared_step_calls.json"), encoding="utf-8") as _f:
+    SQUARED = json.load(_f)
 
 
 def _same_device(tr_n_cu) -> None:
@@ -37,6 +44,7 @@ def test_fixture_holds_every_case():
     assert set(FIXTURE["unit_tabs"]) == set(rtc.FUSED_CASES)
     assert set(FIXTURE["layerwise"]) == {f"{c}@{B}" for c in rtc.LAYERWISE_CASES for B in rtc.LAYERWISE_BATCHES}
     assert FIXTURE["signed"]["calls"]
+    assert set(SQUARED["squared"]) == {f"{c}@{B}" for c, cfg in rtc.SQUARED_CASES.items() for B in cfg[5]}
 
 
 @pytest.mark.gpu
@@ -62,4 +70,14 @@ def test_signed_squared_step_issues_the_recorded_calls_over_the_recorded_tables(
     tr = rtc.make_signed(hip_device)
     _same_device(tr._signed.c._n_cu)
     _compare(rtc.record_signed(tr), FIXTURE["signed"], "signed")
+    torch.cuda.synchronize()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", list(rtc.SQUARED_CASES))
+def test_squared_trainer_issues_the_recorded_calls_over_the_recorded_state(hip_device, case):
+    """(No work segments enter these lists: they hold on any number of CUs.)"""
+    tr = rtc.make_squared(case, hip_device)
+    for B in rtc.SQUARED_CASES[case][5]:
+        _compare(rtc.record_squared(tr, case, B), SQUARED["squared"][f"{case}@{B}"], f"{case}@{B}")
     torch.cuda.synchronize()

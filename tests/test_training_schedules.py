@@ -53,8 +53,8 @@ def _hold_evicted(tr, B: int, held: list, arenas: dict) -> None:
     if sc is not None and B not in sc._bound and len(sc._bound) >= 4:
         B0 = next(iter(sc._bound))
         st = sc._bound[B0]
-        held += [st["xt"]] + ([st["leaf"]["x64"]] if "leaf" in st else [])
-        arenas[("signed", B0)] = st["arena"]
+        held += [st.xt] + ([st.leaf.x64] if st.leaf is not None else [])
+        arenas[("signed", B0)] = st.arena
 
 
 def _same_arena_back(tr, B: int, arenas: dict, monkeypatch) -> None:

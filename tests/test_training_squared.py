@@ -149,7 +149,7 @@ def test_leaf_region_on_linear_tiles_agrees_with_the_layer_launches(hip_device, 
         for k in tensors:
             d, n = float(np.linalg.norm((ga[k] - gb[k]).astype(np.float64))), float(np.linalg.norm(gb[k].astype(np.float64)))
             assert d <= 2e-2 * n + 1e-12, (it, k, d, n)
-    assert int(a._signed.bind(rows)["leaf"]["redo"].sum()) == 0  # (no tile left the linear range)
+    assert int(a._signed.bind(rows).leaf.redo.sum()) == 0  # (no tile left the linear range)
 
 
 @pytest.mark.gpu
@@ -180,7 +180,7 @@ def test_leaf_region_tiles_that_leave_the_linear_range(hip_device, monkeypatch):
     stream = torch.cuda.current_stream().cuda_stream
     a._signed.stage(x, stream)
     a._signed.forward(B, stream)
-    marks = a._signed.bind(B)["leaf"]["redo"]
+    marks = a._signed.bind(B).leaf.redo
     assert int(marks.sum()) > 0  # (the case this test is about)
     a._flat_grad.zero_()
     a._signed.backward(B, -2.0 / B, stream)
