@@ -342,6 +342,11 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_loo_leaf_categorical": [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _l, _p, _p],
     "ck_loo_leaf_gaussian": [_p, _p, _i, _p, _p, _p, _p, _p, _l, _p, _p],
     "ck_loo_log_probs": [_p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _l, _p, _p],
+    "ck_ar_expand": [_p, _i, _l, _i, _p, _p, _i, _p, _l, _l, _p, _p, _p, _p, _p, _p],
+    "ck_ar_leaf_categorical": [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _l, _p, _p],
+    "ck_ar_leaf_gaussian": [_p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p],
+    "ck_ar_log_probs": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p],
+    "ck_ar_quantise": [_p, _p, _p, _l, _i, _i, _p, _p],
     "ck_stats_edge_sum": [_i, _i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p, _i, _p, _l, _p, _p, _l, _p],
     "ck_stats_leaf_categorical": [_p, _p, _l, _i, _i, _p, _i, _i, _p, _p, _i, _p, _l, _p, _p],
     "ck_stats_leaf_gaussian": [_p, _p, _p, _l, _i, _p, _i, _p, _p, _i, _p, _l, _p, _p],

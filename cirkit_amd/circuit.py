@@ -1050,6 +1050,53 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
 
         return conditional_log_probs(self, x, missing_vars, rows_per_chunk=rows_per_chunk)
 
+    def autoregressive_conditionals(self, x: torch.Tensor, order=None, *, positions=None, rows_per_chunk: int | None = None):
+        """The chain-rule conditionals of every row of ``x`` (B, D) along an order of the variables: ``p[b, j, c] =
+        p(X_{order[i]} = c | x_{order[:i]} of row b)`` for ``i = positions[j]``, for any circuit `sample` accepts (the same
+        refusals).  The reference has no such query.
+
+        `order`: a permutation of the variables in the scope of an input layer (None: ascending).  `positions`: a subset of
+        the steps ``0 .. len(order) - 1`` as ids, a range or a bool mask (the forms of ``query_vars``), taken ascending;
+        None: every step; P is their number.  Step i of row b is a `leave_one_out` query on the EXPANDED row (b, i) -- row b
+        with every variable ``order[j]``, ``j >= i``, set to the sentinel (-1 / NaN) -- written chunk by chunk on the device:
+        nothing of size ``B P x D`` exists outside a chunk.  Entries of ``x`` at steps ``>= i`` do not influence ``[b, j]``;
+        sentinels already in ``x`` stay missing at every step.  ``ValueError`` before anything is copied, prepared or
+        launched: an order with duplicates, uncovered, out-of-range or left-out variables, a step outside the order.
+
+        Returns ``(B, P, C)`` fp32 on this device, as `leave_one_out`: ``C`` the largest state count, entries past a
+        variable's own count exactly 0; an all-Gaussian order gives ``(B, P, 2)`` conditional mean and variance; a mixed
+        order is refused (``NotImplementedError``).  A prefix without mass is NaN.  An out-of-range category ANYWHERE in a
+        row is reported by `check_inputs` and makes that row alone NaN, at every step.  `rows_per_chunk`: EXPANDED rows per
+        pass (None: the arenas stay <= 2 GiB); results do not depend on it, bit for bit, and equal those `leave_one_out`
+        gives for the host-expanded batch.  No host synchronisation (cirkit_amd/autoregressive.py)."""
+        from .autoregressive import autoregressive_conditionals
+
+        return autoregressive_conditionals(self, x, order, positions=positions, rows_per_chunk=rows_per_chunk)
+
+    def autoregressive_log_probs(self, x: torch.Tensor, order=None, *, positions=None, rows_per_chunk: int | None = None):
+        """``(B, P)`` fp32: ``log p(x_{order[i]} | x_{order[:i]})`` for ``i = positions[j]`` (a log density for a Gaussian
+        variable), exactly 0 where the row misses ``order[i]``: the rows of the full call sum to ``log p(x)`` over the
+        covered variables (normalised by the circuit's partition function).  The pass of `autoregressive_conditionals`
+        without its ``(B, P, C)`` buffer; discrete and Gaussian variables may be mixed (a Gaussian layer with a
+        ``log_partition`` is refused).  NaN where the prefix has no mass, -inf where only the observed value has none;
+        out-of-range evidence as in `autoregressive_conditionals`."""
+        from .autoregressive import autoregressive_log_probs
+
+        return autoregressive_log_probs(self, x, order, positions=positions, rows_per_chunk=rows_per_chunk)
+
+    def coding_tables(self, x: torch.Tensor, order=None, *, positions=None, precision: int = 16,
+                      rows_per_chunk: int | None = None):
+        """``(B, P, C + 1)`` int32: the cumulative frequency tables of the quantised `autoregressive_conditionals`, what an
+        arithmetic / ANS coder reads (cirkit_amd/codec.py): ``[..., 0] = 0``, ``[..., C] = 2**precision``, every state of
+        the step's variable at least one count and states past its count none.  Discrete variables only.  The quantiser is
+        a deterministic integer function of the fp32 conditionals (`ck_ar_quantise`, restated in numpy by
+        tests/autoregressive_restatement.py): ``1 + floor(p_c (2**precision - S))`` per state, the slack to the first
+        state with the largest count; a NaN row (a prefix without mass, a bad row) becomes the uniform table.
+        ``ValueError``: `precision` outside 8 .. 24 or ``C > 2**(precision - 2)``."""
+        from .autoregressive import coding_tables
+
+        return coding_tables(self, x, order, positions=positions, precision=precision, rows_per_chunk=rows_per_chunk)
+
     def expected_statistics(self, x: torch.Tensor, missing_vars=None, *, rows_per_chunk: int | None = None):
         """The expected sufficient statistics of every parameter under ``p(. | x_O)``, summed over the rows of ``x`` (B, D):
         the E-step of EM, for any circuit `sample` accepts (the same refusals).  The reference has no such query.

@@ -8,18 +8,19 @@
 // file adds the product kernel and the leaves.
 #include <math.h>
 
-#include "ck_down.h"
+#include "ck_loo_leaf.h"
 
 namespace {
 
 using ck::blocks_of;
+using ck::entries_max;
+using ck::finite_d;
 using ck::kMaxLds;
 using ck::kThreads;
 using ck::kWaves;
+using ck::LooEntry;
+using ck::shifted_exp;
 
-__device__ __forceinline__ bool finite_d(float d) { return d > -INFINITY && d < INFINITY; }
-// exp(D - m), 0 for a unit without a derivative (m is finite whenever some D is)
-__device__ __forceinline__ float shifted_exp(float d, float m) { return finite_d(d) ? expf(d - m) : 0.f; }
 // m + log T, -inf where T = 0
 __device__ __forceinline__ float lift(float T, float m) { return T > 0.f ? m + logf(T) : -INFINITY; }
 __device__ __forceinline__ float logaddexp(float a, float b) {
@@ -131,26 +132,7 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 // ---- leaves --------------------------------------------------------------------------------------------------------
-// Per variable the entries start[q] .. start[q + 1] - 1, one per input fold over it, five int64 each: (global fold, units K,
-// states C of the fold's table, element offset of its (K, C) block in `ntab` -- or of its K means / standard deviations --,
-// element offset of its K log normalisers log Z_k in `lz`).
-struct LooEntry {
-  int64_t g, K, C, off, zoff;
-};
-
-// max_k D_k over the finite D_k of the entries s0 .. s1 - 1 at row n, strided over the lanes of a wave (not yet reduced)
-__device__ __forceinline__ float entries_max(const LooEntry* __restrict__ ent, int s0, int s1, const float* __restrict__ der,
-                                             const int64_t* __restrict__ val_off, int64_t n, int first, int step) {
-  float mx = -INFINITY;
-  for (int s = s0; s < s1; ++s) {
-    const LooEntry e = ent[s];
-    const float* dr = der + val_off[e.g] + n * e.K;
-    for (int k = first; k < e.K; k += step)
-      if (finite_d(dr[k])) mx = fmaxf(mx, dr[k]);
-  }
-  return mx;
-}
-
+// The leaf-entry table (LooEntry) and entries_max: ck_loo_leaf.h, shared with ck_ar.hip.
 // Categorical / Binomial query variables.  One wave owns (row, query variable).  With mD = max_k D_k, the weight of unit k is
 // pi_k = exp((D_k - mD) + log Z_k - m2) (m2 the maximum of the exponent's first two terms: nothing is exponentiated
 // unshifted, and the sum with log Z_k is taken at the size of log Z_k, not of D), staged in LDS; a_c = sum_k pi_k ntab[k, c]

@@ -1307,6 +1307,50 @@ int ck_loo_log_probs(const int64_t* entries, const int32_t* vstart, const int32_
                      const float* der, const float* vals, const int64_t* val_off, const void* ev, int x_float,
                      const int32_t* bad, int64_t B, float* out, void* stream);
 
+/* ---- autoregressive conditionals and coding tables ("Autoregressive conditionals and coding";
+ * additive, ABI 51) ----------------------------------------------------------------------------------------------------------
+ * The chain-rule decomposition of a row along an order of the variables: p(x_{o_i} | x_{o_0 .. o_{i-1}}) for every step i.
+ * Expanded row r = b P + j of a (B, D) batch is row b with every variable at step >= positions[j] set to the sentinel (-1 in
+ * an int64 batch, NaN in an fp32 one); its one query variable is the variable at that step.  Per chunk of expanded rows:
+ * ck_ar_expand, the evidence forward, the derivative pass above, then one of the leaves below -- those of the leave-one-out
+ * query with one query variable per row, the same arithmetic in the same order. */
+/* Rows r0 .. r0 + nb - 1 of the B P expanded rows of x (B, D; int64, or fp32 with x_float != 0).  order_pos (D): the step of
+ * each variable, -1 for a variable outside the order (copied as it is); positions (P): the selected steps, each the step of
+ * some variable.  Writes xe (nb, D), the masked evidence in the dtype of x; rowvar (nb), the query variable of each row;
+ * rowobs (nb, the dtype of x), the row's own value at that variable.  states (D) as ck_flow_check_evidence: an out-of-range
+ * category ANYWHERE in row b, hidden or not, sets bad[n] = 1 for its expanded rows and *flag |= 1 (flag may be NULL); bad is
+ * only ever set here. */
+int ck_ar_expand(const void* x, int x_float, int64_t B, int D, const int32_t* order_pos, const int32_t* positions, int P,
+                 const int32_t* states, int64_t r0, int64_t nb, void* xe, int32_t* rowvar, void* rowobs, int32_t* bad,
+                 int32_t* flag, void* stream);
+/* out (B, Cout): ck_loo_leaf_categorical with Q = 1 and the query variable rowvar[n] of each row; vstart (D + 1) the CSR of the
+ * entries over ALL variables.  One wave per row. */
+int ck_ar_leaf_categorical(const int64_t* entries, const int32_t* vstart, const int32_t* rowvar, int Cout, int max_units,
+                           const float* ntab, const float* lz, const float* der, const int64_t* val_off, const int32_t* bad,
+                           int64_t B, float* out, void* stream);
+/* out (B, 2): ck_loo_leaf_gaussian with Q = 1 and the query variable rowvar[n] of each row. */
+int ck_ar_leaf_gaussian(const int64_t* entries, const int32_t* vstart, const int32_t* rowvar, const float* mean,
+                        const float* stddev, const float* der, const int64_t* val_off, const int32_t* bad, int64_t B,
+                        float* out, void* stream);
+/* out (B): log p(x_q | the row's prefix) = lse_k(D_k + v_k) - lse_k(D_k + log Z_k) over the input units of q = rowvar[n], both
+ * sums shifted by max_k D_k, with v_k the unit's log value AT rowobs[n], formed here (the expanded row hides it from the
+ * forward): ltab[k, c] for a discrete unit -- ltab the LOG tables in the layout of ntab, unnormalised as the forward reads
+ * them, -inf for a state without mass --, log N(x; mean_k, stddev_k) for a Gaussian one (vkind[q] == 2; no log_partition).
+ * Exactly 0 where rowobs[n] is the sentinel, NaN where the prefix has no mass or bad[n] != 0, -inf where only the observed
+ * value has no mass.  ltab may be NULL without discrete variables, mean / stddev without Gaussian ones. */
+int ck_ar_log_probs(const int64_t* entries, const int32_t* vstart, const int32_t* vkind, const int32_t* rowvar,
+                    const void* rowobs, int x_float, int has_discrete, int has_gaussian, const float* ltab, const float* lz,
+                    const float* mean, const float* stddev, const float* der, const int64_t* val_off, const int32_t* bad,
+                    int64_t B, float* out, void* stream);
+/* out (rows, C + 1) int32: the cumulative frequency table of each row of p (rows, C) at T = 2^precision, 8 <= precision <= 24,
+ * C <= 2^(precision - 2).  With S = states[rowvar[n]] (clamped into 1 .. C): count_c = 1 + floor(p_c (T - S)) for c < S, the
+ * product rounded once to fp32, and 0 for c >= S; the slack T - sum_c count_c, of either sign, goes to the first state with the
+ * largest count.  A row with a value outside [0, 1] (NaN included), or whose largest count would fall below 1, is uniform:
+ * floor(T / S) each, the remainder to state 0.  out[n, 0] = 0, out[n, c + 1] = sum_{c' <= c} count_c', out[n, C] = T.  A
+ * deterministic integer function of the fp32 row.  One wave per row. */
+int ck_ar_quantise(const float* p, const int32_t* rowvar, const int32_t* states, int64_t rows, int C, int precision,
+                   int32_t* out, void* stream);
+
 /* ---- expected statistics ("Expected statistics"; additive, ABI 51) -----------------------------------
  * The flow pass above reduced OVER THE ROWS of a chunk: the expected sufficient statistics of every parameter under
  * p(. | x_O), the E-step of EM.  vals / flow / val_off as above, after the chunk's flow pass.  live (B) int32: rows with
