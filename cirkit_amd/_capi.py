@@ -330,6 +330,11 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_mpe_up_sum": [_i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _i, _l, _p],
     "ck_mpe_up_product": [_i, _p, _l, _i, _i, _i, _p, _p, _i, _l, _p],
     "ck_mpe_walk": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l, _l, _l, _i, _p, _p, _i, _p, _p],
+    "ck_mmap_input_sum": [_i, _p, _l, _l, _l, _i, _i, _i, _p, _l, _i, _p, _p],
+    "ck_mmap_up_input": [_i, _p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _i, _p, _i, _l, _i, _p, _p, _i, _p, _p,
+                         _p],
+    "ck_mmap_up_sum": [_i, _p, _p, _p, _p, _i, _l, _i, _i, _i, _i, _p, _p, _i, _l, _p],
+    "ck_mmap_walk": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l, _l, _l, _i, _p, _p, _i, _p, _p],
     "ck_flow_down_sum": [_i, _i, _p, _p, _l, _i, _i, _i, _i, _p, _p, _p, _i, _l, _p, _p],
     "ck_flow_segment_add": [_p, _p, _p, _p, _p, _p, _p, _l, _i, _l, _p],
     "ck_flow_down_product": [_i, _p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _l, _p],

@@ -986,6 +986,43 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         return mpe(self, x, query_vars, return_choices=return_choices, return_log_value=return_log_value,
                    rows_per_chunk=rows_per_chunk)
 
+    def marginal_map(self, x: torch.Tensor, query_vars, *, return_choices: bool = False, return_log_value: bool = False,
+                     return_log_prob: bool = False, rows_per_chunk: int | None = None):
+        """Marginal MAP completion of every row of ``x`` (B, D): the query variables are maximised while the missing
+        nuisance variables are summed out, for output fold 0, unit 0 and any circuit `sample` accepts (the same refusals).
+        The reference has no max semiring and no MAP query.
+
+        `query_vars`: the query set ``Q``, ONE for the whole batch: an iterable of variable ids (a ``range``) or a ``(D,)`` /
+        ``(1, D)`` bool mask; a ``(B, D)`` mask with B > 1 is a ``ValueError``, raised before anything is prepared or
+        launched, because the mode of a fold is a property of the call.  Every variable of ``Q`` is maximised in every row
+        and its entries of ``x`` are ignored; every other variable is evidence where ``x`` holds a value and is summed out
+        where it holds the sentinel (a negative category, NaN), so the summed-out set may differ from row to row.
+
+        Upward, a fold of a sum / mixing / CP-T / Tucker layer whose scope is disjoint from ``Q`` computes
+        ``log sum_i w_i exp(v_i)``, the marginal forward's value; a fold whose scope meets ``Q`` computes `mpe`'s
+        ``max_i (log w_i + v_i)``, bit for bit; product units add their children; an input unit gives ``log p(x_v)`` where
+        observed, ``max_c log p(c)`` where maximised and its log integral where summed out.  Downward, the walk of `mpe`
+        (argmax entry, smallest index on ties) ends at the first sum fold on the tree: nothing below holds a query variable.
+
+        Returns ``(B, D)`` on this device with the dtype rule of `sample`: the query entries filled, evidence bit for bit,
+        summed-out entries still holding the sentinel.  `return_choices`: also the ``(F, B)`` int32 choices of every sum-type
+        layer, -1 at sum folds and off the row's tree.  `return_log_value`: also the ``(B,)`` fp32 mixed sum / max value of
+        the root, which is the value of the returned completion's induced tree.  `return_log_prob`: also the ``(B,)`` fp32
+        exact ``log c(q*, x_E)`` of the returned completion with the summed-out variables marginalised (one marginal forward
+        of the returned rows).  ``log_value <= log_prob <= max_q log c(q, x_E)``: `log_prob` is a true LOWER BOUND of the
+        marginal MAP optimum; `log_value` is NOT an upper bound of anything.  With every variable in ``Q`` the results are
+        `mpe`'s, bit for bit; on a circuit that is deterministic over ``Q`` the completion is the exact marginal MAP.
+
+        A row without finite mass keeps the sentinel in its query entries and gets -1 choices and -inf (no exception, no
+        synchronisation); an out-of-range observed category is reported by `check_inputs` and its row's values are NaN,
+        nothing written.  `rows_per_chunk`: rows per upward pass (None: its arenas stay <= 2 GiB); results do not depend on
+        it.  Results are in the order: completion, choices, log value, log probability (cirkit_amd/marginal_map.py,
+        DESIGN.md section 11)."""
+        from .marginal_map import marginal_map
+
+        return marginal_map(self, x, query_vars, return_choices=return_choices, return_log_value=return_log_value,
+                            return_log_prob=return_log_prob, rows_per_chunk=rows_per_chunk)
+
     def posterior_marginals(self, x: torch.Tensor, query_vars, *, return_log_evidence: bool = False,
                             rows_per_chunk: int | None = None):
         """All single-variable posteriors of every row of ``x`` (B, D) at once: ``p[n, q, c] = p(X_{v_q} = c | x_O of row n)``

@@ -181,6 +181,7 @@ class Sampler:
         self._table: torch.Tensor | None = None  # the device descriptor table without choices
         self._desc: np.ndarray | None = None
         self._mpe = None  # the `MPEState` (cirkit_amd/mpe.py), built by the first `mpe` call
+        self._mmap = None  # the `MarginalMapState` (cirkit_amd/marginal_map.py), built by the first `marginal_map` call
         self._posterior = None  # the `PosteriorState` (cirkit_amd/posterior.py), built by the first `posterior_marginals` call
         self._interval = None  # the `IntervalState` (cirkit_amd/interval.py), built by the first `interval_log_prob` call
 

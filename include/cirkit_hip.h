@@ -1201,6 +1201,36 @@ int ck_mpe_walk(const ck_sample_layer* layers, const float* const* logw, const i
                 const int32_t* bad, int64_t row0, int64_t B, int64_t N, int D, const void* ev, void* x, int x_float,
                 float* logv, void* stream);
 
+/* ---- marginal MAP ("Marginal MAP"; additive, ABI 51) ------------------------------------------------
+ * MPE with a third role: the variables of the call's query set Q are maximised, every other variable is evidence where ev
+ * holds a value and summed out where it holds the sentinel.  is_query (D) uint8 marks Q; max_fold (total folds) uint8 marks
+ * the global folds whose scope meets Q.  A sum-type unit of a max fold is MPE's max_i (log w_i + v_i), of any other fold
+ * log sum_i w_i exp(v_i); product layers run ck_mpe_up_product.  The arena, descriptors and choices are MPE's. */
+/* Per (fold, unit) of an input layer: vsum the log integral the marginal forward gives an integrated unit: log_partition
+ * (F, K) or 0 (CK_SAMPLE_GAUSSIAN); the table's row C when row_c (the Binomial log-pmf table); the logsumexp over the C
+ * entries of a table of logits (t_log); 0 for a table of probabilities. */
+int ck_mmap_input_sum(int type, const float* tab, int64_t sf, int64_t sk, int64_t sc, int t_log, int C, int row_c,
+                      const float* log_partition, int64_t F, int K, float* vsum, void* stream);
+/* ck_mpe_up_input with the role of an entry holding the sentinel read from is_query: vmax (F, K) for a variable of Q, vsum
+ * (F, K) for any other.  The same range check, bad and flag. */
+int ck_mmap_up_input(int type, const int64_t* scope, const float* tab, int64_t sf, int64_t sk, int64_t sc, int t_log, int C,
+                     const float* mean, const float* stddev, const float* log_partition, const float* vmax, const float* vsum,
+                     const uint8_t* is_query, int64_t F, int K, const void* ev, int x_float, int64_t B, int D, float* vals,
+                     const int64_t* val_off, int fold_off, int32_t* flag, int32_t* bad, void* stream);
+/* ck_mpe_up_sum with the semiring chosen per fold: where max_fold[fold_off + f] != 0, max_i (lw[f, k, i] + v_i) in MPE's
+ * arithmetic, bit for bit; elsewhere m_r + log sum_i w[f, k, i] exp(v_i - m_r) over the entries with w > 0, m_r the largest
+ * entry value of the row (mixing != 0, a sum layer with Ko == Ki and block-diagonal weights: the largest of the unit's own
+ * H entries), -inf where no such entry is finite.  lw, w (F, Ko, M): the log and the linear weights. */
+int ck_mmap_up_sum(int type, const int32_t* child, const float* lw, const float* w, const uint8_t* max_fold, int mixing,
+                   int64_t F, int H, int Ki, int Ko, int M, float* vals, const int64_t* val_off, int fold_off, int64_t B,
+                   void* stream);
+/* ck_mpe_walk with two rules: a unit of a fold with max_fold[g] == 0 takes no entry (choice -1, nothing below it is walked),
+ * and an input unit writes only a variable of Q, so that a summed-out entry of x keeps its sentinel. */
+int ck_mmap_walk(const ck_sample_layer* layers, const float* const* logw, const int32_t* const* amax,
+                 const uint8_t* max_fold, const uint8_t* is_query, int n_layers, int root_fold, int root_unit,
+                 int total_folds, int S, const float* vals, const int64_t* val_off, const int32_t* bad, int64_t row0, int64_t B,
+                 int64_t N, int D, const void* ev, void* x, int x_float, float* logv, void* stream);
+
 /* ---- posterior marginals ("Posterior marginals"; additive, ABI 51) ---------------------------------
  * All single-variable posteriors p(X_v = c | x_O) of every row in one evidence forward and one top-down FLOW pass: the flow
  * of unit u is f(u) = d log c(x_O) / d log u in LINEAR space, f(root) = 1, and the posterior of v is the flow reaching the
