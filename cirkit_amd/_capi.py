@@ -360,6 +360,9 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_interval_block_sums": [_p, _p, _i, _i, _i, _p],
     "ck_categorical_interval_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ck_gaussian_interval_fwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "ck_soft_tables": [_p, _p, _p, _p, _i, _i, _i, _p],
+    "ck_soft_leaf_fwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
+    "ck_soft_posterior": [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _p],
     "ck_em_job_blocks": [_i, _l, _i],
     "ck_em_update": [_p, _p, _i, _f, _f, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],

@@ -1194,6 +1194,50 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
 
         return log_cdf(self, x, integrate_vars=integrate_vars, rows_per_chunk=rows_per_chunk)
 
+    def soft_evidence_log_prob(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None,
+                               rows_per_chunk: int | None = None):
+        """``(B, O, K)`` fp32, as `forward`: ``log Z(lambda)[n] = log sum_x c(x) prod_{v in S} lambda[n, v, x_v]`` -- soft
+        (likelihood, Pearl's virtual) evidence: every soft variable of a row carries a non-negative weight per state instead
+        of a value.  Exact, in one bottom-up pass: an input unit over a soft variable emits ``log sum_c lambda(c) t_k(c)``,
+        the inner layers are the layer-wise forward's.  Point evidence, missing values, intervals and arbitrary per-variable
+        sets are its 0/1 special cases.  The reference has no such query.
+
+        `soft_vars`: the soft variables ``S``, an iterable of ids or a ``(D,)`` / ``(1, D)`` bool mask (the forms and errors
+        of `posterior_marginals`' ``query_vars``), one set for the whole batch, in ascending order; None: every variable a
+        Categorical / Binomial layer reads.  `log_lik`: ``(B, S, C)`` floating point (staged as fp32),
+        ``log_lik[n, s, c] = log lambda`` of state ``c`` of the ``s``-th soft variable; ``C`` at least the largest state
+        count among the soft variables, entries at ``c >= states(v)`` are never read.  ``-inf`` is weight 0 (a variable
+        whose read entries are all ``-inf`` gives ``-inf`` for the row); a NaN or ``+inf`` in a read entry makes that row
+        alone NaN.  `x`: ``(B, D)`` hard evidence for the other variables, `forward`'s dtype and sentinels (None: all of
+        them integrated out); its entries at soft variables are ignored; an out-of-range observed category makes that row
+        alone NaN and is reported by `check_inputs` (`posterior_marginals`' rule).
+
+        Refused before anything is allocated or launched: a complex semiring (``ValueError``), Embedding / ConstantValue /
+        TensorDot layers (``TypeError``), a soft variable read by a Gaussian layer (``NotImplementedError``: Gaussian
+        variables stay hard evidence), a soft variable outside every input layer's scope and a `log_lik` of the wrong rank,
+        ``S``, ``C`` or batch (``ValueError``).  The result is the caller's own tensor.  `rows_per_chunk`: rows per pass
+        (None: the activation arena stays <= 2 GiB); results do not depend on it.  No host synchronisation
+        (cirkit_amd/soft_evidence.py, cirkit_amd/csrc/ck_soft.hip, DESIGN.md section 11 "Soft evidence")."""
+        from .soft_evidence import soft_evidence_log_prob
+
+        return soft_evidence_log_prob(self, log_lik, x, soft_vars=soft_vars, rows_per_chunk=rows_per_chunk)
+
+    def soft_posterior_marginals(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None,
+                                 return_log_evidence: bool = False, rows_per_chunk: int | None = None):
+        """``(B, S, C)`` fp32, the shape of `log_lik`: the posterior of every soft variable under the soft evidence of
+        `soft_evidence_log_prob` (its arguments, rules and refusals, and those of `sample`),
+        ``p[n, s, c] = p(X_{v_s} = c | lambda, x) = d log Z(lambda)[n] / d log_lik[n, s, c]``, for output fold 0, unit 0 as
+        `posterior_marginals`: that bottom-up pass, the flow pass of `posterior_marginals` and one leaf launch.  Entries at
+        ``c >= states(v)`` are 0; the output is not renormalised (a row sums to 1 up to rounding).  A row without a finite
+        ``log Z`` -- no mass, a NaN / ``+inf`` in a read entry, an out-of-range hard category -- is NaN.
+        `return_log_evidence`: also the ``(B,)`` fp32 ``log Z(lambda)``.  `rows_per_chunk`: rows per pass (None: the value
+        arena plus the flow arena and its message buffer stay <= 2 GiB); results do not depend on it.  No host
+        synchronisation beyond `posterior_marginals`' one read per parameter state (cirkit_amd/soft_evidence.py)."""
+        from .soft_evidence import soft_posterior_marginals
+
+        return soft_posterior_marginals(self, log_lik, x, soft_vars=soft_vars, return_log_evidence=return_log_evidence,
+                                        rows_per_chunk=rows_per_chunk)
+
     def log_likelihood_sum(self, x: torch.Tensor, out: torch.Tensor | None = None, *, reduce: bool = False) -> torch.Tensor:
         """Device tensor ``[sum_b log p(x_b), B]`` in fp64 -- the two numbers the data-parallel
         all-reduce exchanges (SURVEY.md section 8 e).  Requires a single scalar output.

@@ -184,6 +184,7 @@ class Sampler:
         self._mmap = None  # the `MarginalMapState` (cirkit_amd/marginal_map.py), built by the first `marginal_map` call
         self._posterior = None  # the `PosteriorState` (cirkit_amd/posterior.py), built by the first `posterior_marginals` call
         self._interval = None  # the `IntervalState` (cirkit_amd/interval.py), built by the first `interval_log_prob` call
+        self._soft = None  # the `SoftEvidenceState` (cirkit_amd/soft_evidence.py), built by the first soft-evidence call
 
     # -- once per parameter state ------------------------------------------------------------------------------------
     def _z_circuit(self):

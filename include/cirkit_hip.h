@@ -1474,6 +1474,34 @@ int ck_categorical_interval_fwd(const float* table, const float* side, const int
 int ck_gaussian_interval_fwd(const float* mean, const float* stddev, const float* log_partition, const float* lo,
                              const float* hi, const int64_t* scope, float* out, int F, int B, int K, int D, void* stream);
 
+/* ---- soft (likelihood) evidence ("Soft evidence"; additive, ABI 51) --------------------------------
+ * A soft variable of a row carries log_lik[n, s, c] = the log of a non-negative weight per state, s its position among the
+ * soft variables; an input unit over it emits log sum_c exp(log_lik[n, s, c] + table[c, k]).
+ *
+ * ck_soft_tables: once per parameter state, from a (F, C+1, K) log table: mt (F, K) the maximum of each unit's C terms (0
+ * where all are -inf), lin (F, C, K) = exp(table - mt) and linT (F, K, C), its transpose. */
+int ck_soft_tables(const float* table, float* lin, float* linT, float* mt, int F, int C, int K, void* stream);
+/* out (F, B, K), the folds f with spos[f] >= 0 only (spos (F) int32: the position of the fold's variable among the soft
+ * variables, -1 for a hard one, whose block is left alone): out[f, n, k] = log sum_{c < C} exp(log_lik[n, spos[f], c] +
+ * table[f, c, k]); log_lik (B, S, Cl) fp32, Cl >= C, columns >= C never read.  -inf is weight 0 (every term -inf: -inf).  A
+ * NaN or +inf in a read entry makes the row's K outputs NaN and sets bad[n] = 1 (bad (B) int32 is only ever set).  K = 32 /
+ * 64, C <= 256 and exact == 0: rows shifted by their maximum and exponentiated in LDS, contracted with lin on
+ * v_mfma_f32_32x32x2_f32, out = ml + mt + log(acc), and every entry with acc < 2^-60 recomputed by the exact form.
+ * Otherwise, and with exact != 0: the exact two-pass log-sum-exp per (n, k). */
+int ck_soft_leaf_fwd(const float* table, const float* lin, const float* mt, const float* log_lik, const int32_t* spos,
+                     float* out, int32_t* bad, int F, int B, int K, int C, int S, int Cl, int exact, void* stream);
+/* out (B, S, Cl): out[n, s, c] = sum over the input folds of soft variable s and their units k of
+ * f_k exp(table[c, k] + log_lik[n, s, c] - v_k), f from the flow arena and v the fold's own value in the value arena; 0 at
+ * c >= the fold's states.  entries: six int64 per input fold (global fold, units K, states C, address of its (C+1, K) log
+ * table, element offset of its (K, C) block in linT, element offset of its K maxima in mt), those of variable s at
+ * qstart[s] .. qstart[s + 1] - 1.  Rows and logev as ck_flow_leaf_categorical.  K_uniform 32 / 64 and C_uniform <= 256 when
+ * every entry has that many units and states (matrix cores; a row with a unit whose v_k - ml - mt_k < log 2^-60 takes the
+ * exact form), 0 otherwise (the exact form everywhere). */
+int ck_soft_posterior(const int64_t* entries, const int32_t* qstart, int S, int Cl, int K_uniform, int C_uniform,
+                      const float* log_lik, const float* linT, const float* mt, const float* flow, const float* vals,
+                      const int64_t* val_off, int root_fold, int root_ko, const int32_t* bad, int64_t B, float* out,
+                      float* logev, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
