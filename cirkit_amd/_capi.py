@@ -363,6 +363,10 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_soft_tables": [_p, _p, _p, _p, _i, _i, _i, _p],
     "ck_soft_leaf_fwd": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p],
     "ck_soft_posterior": [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _l, _p, _p, _p],
+    "ck_soft_max_leaf": [_p, _p, _p, _p, _p, _i, _p, _l, _l, _i, _i, _i, _i, _p],
+    "ck_soft_sample_walk": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l, _l, _l, _i, C.c_uint64, _i, _p, _p, _p, _i, _p, _p],
+    "ck_soft_mpe_walk": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _l, _l, _l, _i, _i, _p, _p, _p, _i, _p, _p],
+    "ck_soft_decode_leaf": [_i, _p, _p, _p, _i, _i, _i, _p, _p, _l, _l, _i, C.c_uint64, _p, _i, _p],
     "ck_em_job_blocks": [_i, _l, _i],
     "ck_em_update": [_p, _p, _i, _f, _f, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],

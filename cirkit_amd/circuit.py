@@ -1238,6 +1238,52 @@ class HipCircuit(_LaunchMixin, _ProfilingMixin):
         return soft_posterior_marginals(self, log_lik, x, soft_vars=soft_vars, return_log_evidence=return_log_evidence,
                                         rows_per_chunk=rows_per_chunk)
 
+    def soft_mpe(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, return_choices: bool = False,
+                 return_log_value: bool = False, rows_per_chunk: int | None = None):
+        """``(B, D)`` in `sample_conditional`'s dtype (int64, or fp32 with a Gaussian layer): the max-product completion of
+        every row under the soft evidence of `soft_evidence_log_prob` (its `log_lik`, `x`, `soft_vars` and `rows_per_chunk`,
+        rules, refusals and their order; then the refusals of `sample`) -- `mpe` with one more kind of input: a unit over a
+        soft variable is worth ``max_c (t_k(c) + log_lik[n, s, c])``.  Observed entries of `x` come back exactly; every soft
+        variable is filled with the state the row's tree takes; every other entry of `x` holding the sentinel is filled as
+        `mpe` fills it (the unit's argmax state, the Gaussian mean); variables outside every input layer's scope read 0.
+        Smallest index among equal maxima, at sum units and at the soft leaf.  On a deterministic circuit the result is the
+        exact ``argmax_x [log c(x) + sum_v log lambda_v(x_v)]``, otherwise the usual max-product approximation.
+
+        `return_choices`: also the sum-type layers' choices, as `mpe`.  `return_log_value`: also the ``(B,)`` fp32 root
+        max-product value.  A row with a NaN / ``+inf`` in a read entry of `log_lik`, or with an out-of-range observed
+        category (reported by `check_inputs`), keeps its sentinels and has value NaN; a row whose root value is ``-inf``
+        (a soft variable whose read entries are all ``-inf``) keeps them with value ``-inf``; no other row is affected.
+        Results do not depend on `rows_per_chunk`.  No host synchronisation beyond `sample`'s one read per parameter state.
+        The reference has no such query (cirkit_amd/soft_decode.py, cirkit_amd/csrc/ck_soft_decode.hip, DESIGN.md section
+        11 "Decoding under soft evidence")."""
+        from .soft_decode import soft_mpe
+
+        return soft_mpe(self, log_lik, x, soft_vars=soft_vars, return_choices=return_choices,
+                        return_log_value=return_log_value, rows_per_chunk=rows_per_chunk)
+
+    def sample_soft(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, seed: int | None = None,
+                    return_choices: bool = False, return_log_evidence: bool = False, rows_per_chunk: int | None = None):
+        """``(B, D)`` in `sample_conditional`'s dtype: one exact joint draw per row from
+        ``p(x_unobserved | lambda, x_O)``, proportional to ``c(x) prod_v lambda_v(x_v)``, under the soft evidence of
+        `soft_evidence_log_prob` (its arguments, rules, refusals and their order; then the refusals of `sample`).
+        `sample_conditional`'s walk over the values of the soft bottom-up pass; an input unit over a soft variable on the
+        row's tree draws ``c`` in proportion to ``exp(t_k(c) + log_lik[n, s, c])``.  With 0 / ``-inf`` weights this is exact
+        truncated sampling (intervals, arbitrary per-variable sets).  Observed entries of `x` come back exactly; every soft
+        variable and every other entry holding the sentinel is drawn; variables outside every input layer's scope read 0.
+
+        `seed`: as `sample_conditional`; every node's one Philox call is keyed by (row of the whole batch, global fold),
+        so the draws do not depend on `rows_per_chunk`, and with ``log_lik == 0`` the stream is `sample_conditional`'s.
+        `return_choices`: also the sum-type layers' choices.  `return_log_evidence`: also the ``(B,)`` fp32
+        ``log Z(lambda)``, bit for bit `soft_evidence_log_prob`'s value of the row.  Rows that draw nothing and keep their
+        sentinels: a NaN / ``+inf`` in a read entry of `log_lik` or an out-of-range observed category (evidence NaN; the
+        latter reported by `check_inputs`), a root value of ``-inf`` (evidence ``-inf``); no other row is affected.  No
+        host synchronisation beyond `sample`'s one read per parameter state.  The reference has no such query
+        (cirkit_amd/soft_decode.py, DESIGN.md section 11 "Decoding under soft evidence")."""
+        from .soft_decode import sample_soft
+
+        return sample_soft(self, log_lik, x, soft_vars=soft_vars, seed=seed, return_choices=return_choices,
+                           return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
+
     def log_likelihood_sum(self, x: torch.Tensor, out: torch.Tensor | None = None, *, reduce: bool = False) -> torch.Tensor:
         """Device tensor ``[sum_b log p(x_b), B]`` in fp64 -- the two numbers the data-parallel
         all-reduce exchanges (SURVEY.md section 8 e).  Requires a single scalar output.

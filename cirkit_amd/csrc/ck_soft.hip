@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "ck_internal.h"
+#include "ck_soft_entry.h"
 
 namespace {
 
@@ -191,13 +192,7 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 // ---- posteriors --------------------------------------------------------------------------------------------------------
-// Per soft variable s the entries qstart[s] .. qstart[s + 1] - 1, one per input fold over it, six int64 each.
-struct SoftEntry {
-  int64_t g, K, C;  // global fold, units, states
-  const float* table;  // the fold's (C + 1, K) log table
-  int64_t lin_off;     // element offset of its (K, C) block in linT
-  int64_t mt_off;      // element offset of its K maxima in mt
-};
+using ck::SoftEntry;  // (ck_soft_entry.h, shared with ck_soft_decode.hip)
 
 __device__ __forceinline__ bool row_ok(const float* __restrict__ vals, const int64_t* __restrict__ val_off, int root_fold,
                                        int root_ko, const int32_t* __restrict__ bad, int64_t n) {

@@ -93,21 +93,30 @@ class MPEState:
             hit = self._arenas[R] = (arena, torch.from_numpy(off).to(self.s.device), bases)
         return hit
 
-    def _upward(self, xm: torch.Tensor, R: int, flag: torch.Tensor | None, bad: torch.Tensor, stream: int):
+    def _up_layer(self, j: int, xm: torch.Tensor, R: int, flag: torch.Tensor | None, bad: torch.Tensor, stream: int) -> None:
+        """The upward launch of layer j into the arena of R rows."""
         s = self.s
         arena, val_off, _ = self._arena(R)
         vals, vo = arena.data_ptr(), val_off.data_ptr()
-        x_float = 1 if s.float_out else 0
-        for j, d in enumerate(s.layers):
-            F, H, Ki, Ko, M, kind, g0 = d["F"], d["H"], d["Ki"], d["Ko"], d["M"], d["kind"], int(s.fold_off[j])
-            if kind in (capi.CK_SAMPLE_CATEGORICAL, capi.CK_SAMPLE_GAUSSIAN):
-                capi.call("ck_mpe_up_input", kind, d["scope"].data_ptr(), *d["src"], d["vmax"].data_ptr(), F, Ko, xm.data_ptr(),
-                          x_float, R, s.D, vals, vo, g0, None if flag is None else flag.data_ptr(), bad.data_ptr(), stream)
-            elif kind in (capi.CK_SAMPLE_HADAMARD, capi.CK_SAMPLE_KRONECKER):
-                capi.call("ck_mpe_up_product", kind, d["child"].data_ptr(), F, H, Ki, Ko, vals, vo, g0, R, stream)
-            else:
-                capi.call("ck_mpe_up_sum", kind, d["child"].data_ptr(), d["lw"].data_ptr(), F, H, Ki, Ko, M, vals, vo, g0, R,
-                          stream)
+        d = s.layers[j]
+        F, H, Ki, Ko, M, kind, g0 = d["F"], d["H"], d["Ki"], d["Ko"], d["M"], d["kind"], int(s.fold_off[j])
+        if kind in (capi.CK_SAMPLE_CATEGORICAL, capi.CK_SAMPLE_GAUSSIAN):
+            capi.call("ck_mpe_up_input", kind, d["scope"].data_ptr(), *d["src"], d["vmax"].data_ptr(), F, Ko, xm.data_ptr(),
+                      1 if s.float_out else 0, R, s.D, vals, vo, g0, None if flag is None else flag.data_ptr(), bad.data_ptr(),
+                      stream)
+        elif kind in (capi.CK_SAMPLE_HADAMARD, capi.CK_SAMPLE_KRONECKER):
+            capi.call("ck_mpe_up_product", kind, d["child"].data_ptr(), F, H, Ki, Ko, vals, vo, g0, R, stream)
+        else:
+            capi.call("ck_mpe_up_sum", kind, d["child"].data_ptr(), d["lw"].data_ptr(), F, H, Ki, Ko, M, vals, vo, g0, R, stream)
+
+    def _upward(self, xm: torch.Tensor, R: int, flag: torch.Tensor | None, bad: torch.Tensor, stream: int, after_input=None):
+        """Every layer's upward launch, in plan order (`after_input(j)`: called after the launch of input layer j -- the soft
+        max leaf of `soft_mpe`, cirkit_amd/soft_decode.py)."""
+        for j, d in enumerate(self.s.layers):
+            self._up_layer(j, xm, R, flag, bad, stream)
+            if after_input is not None and "scope" in d:
+                after_input(j)
+        arena, val_off, _ = self._arena(R)
         return arena, val_off
 
     # -- once per call ------------------------------------------------------------------------------------------------

@@ -185,6 +185,7 @@ class Sampler:
         self._posterior = None  # the `PosteriorState` (cirkit_amd/posterior.py), built by the first `posterior_marginals` call
         self._interval = None  # the `IntervalState` (cirkit_amd/interval.py), built by the first `interval_log_prob` call
         self._soft = None  # the `SoftEvidenceState` (cirkit_amd/soft_evidence.py), built by the first soft-evidence call
+        self._soft_decode = None  # the `SoftDecodeState` (cirkit_amd/soft_decode.py), built by the first soft_mpe / sample_soft
 
     # -- once per parameter state ------------------------------------------------------------------------------------
     def _z_circuit(self):

@@ -165,7 +165,8 @@ class SoftEvidenceState:
         ks, cs = set(ent[:, 1].tolist()), set(ent[:, 2].tolist())
         uniform = len(ks) == 1 and len(cs) == 1 and next(iter(ks)) in (32, 64)
         return {"spos": spos, "entries": torch.from_numpy(ent).to(s.device), "start": torch.from_numpy(start).to(s.device),
-                "K_uniform": next(iter(ks)) if uniform else 0, "C_uniform": next(iter(cs)) if uniform else 0}
+                "K_uniform": next(iter(ks)) if uniform else 0, "C_uniform": next(iter(cs)) if uniform else 0,
+                "entries_host": ent}
 
     # -- per chunk -------------------------------------------------------------------------------------------------------
     def hard_inputs(self, bd, xc: torch.Tensor, bad: torch.Tensor, stream: int) -> None:
@@ -285,14 +286,20 @@ class SoftEvidenceState:
         return (out, logev) if return_log_evidence else out
 
 
-def _state(hc: "HipCircuit", log_lik, x, soft_vars) -> tuple[SoftEvidenceState, list[int]]:
-    """Every refusal and argument error, then the circuit's state: nothing is allocated or launched before them."""
+def check_call(hc: "HipCircuit", log_lik, x, soft_vars) -> list[int]:
+    """Every refusal and argument error of a soft-evidence query, in order; returns the soft variable ids."""
     check_plan(hc.user_plan)
     ids = soft_ids(hc.user_plan, soft_vars)
     check_arguments(hc.user_plan, log_lik, x, ids)
     for l in hc.layers:
         if isinstance(l, HipInputLayer) and not isinstance(l, HipConstantValueLayer) and not l.can_integrate:
             raise NotImplementedError(f"soft evidence through {type(l).__name__}: it cannot integrate")
+    return ids
+
+
+def _state(hc: "HipCircuit", log_lik, x, soft_vars) -> tuple[SoftEvidenceState, list[int]]:
+    """Every refusal and argument error, then the circuit's state: nothing is allocated or launched before them."""
+    ids = check_call(hc, log_lik, x, soft_vars)
     s = sampler(hc)
     if s._soft is None:
         s._soft = SoftEvidenceState(s)

@@ -1502,6 +1502,44 @@ int ck_soft_posterior(const int64_t* entries, const int32_t* qstart, int S, int 
                       const int64_t* val_off, int root_fold, int root_ko, const int32_t* bad, int64_t B, float* out,
                       float* logev, void* stream);
 
+/* ---- decoding under soft evidence ("Decoding under soft evidence"; additive, ABI 51) ---------------
+ * An assignment under c(x) prod_v lambda_v(x_v): the max-product completion (soft_mpe) or an exact joint draw (sample_soft).
+ * The reference has no such query: its queries are IntegrateQuery and SamplingQuery (queries.py), neither takes weights
+ * per state.
+ *
+ * ck_soft_max_leaf: the max-product value of the input units over a soft variable, into the MPE arena (vals / val_off as
+ * ck_mpe_up_input writes it, global folds fold_off .. fold_off + F - 1): for the folds f with spos[f] >= 0,
+ * vals[val_off[fold_off + f] + n K + k] = max_{c < C} (table[f, c, k] + log_lik[n, spos[f], c]); table the (F, C+1, K) log
+ * table ck_soft_leaf_fwd reads, log_lik (B, S, Cl) fp32, Cl >= C.  The add and the 3-way max are ck_mpe_up_sum's; -inf is
+ * weight 0; a NaN or +inf in a read entry sets bad[n] = 1 (bad (B) int32 is only ever set).  Folds with spos[f] < 0 are
+ * left alone. */
+int ck_soft_max_leaf(const float* table, const float* log_lik, const int32_t* spos, float* vals, const int64_t* val_off,
+                     int fold_off, int32_t* bad, int64_t F, int64_t B, int K, int C, int S, int Cl, void* stream);
+/* ck_sample_cond_walk / ck_mpe_walk with one more rule: an unobserved input unit of a fold over a soft variable writes no
+ * value; it records the node, node[n S_soft + s] = g * 32768 + k (global fold g, unit k; n the row of the whole batch, s the
+ * variable's position among the soft variables).  spos: a DEVICE array of n_layers pointers, each layer's (F) int32
+ * positions (-1: hard) or NULL; node (N, S_soft) int32 holds -1 on entry.  ck_soft_sample_walk: bad (N) as ck_mpe_walk; a
+ * row with bad[n] != 0 draws nothing; logev[n] is the root value, NaN where bad[n] != 0. */
+int ck_soft_sample_walk(const ck_sample_layer* layers, const float* const* weights, const int32_t* const* spos, int n_layers,
+                        int root_fold, int root_unit, int total_folds, int S, const float* vals, const int64_t* val_off,
+                        const int32_t* bad, int64_t row0, int64_t B, int64_t N, int D, uint64_t seed, int S_soft,
+                        int32_t* node, const void* ev, void* x, int x_float, float* logev, void* stream);
+int ck_soft_mpe_walk(const ck_sample_layer* layers, const float* const* logw, const int32_t* const* amax,
+                     const int32_t* const* spos, int n_layers, int root_fold, int root_unit, int total_folds, int S,
+                     const float* vals, const int64_t* val_off, const int32_t* bad, int64_t row0, int64_t B, int64_t N, int D,
+                     int S_soft, int32_t* node, const void* ev, void* x, int x_float, float* logv, void* stream);
+/* The value of every soft variable with a recorded node, rows row0 .. row0 + B - 1 of the batch: x[nl D + vars[s]] (x
+ * (B, D) the chunk's output, int64 or fp32 with x_float; log_lik (B, S, Cl) the chunk's; node (N, S) the whole batch's).  The
+ * node's fold selects one of the entries of variable s (entries / qstart as ck_soft_posterior, but the table address is
+ * that of the fold's TRANSPOSED log table, (K, C): the same values, a unit's states contiguous).  mode 0: the smallest c
+ * with table[c, k] + log_lik[n, s, c] equal to its maximum, the sum by ck_soft_max_leaf's add, so that the maximum is the
+ * stored unit value bit for bit.  mode 1: c drawn in proportion to exp(table[c, k] + log_lik[n, s, c]), every term relative
+ * to the maximum, with u = the uniform of word 0 of the node's Philox call (row0 + nl, g).  C_max: the largest state count
+ * among the entries (the lanes per item). */
+int ck_soft_decode_leaf(int mode, const int64_t* entries, const int32_t* qstart, const int64_t* vars, int S, int Cl,
+                        int C_max, const float* log_lik, const int32_t* node, int64_t row0, int64_t B, int D, uint64_t seed,
+                        void* x, int x_float, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
