@@ -22,6 +22,13 @@ namespace {
 
 constexpr int kBwdNC = 32;
 
+// Lab builds only (scripts/defect_injection.sh layer): defects the kernel-by-kernel suite (tests/test_gpu_layer_backward.py)
+// must see.  1: tile32 computes rows beyond B as live (their stores stay masked: dW takes the repeated last row); 2: tile32
+// stops after a wave's first tile; 3: the register mixing kernel scales dmw by 1 + 1e-3.
+#ifndef CK_BWD_LAB_DEFECT
+#define CK_BWD_LAB_DEFECT 0
+#endif
+
 __device__ __forceinline__ void grad_store(float* p, float g, int accumulate) {
   if (accumulate == 0)
     *p = g;
@@ -282,11 +289,12 @@ __global__ void __launch_bounds__(256)
   float* gy_s = lds[wave][0];
   float* e_s = lds[wave][1];
   const int tile0 = (blockIdx.x * 4 + wave) * tiles_per_wave;
-  for (int tt = 0; tt < tiles_per_wave; ++tt) {
+  for (int tt = 0; tt < (CK_BWD_LAB_DEFECT == 2 ? 1 : tiles_per_wave); ++tt) {
     const int b0 = (tile0 + tt) * 32;
     if (b0 >= B) break;
     const int b = b0 + b_in;
     const bool live = b < B;
+    const bool in_batch = CK_BWD_LAB_DEFECT == 1 ? true : live;  // (what masks the row's e and gy)
     const int bl = live ? b : B - 1;
     float v[16];
 #pragma unroll
@@ -295,7 +303,7 @@ __global__ void __launch_bounds__(256)
     const float m = row_max16(v);
     float e[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) e[j] = live ? __builtin_amdgcn_exp2f((v[j] - m) * kL2E) : 0.f;  // (v_exp_f32, as the forward: ~5e-7 relative)
+    for (int j = 0; j < 16; ++j) e[j] = in_batch ? __builtin_amdgcn_exp2f((v[j] - m) * kL2E) : 0.f;  // (v_exp_f32, as the forward: ~5e-7 relative)
     // y = W e
     f32x16 acc;
 #pragma unroll
@@ -313,7 +321,7 @@ __global__ void __launch_bounds__(256)
       float go[16];
       tile_load(gout + (static_cast<int64_t>(f) * B + bl) * kK + 4 * kh, go);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) gy[r] = (live && acc[r] > 0.f && go[r] != 0.f) ? go[r] * __builtin_amdgcn_rcpf(acc[r]) : 0.f;
+      for (int r = 0; r < 16; ++r) gy[r] = (in_batch && acc[r] > 0.f && go[r] != 0.f) ? go[r] * __builtin_amdgcn_rcpf(acc[r]) : 0.f;
     }
     // gv = e * (W^T gy)
 #pragma unroll
@@ -1048,7 +1056,7 @@ __global__ void __launch_bounds__(256)
 // out[k] = log(sum_h w[k,h] e_h[k]) + m, e_h[k] = exp(x_h[k] - m), m = max over (h, k) of the row
 // (ck_mixing_lse_fwd).  With y[k] = exp(out[k] - m) recomputed as sum_h w e:
 //   g x_h[k] = gout[k] w[k,h] e_h[k] / y[k],     d w[k,h] += sum_b gout[k] e_h[k] / y[k].
-// One wave per batch row (lanes over k), dW partials in LDS per workgroup, one atomic per (k, h).
+// One wave per batch row (lanes over k), dW partials in LDS per workgroup, one atomic per (k, h).  (gout / y: 0 where y = 0 or gout = 0.)
 __global__ void __launch_bounds__(256)
     mixing_bwd_kernel(const float* __restrict__ arena, float* __restrict__ garena, const int64_t* __restrict__ row_off,
                       const int64_t* __restrict__ grow_off,
@@ -1075,7 +1083,8 @@ __global__ void __launch_bounds__(256)
       float y = 0.f;
       for (int h = 0; h < H; ++h)
         y = fmaf(mwf[static_cast<int64_t>(k) * H + h], expf(arena[ro[h] + static_cast<int64_t>(b) * K + k] - mx), y);
-      const float gy = gout[(static_cast<int64_t>(f) * B + b) * K + k] / y;
+      const float go = gout[(static_cast<int64_t>(f) * B + b) * K + k];
+      const float gy = (y > 0.f && go != 0.f) ? go / y : 0.f;  // (as the sum kernels: a row of -inf inputs has y = 0 and gradient 0)
       for (int h = 0; h < H; ++h) {
         const float e = expf(arena[ro[h] + static_cast<int64_t>(b) * K + k] - mx);
         const float ge = gy * e;
@@ -1142,7 +1151,8 @@ __global__ void __launch_bounds__(256)
         x[h] = expf(x[h] - mx);
         y = fmaf(wk[h], x[h], y);
       }
-    const float gy = live ? gout[(static_cast<int64_t>(f) * B + bl) * K + k] / y : 0.f;
+    const float go = live ? gout[(static_cast<int64_t>(f) * B + bl) * K + k] : 0.f;
+    const float gy = (y > 0.f && go != 0.f) ? go / y : 0.f;
 #pragma unroll
     for (int h = 0; h < HMAX; ++h)
       if (h < H) {
@@ -1159,6 +1169,7 @@ __global__ void __launch_bounds__(256)
     float t = 0.f;
     for (int wv = 0; wv < 4; ++wv)
       for (int sb = 0; sb < rpw; ++sb) t += red[wv][sb * K + kk][h];
+    if (CK_BWD_LAB_DEFECT == 3) t *= 1.001f;
     if (t != 0.f) atomicAdd(&dmw[(static_cast<int64_t>(f) * K + kk) * H + h], t);
   }
 }

@@ -605,7 +605,9 @@ int ck_hadamard_bwd(float* garena, const int64_t* row_off, const float* gout, in
 int ck_gaussian_bwd(const float* gout, const float* xt, const int64_t* scope, const float* mean, const float* stddev,
                     float* dmean, float* dstddev, int F, int B, int K, void* stream);
 /* Mixing layer backward (forward: ck_mixing_lse_fwd): input gradients into garena at the children's
- * offsets (accumulate 0 store / 1 add / 2 atomic), dmw (F, K, H) += batch sums (zero it first). */
+ * offsets (accumulate 0 store / 1 add / 2 atomic), dmw (F, K, H) += batch sums (zero it first).  As in ck_sum_lse_bwd,
+ * gout[k] / y[k] is taken as 0 where y[k] = 0 (every input of the row -inf, or only zero coefficients meet finite inputs) or
+ * gout[k] = 0: such a row has input gradients 0 and adds nothing to dmw (autograd gives NaN there). */
 int ck_mixing_lse_bwd(const float* arena, float* garena, const int64_t* row_off, const int64_t* grad_row_off,
                       const float* mw, const float* gout, float* dmw, int F, int H, int B, int K, int accumulate,
                       void* stream);
