@@ -2,7 +2,7 @@
 
 from .plan import Plan, plan_from_torch_circuit  # noqa: F401
 
-__all__ = ["Plan", "plan_from_torch_circuit", "HipCircuit", "HipCircuitStreams", "HipTrainer", "HipCircuitModule", "compile"]
+__all__ = ["Plan", "plan_from_torch_circuit", "HipCircuit", "HipCircuitStreams", "HipTrainer", "HipCircuitModule", "HipSquaredCircuit", "compile"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch/ROCm
@@ -18,6 +18,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch/ROC
         from . import training
 
         return getattr(training, name)
+    if name == "HipSquaredCircuit":
+        from .squared import HipSquaredCircuit
+
+        return HipSquaredCircuit
     if name == "compile":
         from .pipeline import compile
 

@@ -128,13 +128,18 @@ def _gaussian_square_integral(l: LayerSpec) -> LayerSpec:
     return LayerSpec("constant", F, 1, 0, K * K, {"num_output_units": K * K, "log_space": True}, {"value": value})
 
 
-def squared_partition_plan(plan: Plan, *, conjugate: bool | None = None) -> Plan:
+def squared_partition_plan(plan: Plan, *, conjugate: bool | None = None, return_layer_map: bool = False):
     """The plan of ``Z = integral of c(x) * conj(c(x)) dx`` for a circuit ``c`` made of Embedding
     inputs, Hadamard products and dense sums (as such or fused into CP-T layers).  Z has no
     variables: evaluate it with ``HipCircuit(z_plan, tensors_of_c)()`` -> ``(1, 1)``.  Categorical and Gaussian
     inputs are covered too (a real circuit squared: Z = sum / integral of c(x)^2).
 
-    `conjugate` defaults to True under the complex semiring (|c|^2) and False otherwise (c^2)."""
+    `conjugate` defaults to True under the complex semiring (|c|^2) and False otherwise (c^2).
+
+    `return_layer_map`: also return ``{layer of c: layer of Z}``, the layer of Z that carries the squared output of each
+    layer of ``c`` (K^2 units, unit ``k K + l`` pairing unit k of c with unit l of its conjugate; fold order is kept, so fold f
+    of the one is fold f of the other) -- what `cirkit_amd.squared` reads the integrated folds of a marginal from.  For a sum
+    / CP-T layer it is the second TensorDot layer of the pair, the first one sits right before it."""
     if conjugate is None:
         conjugate = plan.semiring == "complex-lse-sum"
     folds = [l.num_folds for l in plan.layers]
@@ -183,4 +188,5 @@ def squared_partition_plan(plan: Plan, *, conjugate: bool | None = None) -> Plan
                                     _fold_index([[(first, f)] for f in range(F)], z_folds)))
     out_pairs = resolve_fold_index(plan.output, folds).reshape(-1, 2)
     output = _fold_index([[(last_of[int(p)], int(f)) for p, f in out_pairs]], z_folds, output=True)
-    return Plan(plan.semiring, 0, out_layers, output, dict(plan.tensors), plan.name + "_Z")
+    z_plan = Plan(plan.semiring, 0, out_layers, output, dict(plan.tensors), plan.name + "_Z")
+    return (z_plan, dict(last_of)) if return_layer_map else z_plan

@@ -1,0 +1,374 @@
+"""Exact marginals and conditionals of a squared circuit ``p(x) = |c(x)|^2 / Z`` on the GPU.
+
+The reference answers ``integral of |c(x_O, x_M)|^2 dx_M`` by building the product circuit symbolically,
+``integrate(multiply(c, conjugate(c)), scope=M)`` (cirkit/symbolic/functional.py:161-258 integrate, :259-593 multiply),
+and evaluating ALL of it: every fold of ``c`` becomes a fold with ``K^2`` units per row.  Here every fold of ``c`` falls, for
+the set ``M`` of a call, into one of three classes (`fold_classes`):
+
+* OBSERVED -- its scope does not meet ``M``: the value of its product fold is the outer product of the ``K`` outputs of
+  ``c``'s own forward with their conjugates; never materialised, lifted while it is read (kind RANK-1);
+* INTEGRATED -- its scope lies inside ``M``: the value does not depend on the row and is what the partition-function
+  circuit (`functional.squared_partition_plan`) computes for that fold once, at batch 1 (kind CONST);
+* MIXED -- its scope meets both: only these folds are evaluated at ``K^2`` units per row, by `ck_squared_mixed_fwd`
+  (cirkit_amd/csrc/ck_sqmar.hip; kind FULL), one launch per layer of ``c`` that has any.
+
+Input folds have one variable and are never mixed, so the leaf layer of the product circuit is never materialised.
+
+Out of scope: per-row masks (the class of a fold is a property of the call), complex parameter tensors, sampling from
+squared circuits, posteriors over all states of a variable (``C`` calls of `conditional_log_prob` do it), fusing ``c``'s
+forward with the mixed pass, and a backward.
+"""
+
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Mapping
+
+import numpy as np
+import torch
+
+from . import _capi as capi
+from .plan import Plan, resolve_fold_index
+
+OBSERVED, INTEGRATED, MIXED = 0, 1, 2
+_INPUTS = ("embedding", "categorical", "gaussian")
+_CHUNK_BYTES = 2 << 30  # c's arena + the mixed arena of one chunk of rows
+
+
+def check_squarable(plan: Plan) -> None:
+    """What `HipSquaredCircuit` refuses about a plan, before anything is allocated."""
+    for l in plan.layers:
+        if l.inputs is None and (l.scope_idx is None or l.scope_idx.shape[1] != 1):
+            raise NotImplementedError("HipSquaredCircuit: input layers over several variables")
+        if l.inputs is None and l.type not in _INPUTS:
+            raise NotImplementedError(f"HipSquaredCircuit: squaring {l.type!r} input layers")
+        if l.inputs is not None and not (l.type in ("hadamard", "cpt") or (l.type == "sum" and l.arity == 1)):
+            raise NotImplementedError(f"HipSquaredCircuit: squaring {l.type!r} layers of arity {l.arity}")
+
+
+def fold_classes(plan: Plan, mask: np.ndarray) -> list[np.ndarray]:
+    """Per layer of ``c`` the class of every fold -- OBSERVED (scope disjoint from the integrated set), INTEGRATED (scope
+    inside it) or MIXED -- for the ``(D,)`` bool mask of integrated variables; bottom-up from the input layers' variables."""
+    folds = [l.num_folds for l in plan.layers]
+    cls: list[np.ndarray] = []
+    for l in plan.layers:
+        if l.inputs is None:
+            cls.append(np.where(mask[np.asarray(l.scope_idx[:, 0], dtype=np.int64)], INTEGRATED, OBSERVED).astype(np.int8))
+            continue
+        ch = resolve_fold_index(l.inputs, folds)  # (F, H, 2)
+        c = np.stack([np.asarray([cls[int(p)][int(f)] for p, f in row], dtype=np.int8) for row in ch])
+        cls.append(np.where((c == OBSERVED).all(1), OBSERVED, np.where((c == INTEGRATED).all(1), INTEGRATED, MIXED)).astype(np.int8))
+    return cls
+
+
+@dataclass
+class MixedLayer:
+    """The launch of one layer of ``c``: its evaluated folds, and per (fold, child) the kind and where the child lives --
+    ``(layer of c, fold)`` for RANK-1 and CONST children, ``(layer of c, position among that layer's evaluated folds)`` for FULL."""
+
+    layer: int
+    folds: np.ndarray  # (n,) folds of the layer, ascending
+    kind: np.ndarray  # (n, H) CK_SQ_*
+    src: np.ndarray  # (n, H, 2)
+
+
+@dataclass
+class MixedPlan:
+    classes: list[np.ndarray]
+    layers: list[MixedLayer]
+    root: tuple[int, int, int]  # (class of the output fold, layer, fold -- or position among the evaluated folds when MIXED)
+    dev: dict = field(default_factory=dict)  # batch size -> device tables
+
+    @property
+    def num_mixed(self) -> int:
+        return int(sum(len(m.folds) for m in self.layers))
+
+
+def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None) -> MixedPlan:
+    """Which folds a call with this mask evaluates at K^2 units, layer by layer in plan order, and the kind tables of their
+    children.  `const_available(layer)`: whether the partition-function circuit keeps that layer's squared output in memory;
+    an INTEGRATED child without one is evaluated here like a mixed fold (from CONST children: still exact)."""
+    folds = [l.num_folds for l in plan.layers]
+    cls = fold_classes(plan, mask)
+    children = [None if l.inputs is None else resolve_fold_index(l.inputs, folds) for l in plan.layers]
+    need = [set(np.nonzero(c == MIXED)[0].tolist()) for c in cls]
+    for i in range(len(plan.layers) - 1, -1, -1):  # (children sit below their readers)
+        if children[i] is None:
+            continue
+        for f in sorted(need[i]):
+            for p, g in children[i][f]:
+                p, g = int(p), int(g)
+                if cls[p][g] == INTEGRATED and const_available is not None and not const_available(p):
+                    if plan.layers[p].inputs is None:
+                        raise NotImplementedError("HipSquaredCircuit: the partition-function circuit keeps no value of an input layer")
+                    need[p].add(g)
+    out: list[MixedLayer] = []
+    pos: list[dict[int, int]] = [{} for _ in plan.layers]
+    for i, l in enumerate(plan.layers):
+        if not need[i]:
+            continue
+        fs = np.asarray(sorted(need[i]), dtype=np.int64)
+        pos[i] = {int(f): j for j, f in enumerate(fs)}
+        kind = np.zeros((len(fs), l.arity), dtype=np.int32)
+        src = np.zeros((len(fs), l.arity, 2), dtype=np.int64)
+        for j, f in enumerate(fs):
+            for h, (p, g) in enumerate(children[i][f]):
+                p, g = int(p), int(g)
+                if g in pos[p]:
+                    kind[j, h], src[j, h] = capi.CK_SQ_FULL, (p, pos[p][g])
+                elif cls[p][g] == OBSERVED:
+                    kind[j, h], src[j, h] = capi.CK_SQ_RANK1, (p, g)
+                else:
+                    kind[j, h], src[j, h] = capi.CK_SQ_CONST, (p, g)
+        out.append(MixedLayer(i, fs, kind, src))
+    op, of = (int(v) for v in resolve_fold_index(plan.output, folds).reshape(-1, 2)[0])
+    rc = int(cls[op][of])
+    return MixedPlan(cls, out, (rc, op, pos[op][of] if rc == MIXED else of))
+
+
+def _mask_of(integrate_vars, D: int, what: str = "marginalize") -> np.ndarray:
+    """``(D,)`` bool numpy mask from an iterable of ids or a ``(D,)`` / ``(1, D)`` bool tensor (worded as
+    `HipCircuit._apply_integration_mask` words its errors)."""
+    if integrate_vars is None:
+        return np.zeros(D, dtype=bool)
+    if isinstance(integrate_vars, (torch.Tensor, np.ndarray)):
+        m = torch.as_tensor(integrate_vars)
+        if m.dtype != torch.bool:
+            raise ValueError(f"Expected dtype of tensor to be torch.bool, got {m.dtype}")
+        if m.dim() == 1:
+            m = m.unsqueeze(0)
+        if m.dim() != 2 or m.shape[1] != D:
+            raise ValueError(f"Circuit scope has {D} variables but integrate_vars was defined over "
+                             f"{m.shape[-1] if m.dim() else 0} != {D} variables")
+        if m.shape[0] != 1:
+            raise ValueError("HipSquaredCircuit takes ONE scope to integrate over per call (a (D,) or (1, D) mask): "
+                             "which folds are mixed is a property of the call")
+        return np.ascontiguousarray(m[0].cpu().numpy())
+    ids = sorted({int(v) for v in integrate_vars})
+    if ids and (ids[0] < 0 or ids[-1] >= D):
+        raise ValueError(f"The variables to {what} must be a subset of the circuit scope")
+    mask = np.zeros(D, dtype=bool)
+    mask[ids] = True
+    return mask
+
+
+class HipSquaredCircuit:
+    """``p(x) = |c(x)|^2 / Z`` for a circuit ``c`` of Embedding / Categorical / Gaussian inputs (one variable each), Hadamard
+    products and dense sums (as such or fused into CP-T layers) with REAL parameter tensors: `log_partition`, `log_prob`,
+    `log_marginal` and `conditional_log_prob`, all exact.
+
+    It owns a `HipCircuit` of ``c`` that materialises every fold (no cross-layer fusion; unit counts padded to 32 where
+    `HipCircuit` pads them), a `HipCircuit` of the partition function over the same parameter store, and the fold classes
+    of the masks it has seen.  Refused (``NotImplementedError``, before anything is allocated): complex parameter tensors,
+    layers `functional.squared_partition_plan` refuses (Tucker, Kronecker, dense sums of arity > 1), input layers over several
+    variables.  Not offered: per-row masks, sampling, posteriors over all states of a variable (``C`` calls of
+    `conditional_log_prob`), a backward; ``c``'s forward and the mixed pass are separate launches."""
+
+    def __init__(self, plan_c: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0", rows_per_block: int = 1) -> None:
+        from .circuit import HipCircuit
+        from .functional import squared_partition_plan
+
+        if plan_c.semiring not in ("complex-lse-sum", "lse-sum"):
+            raise NotImplementedError(f"HipSquaredCircuit: semiring {plan_c.semiring!r}")
+        for n in plan_c.tensors:
+            v = tensors[n]
+            if np.iscomplexobj(v) or (hasattr(v, "is_complex") and v.is_complex()):
+                raise NotImplementedError("HipSquaredCircuit: complex parameter tensors")
+        check_squarable(plan_c)
+        squared_partition_plan(plan_c)  # (whatever else it refuses, refused here)
+        self.device = torch.device(device)
+        self.rows_per_block = int(rows_per_block)
+        self.c = HipCircuit(plan_c, tensors, device=self.device, fuse=False)
+        if self.c._virtual or self.c._clin is not None or self.c._cp_leftover or self.c._cp_subset:
+            raise RuntimeError("HipSquaredCircuit: the circuit of c does not materialise every fold")
+        self.plan = self.c.plan  # (padded where HipCircuit pads)
+        z_plan, self._z_of = squared_partition_plan(self.plan, return_layer_map=True)
+        self.z = HipCircuit(z_plan, self.c.store, device=self.device)
+        self._complex = self.plan.semiring == "complex-lse-sum"
+        self._esize = 8 if self._complex else 4
+        self._cache: dict[bytes, MixedPlan] = {}
+        self._z_state = None
+        self._z_bd = None
+        self.last_launches = 0  # launches of `ck_squared_mixed_fwd` in the last call of `log_marginal`
+
+    @property
+    def num_variables(self) -> int:
+        return self.plan.num_variables
+
+    # -- the partition function ------------------------------------------------------------------------------------------------
+    def _z_binding(self):
+        """The binding of the partition-function circuit at batch 1 with current values (re-evaluated when a parameter changed)."""
+        state = (self.c.store.version, self.c.store.state())
+        if self._z_bd is None or self._z_state != state:
+            self._z_bd = self.z._run(None)
+            self._z_state = state
+        return self._z_bd
+
+    def _root_of_z(self) -> torch.Tensor:
+        bd = self._z_binding()
+        p, f = (int(v) for v in self.z._out_pairs[0])
+        v = bd.views[p][f, 0, 0]
+        return (v.real if self._complex else v).to(torch.float32)
+
+    def log_partition(self) -> torch.Tensor:
+        """``log Z`` (0-d fp32)."""
+        return self._root_of_z().clone()
+
+    def log_prob(self, x: torch.Tensor) -> torch.Tensor:
+        """``(B,)``: ``2 Re log c(x) - log Z``."""
+        y = self.c(x)[:, 0, 0]
+        return 2 * (y.real if self._complex else y).to(torch.float32) - self._root_of_z()
+
+    # -- marginals ---------------------------------------------------------------------------------------------------------------
+    def classify(self, integrate_vars) -> MixedPlan:
+        """The fold classes and launch tables of a mask (cached by mask)."""
+        mask = _mask_of(integrate_vars, self.plan.num_variables)
+        key = mask.tobytes()
+        mp = self._cache.get(key)
+        if mp is None:
+            if len(self._cache) >= 16:
+                self._cache.pop(next(iter(self._cache)))
+            self._z_binding()
+            views = self._z_bd.views
+            mp = self._cache[key] = mixed_plan(self.plan, mask, lambda p: views[self._z_of[p]] is not None)
+        return mp
+
+    def _row_bytes(self, mp: MixedPlan) -> int:
+        """Bytes per row of c's arena plus the mixed arena (with the shape-generic form's block between the stages)."""
+        n = sum(l.num_folds * l.num_output_units for l in self.plan.layers)
+        for m in mp.layers:
+            l = self.plan.layers[m.layer]
+            ko = l.num_input_units if l.type == "hadamard" else l.num_output_units
+            n += len(m.folds) * (ko * ko + (0 if self._special(l) else l.num_input_units * l.num_output_units))
+        return n * self._esize
+
+    @staticmethod
+    def _special(l) -> bool:
+        return l.type == "hadamard" or (l.num_input_units == 32 and l.num_output_units in (1, 32))
+
+    def rows_per_chunk(self, integrate_vars=None) -> int:
+        """How many rows one chunk of `log_marginal` holds by default: c's arena plus the mixed arena at or below 2 GiB."""
+        return max(1, _CHUNK_BYTES // self._row_bytes(self.classify(integrate_vars)))
+
+    def _tables(self, mp: MixedPlan, B: int, bd_c, bd_z):
+        """Device tables of a mask at batch size B: per launch (kind, off, wfold), the mixed arena's layout."""
+        key = (B, bd_c.arena.data_ptr(), bd_z.arena.data_ptr())
+        hit = mp.dev.get(B)
+        if hit is not None and hit["key"] == key:
+            return hit
+        bases, total, mid = {}, 0, 0
+        for m in mp.layers:
+            l = self.plan.layers[m.layer]
+            ko = l.num_input_units if l.type == "hadamard" else l.num_output_units
+            bases[m.layer] = (total, ko * ko)
+            total += (len(m.folds) * B * ko * ko + 3) // 4 * 4
+            if not self._special(l):
+                mid = max(mid, len(m.folds) * B * l.num_input_units * l.num_output_units)
+        launches = []
+        for m in mp.layers:
+            l = self.plan.layers[m.layer]
+            K = l.num_input_units
+            off = np.zeros(m.kind.shape, dtype=np.int64)
+            for j in range(m.kind.shape[0]):
+                for h in range(m.kind.shape[1]):
+                    p, g = int(m.src[j, h, 0]), int(m.src[j, h, 1])
+                    kd = int(m.kind[j, h])
+                    if kd == capi.CK_SQ_FULL:
+                        if bases[p][1] != K * K:
+                            raise ValueError("a layer's children do not all have its number of input units")
+                        off[j, h] = bases[p][0] + g * B * K * K
+                    elif kd == capi.CK_SQ_RANK1:
+                        off[j, h] = bd_c.views[p].storage_offset() + g * B * K
+                    else:
+                        off[j, h] = bd_z.views[self._z_of[p]].storage_offset() + g * K * K
+            launches.append(dict(
+                layer=m.layer, n=len(m.folds), H=l.arity, Ki=K, Ko=l.num_output_units, stages=0 if l.type == "hadamard" else 2,
+                base=bases[m.layer][0], kind=torch.from_numpy(np.ascontiguousarray(m.kind)).to(self.device),
+                off=torch.from_numpy(off).to(self.device), wfold=torch.from_numpy(m.folds.astype(np.int32)).to(self.device)))
+        dt = torch.complex64 if self._complex else torch.float32
+        hit = mp.dev[B] = dict(key=key, launches=launches, arena=torch.empty(max(total, 1), dtype=dt, device=self.device),
+                               mid=torch.empty(mid, dtype=dt, device=self.device) if mid else None)
+        if len(mp.dev) > 2:
+            mp.dev.pop(next(iter(mp.dev)))
+        return hit
+
+    def _chunk(self, x: torch.Tensor, mp: MixedPlan) -> torch.Tensor:
+        """Unnormalised log marginal of the (cleaned) rows x."""
+        B = int(x.shape[0])
+        rc, rl, rf = mp.root
+        if rc == INTEGRATED:
+            return self._root_of_z().expand(B).clone()
+        bd_c = self.c._run(x)
+        if rc == OBSERVED:
+            y = bd_c.views[rl][rf, :, 0]
+            return 2 * (y.real if self._complex else y).to(torch.float32)
+        bd_z = self._z_binding()
+        tb = self._tables(mp, B, bd_c, bd_z)
+        arena, mid = tb["arena"], tb["mid"]
+        esz = self._esize
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            for la in tb["launches"]:
+                w1 = w2 = None
+                if la["stages"]:
+                    zl = self._z_of[la["layer"]]
+                    w1, w2 = self.z.layers[zl - 1]._w, self.z.layers[zl]._w
+                    for w in (w1, w2):
+                        if w is None or w.dtype != torch.float32 or not w.is_contiguous() \
+                                or tuple(w.shape[-2:]) != (la["Ko"], la["Ki"]):
+                            raise NotImplementedError("HipSquaredCircuit: sum weights that are not real (F, Ko, Ki) blocks")
+                capi.call("ck_squared_mixed_fwd", arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(), la["kind"].data_ptr(),
+                          la["off"].data_ptr(), la["H"], None if w1 is None else w1.data_ptr(), None if w2 is None else w2.data_ptr(),
+                          la["wfold"].data_ptr(), None if mid is None else mid.data_ptr(), arena.data_ptr() + la["base"] * esz,
+                          la["n"], B, la["Ki"], la["Ko"], la["stages"], self.rows_per_block, 1 if self._complex else 0, stream)
+                self.last_launches += 1
+        last = tb["launches"][-1]
+        if last["layer"] != rl:
+            raise RuntimeError("HipSquaredCircuit: the output fold is not in the last evaluated layer")
+        ko2 = last["Ko"] ** 2 if last["stages"] else last["Ki"] ** 2
+        y = arena[last["base"]: last["base"] + last["n"] * B * ko2].view(last["n"], B, ko2)[rf, :, 0]
+        return (y.real if self._complex else y).to(torch.float32).clone()
+
+    def log_marginal(self, x: torch.Tensor, integrate_vars=None, *, normalized: bool = True, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B,)`` fp32: ``log integral of |c(x_O, x_M)|^2 dx_M`` over the variables ``M = integrate_vars`` (an iterable of
+        ids or a ``(D,)`` / ``(1, D)`` bool mask; one mask per call), minus ``log Z`` when `normalized`.  Entries of ``x`` at
+        integrated variables are ignored; a negative entry (NaN for Gaussian inputs) at an OBSERVED variable makes that row
+        NaN.  With no mixed fold -- nothing or everything integrated -- nothing beyond ``c``'s forward / the partition function
+        is launched.  `rows_per_chunk`: rows evaluated at a time (default: c's arena plus the mixed arena within 2 GiB); the
+        results do not depend on it."""
+        D = self.plan.num_variables
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
+        mp = self.classify(integrate_vars)
+        mask = torch.from_numpy(_mask_of(integrate_vars, D)).to(self.device)
+        x = x.to(self.device)
+        floating = self.c._float_input
+        x = x.to(torch.float32 if floating else torch.int64)
+        absent = torch.isnan(x) if floating else x < 0
+        bad = (absent & ~mask).any(dim=1)
+        x = torch.where(mask | absent, torch.zeros((), dtype=x.dtype, device=self.device), x)
+        B = int(x.shape[0])
+        step = int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // self._row_bytes(mp))
+        if step <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+        self.last_launches = 0
+        out = torch.empty(B, dtype=torch.float32, device=self.device)
+        for r0 in range(0, B, step):
+            out[r0: r0 + step] = self._chunk(x[r0: r0 + step].contiguous(), mp)
+        if normalized:
+            out = out - self._root_of_z()
+        return torch.where(bad, torch.full((), float("nan"), device=self.device), out)
+
+    def conditional_log_prob(self, x: torch.Tensor, query_vars, integrate_vars=None, *, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B,)``: ``log p(x_Q | x_O)`` with ``M = integrate_vars`` integrated out and ``O`` the rest:
+        ``log_marginal(x, M) - log_marginal(x, M + Q)``, both unnormalised."""
+        D = self.plan.num_variables
+        m = _mask_of(integrate_vars, D)
+        q = _mask_of(query_vars, D, "query")
+        if not q.any():
+            raise ValueError("conditional_log_prob needs at least one query variable")
+        if (q & m).any():
+            raise ValueError("a query variable cannot be integrated out")
+        num = self.log_marginal(x, torch.from_numpy(m), normalized=False, rows_per_chunk=rows_per_chunk)
+        den = self.log_marginal(x, torch.from_numpy(m | q), normalized=False, rows_per_chunk=rows_per_chunk)
+        return num - den

@@ -1542,6 +1542,32 @@ int ck_soft_decode_leaf(int mode, const int64_t* entries, const int32_t* qstart,
                         int C_max, const float* log_lik, const int32_t* node, int64_t row0, int64_t B, int D, uint64_t seed,
                         void* x, int x_float, void* stream);
 
+/* ---- marginals of squared circuits ("Marginals of squared circuits"; additive, ABI 51) ----------------
+ * The MIXED folds of the product circuit c (x) conj(c) under a set M of integrated variables: what the reference evaluates as
+ * integrate(multiply(c, conjugate(c)), scope=M) (symbolic/functional.py:161-258 integrate, :259-593 multiply) with the
+ * Kronecker-weighted sums split into TensorDot pairs (optimization/layers.py:90-127, 282-422), for the n folds of ONE layer of
+ * c whose scope meets M and its complement, B rows:
+ *     out[f, b, :] = TD2(TD1(sum_h lift(child[f, h])))
+ * the sum over the H children is the Hadamard product in log space; TD1 contracts the slow factor of the (Ki, Ki) block with
+ * w1[wfold[f]] (Ko, Ki) and TD2 the other one with w2[wfold[f]] (ck_tensordot2_lse_fwd's two stages, the same arithmetic and
+ * order of sums; real fp32 weights of the whole layer, row-major).  stages = 0: a Hadamard layer of c, out (n, B, Ki^2) is the
+ * product itself and w1 / w2 / wfold / mid are not read; stages = 2: a dense sum (H = 1) or CP-T layer, out (n, B, Ko^2).
+ * Child (f, h) is kind[f H + h] at element offset off[f H + h] (elements of the value type):
+ *     CK_SQ_FULL   Ki^2 values per row in `full`, at off + b Ki^2  (an earlier launch of this query; `out` lies in the same buffer)
+ *     CK_SQ_CONST  Ki^2 values without a row stride in `cst`       (the partition-function circuit, evaluated once at batch 1)
+ *     CK_SQ_RANK1  Ki values y per row in `rank1`, at off + b Ki   (c's own forward); unit k Ki + l reads y_k + conj(y_l)
+ * unit k Ki + l pairs unit k of c (slow) with unit l of conj(c), the order of the Gram layers of the partition function.
+ * complex_values: 0 fp32 under lse-sum (the lift is y_k + y_l), 1 complex64 under complex-lse-sum.  Shapes: Ki = Ko = 32 and
+ * the root Ki = 32, Ko = 1 take specialised forms (weights staged once per workgroup, rows_per_block rows walked by it; the
+ * root one row); every other shape takes the shape-generic form, which hands the block between the stages through
+ * mid (n, B, Ki Ko) -- required then -- and is refused with CK_ERR_UNSUPPORTED where a stage does not fit in LDS.  n <= 65535. */
+#define CK_SQ_FULL 0
+#define CK_SQ_CONST 1
+#define CK_SQ_RANK1 2
+int ck_squared_mixed_fwd(const float* full, const float* cst, const float* rank1, const int32_t* kind, const int64_t* off, int H,
+                         const float* w1, const float* w2, const int32_t* wfold, float* mid, float* out, int n, int B, int Ki, int Ko,
+                         int stages, int rows_per_block, int complex_values, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
