@@ -14,8 +14,11 @@ the set ``M`` of a call, into one of three classes (`fold_classes`):
 
 Input folds have one variable and are never mixed, so the leaf layer of the product circuit is never materialised.
 
-Out of scope: per-row masks (the class of a fold is a property of the call), complex parameter tensors, sampling from
-squared circuits, posteriors over all states of a variable (``C`` calls of `conditional_log_prob` do it), fusing ``c``'s
+Sampling and the posterior of one variable over all its states walk the other way, from the root down to one input fold
+(cirkit_amd/squared_sampling.py: `sample`, `sample_conditional`, `state_log_marginals`, `posterior`), and read the folds beside
+that path by the same three kinds.
+
+Out of scope: per-row masks (the class of a fold is a property of the call), complex parameter tensors, fusing ``c``'s
 forward with the mixed pass, and a backward.
 """
 
@@ -84,20 +87,29 @@ class MixedPlan:
         return int(sum(len(m.folds) for m in self.layers))
 
 
-def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None) -> MixedPlan:
+def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None) -> MixedPlan:
     """Which folds a call with this mask evaluates at K^2 units, layer by layer in plan order, and the kind tables of their
     children.  `const_available(layer)`: whether the partition-function circuit keeps that layer's squared output in memory;
-    an INTEGRATED child without one is evaluated here like a mixed fold (from CONST children: still exact)."""
+    an INTEGRATED child without one is evaluated here like a mixed fold (from CONST children: still exact).  `path`: a set of
+    ``(layer, fold)`` that needs no value -- the ancestry of one variable, walked downwards by `squared_sampling` -- but whose
+    other children do; the root of the result is then not looked up among the evaluated folds."""
     folds = [l.num_folds for l in plan.layers]
     cls = fold_classes(plan, mask)
     children = [None if l.inputs is None else resolve_fold_index(l.inputs, folds) for l in plan.layers]
     need = [set(np.nonzero(c == MIXED)[0].tolist()) for c in cls]
+    path = path or set()
+    on_path: list[set] = [set() for _ in plan.layers]
+    for i, f in path:
+        need[i].discard(f)
+        on_path[i].add(f)
     for i in range(len(plan.layers) - 1, -1, -1):  # (children sit below their readers)
         if children[i] is None:
             continue
-        for f in sorted(need[i]):
+        for f in sorted(need[i] | on_path[i]):
             for p, g in children[i][f]:
                 p, g = int(p), int(g)
+                if (p, g) in path:
+                    continue
                 if cls[p][g] == INTEGRATED and const_available is not None and not const_available(p):
                     if plan.layers[p].inputs is None:
                         raise NotImplementedError("HipSquaredCircuit: the partition-function circuit keeps no value of an input layer")
@@ -123,7 +135,7 @@ def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None) -> MixedPlan:
         out.append(MixedLayer(i, fs, kind, src))
     op, of = (int(v) for v in resolve_fold_index(plan.output, folds).reshape(-1, 2)[0])
     rc = int(cls[op][of])
-    return MixedPlan(cls, out, (rc, op, pos[op][of] if rc == MIXED else of))
+    return MixedPlan(cls, out, (rc, op, pos[op][of] if rc == MIXED and (op, of) not in path else of))
 
 
 def _mask_of(integrate_vars, D: int, what: str = "marginalize") -> np.ndarray:
@@ -161,8 +173,9 @@ class HipSquaredCircuit:
     `HipCircuit` pads them), a `HipCircuit` of the partition function over the same parameter store, and the fold classes
     of the masks it has seen.  Refused (``NotImplementedError``, before anything is allocated): complex parameter tensors,
     layers `functional.squared_partition_plan` refuses (Tucker, Kronecker, dense sums of arity > 1), input layers over several
-    variables.  Not offered: per-row masks, sampling, posteriors over all states of a variable (``C`` calls of
-    `conditional_log_prob`), a backward; ``c``'s forward and the mixed pass are separate launches."""
+    variables.  `sample`, `sample_conditional`, `state_log_marginals` and `posterior` (exact too; discrete inputs and region
+    graphs that are trees) refuse Gaussian inputs and DAG ancestries.  Not offered: per-row masks, a backward; ``c``'s forward
+    and the mixed pass are separate launches."""
 
     def __init__(self, plan_c: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0", rows_per_block: int = 1) -> None:
         from .circuit import HipCircuit
@@ -190,6 +203,8 @@ class HipSquaredCircuit:
         self._z_state = None
         self._z_bd = None
         self.last_launches = 0  # launches of `ck_squared_mixed_fwd` in the last call of `log_marginal`
+        self.last_mixed_launches = 0  # ... in the last call of `state_log_marginals` / `posterior` / `sample` / `sample_conditional`
+        self._sampler = None
 
     @property
     def num_variables(self) -> int:
@@ -250,9 +265,10 @@ class HipSquaredCircuit:
         """How many rows one chunk of `log_marginal` holds by default: c's arena plus the mixed arena at or below 2 GiB."""
         return max(1, _CHUNK_BYTES // self._row_bytes(self.classify(integrate_vars)))
 
-    def _tables(self, mp: MixedPlan, B: int, bd_c, bd_z):
-        """Device tables of a mask at batch size B: per launch (kind, off, wfold), the mixed arena's layout."""
-        key = (B, bd_c.arena.data_ptr(), bd_z.arena.data_ptr())
+    def _tables(self, mp: MixedPlan, B: int, bd_c, bd_z, alloc: bool = True):
+        """Device tables of a mask at batch size B: per launch (kind, off, wfold), the mixed arena's layout (`alloc` False:
+        its sizes in values, `total` and `mid_size`, for a caller that brings the buffers)."""
+        key = (B, bd_c.arena.data_ptr(), bd_z.arena.data_ptr(), alloc)  # (an entry without buffers never serves a caller that needs them)
         hit = mp.dev.get(B)
         if hit is not None and hit["key"] == key:
             return hit
@@ -286,11 +302,34 @@ class HipSquaredCircuit:
                 base=bases[m.layer][0], kind=torch.from_numpy(np.ascontiguousarray(m.kind)).to(self.device),
                 off=torch.from_numpy(off).to(self.device), wfold=torch.from_numpy(m.folds.astype(np.int32)).to(self.device)))
         dt = torch.complex64 if self._complex else torch.float32
-        hit = mp.dev[B] = dict(key=key, launches=launches, arena=torch.empty(max(total, 1), dtype=dt, device=self.device),
-                               mid=torch.empty(mid, dtype=dt, device=self.device) if mid else None)
+        hit = mp.dev[B] = dict(key=key, launches=launches, total=max(total, 1), mid_size=mid,
+                               arena=torch.empty(max(total, 1), dtype=dt, device=self.device) if alloc else None,
+                               mid=torch.empty(mid, dtype=dt, device=self.device) if mid and alloc else None)
         if len(mp.dev) > 2:
             mp.dev.pop(next(iter(mp.dev)))
         return hit
+
+    def _stage_weights(self, layer: int, Ko: int, Ki: int):
+        """The real (F, Ko, Ki) weight blocks of the two TensorDot stages of a sum / CP-T layer of ``c``."""
+        zl = self._z_of[layer]
+        w1, w2 = self.z.layers[zl - 1]._w, self.z.layers[zl]._w
+        for w in (w1, w2):
+            if w is None or w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape[-2:]) != (Ko, Ki):
+                raise NotImplementedError("HipSquaredCircuit: sum weights that are not real (F, Ko, Ki) blocks")
+        return w1, w2
+
+    def _launch_mixed(self, launches, arena, mid, bd_c, bd_z, B: int) -> int:
+        """The launches of `_tables` into `arena`, in order; how many there were."""
+        esz = self._esize
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            for la in launches:
+                w1, w2 = self._stage_weights(la["layer"], la["Ko"], la["Ki"]) if la["stages"] else (None, None)
+                capi.call("ck_squared_mixed_fwd", arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(), la["kind"].data_ptr(),
+                          la["off"].data_ptr(), la["H"], None if w1 is None else w1.data_ptr(), None if w2 is None else w2.data_ptr(),
+                          la["wfold"].data_ptr(), None if mid is None else mid.data_ptr(), arena.data_ptr() + la["base"] * esz,
+                          la["n"], B, la["Ki"], la["Ko"], la["stages"], self.rows_per_block, 1 if self._complex else 0, stream)
+        return len(launches)
 
     def _chunk(self, x: torch.Tensor, mp: MixedPlan) -> torch.Tensor:
         """Unnormalised log marginal of the (cleaned) rows x."""
@@ -304,24 +343,8 @@ class HipSquaredCircuit:
             return 2 * (y.real if self._complex else y).to(torch.float32)
         bd_z = self._z_binding()
         tb = self._tables(mp, B, bd_c, bd_z)
-        arena, mid = tb["arena"], tb["mid"]
-        esz = self._esize
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            for la in tb["launches"]:
-                w1 = w2 = None
-                if la["stages"]:
-                    zl = self._z_of[la["layer"]]
-                    w1, w2 = self.z.layers[zl - 1]._w, self.z.layers[zl]._w
-                    for w in (w1, w2):
-                        if w is None or w.dtype != torch.float32 or not w.is_contiguous() \
-                                or tuple(w.shape[-2:]) != (la["Ko"], la["Ki"]):
-                            raise NotImplementedError("HipSquaredCircuit: sum weights that are not real (F, Ko, Ki) blocks")
-                capi.call("ck_squared_mixed_fwd", arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(), la["kind"].data_ptr(),
-                          la["off"].data_ptr(), la["H"], None if w1 is None else w1.data_ptr(), None if w2 is None else w2.data_ptr(),
-                          la["wfold"].data_ptr(), None if mid is None else mid.data_ptr(), arena.data_ptr() + la["base"] * esz,
-                          la["n"], B, la["Ki"], la["Ko"], la["stages"], self.rows_per_block, 1 if self._complex else 0, stream)
-                self.last_launches += 1
+        arena = tb["arena"]
+        self.last_launches += self._launch_mixed(tb["launches"], arena, tb["mid"], bd_c, bd_z, B)
         last = tb["launches"][-1]
         if last["layer"] != rl:
             raise RuntimeError("HipSquaredCircuit: the output fold is not in the last evaluated layer")
@@ -372,3 +395,55 @@ class HipSquaredCircuit:
         num = self.log_marginal(x, torch.from_numpy(m), normalized=False, rows_per_chunk=rows_per_chunk)
         den = self.log_marginal(x, torch.from_numpy(m | q), normalized=False, rows_per_chunk=rows_per_chunk)
         return num - den
+
+    # -- all states of one variable, sampling (cirkit_amd/squared_sampling.py) ---------------------------------------------------
+    def state_log_marginals(self, x: torch.Tensor, var: int, integrate_vars=None, *, normalized: bool = True,
+                            rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, C)`` fp32: ``log integral of |c(x_O, X_var = s, x_M)|^2 dx_M`` for every state ``s`` of `var` at once, minus
+        ``log Z`` when `normalized` -- row ``b``, column ``s`` is ``log_marginal`` of row ``b`` with ``x_var = s``, from ONE launch
+        on top of ``c``'s forward (and the mixed launches of the folds beside the path of `var`, `last_mixed_launches`).
+        `integrate_vars` as in `log_marginal`, without `var`.  The entry of ``x`` at `var` is ignored; a negative entry at an
+        observed variable makes the row NaN.  ``NotImplementedError`` for Gaussian inputs and for a variable whose ancestry
+        is not a path (a DAG region graph).
+
+        Accuracy: a state is a sum of ``K^2`` signed terms in fp32 and is accurate to about 1e-5 OF ITS ROW'S LARGEST STATE,
+        not of itself -- all a sampler or a normalised posterior needs, but the LOGARITHM of a state that holds ``e^-g`` of the
+        largest has a relative error of about ``e^g 1e-5``: within ``1e-4 |log m|`` down to ``e^-4`` of the largest, unreliable
+        below about ``e^-6`` (most states of a 256-state posterior on real images).  Where the logarithm of such a state
+        matters, take `log_marginal` with ``x_var = s``, one call per state ("Sampling squared circuits")."""
+        from .squared_sampling import state_log_marginals
+
+        return state_log_marginals(self, x, var, integrate_vars, normalized=normalized, rows_per_chunk=rows_per_chunk)
+
+    def posterior(self, x: torch.Tensor, var: int, integrate_vars=None, *, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, C)``: ``log p(X_var = s | x_O)`` with `integrate_vars` integrated out: `state_log_marginals` normalised over
+        ``s``, with its accuracy: the probabilities are right to about 1e-5 absolute, so the logarithm of a state far below the
+        most probable one (``e^-6`` of it or less) is not; `conditional_log_prob`, one call per state, is there for those."""
+        from .squared_sampling import posterior
+
+        return posterior(self, x, var, integrate_vars, rows_per_chunk=rows_per_chunk)
+
+    def sample(self, num_samples: int, *, seed: int | None = None, order=None, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(N, D)`` int64 exact samples of ``p(x) = |c(x)|^2 / Z``, one variable after the other: `order` (a permutation of
+        the variables; default `squared_sampling.tree_order`, in which a step is ``c``'s forward plus one launch and
+        `last_mixed_launches` stays 0).  `seed`: the 64-bit Philox key (None: drawn from torch's CPU generator); the draw of
+        variable v in row n takes counter (n, global fold id of v's input fold), so the samples depend on the seed and the
+        order only: not on `rows_per_chunk` or `rows_per_block`.  Nothing waits for the device between the steps."""
+        from .squared_sampling import sample
+
+        return sample(self, num_samples, seed=seed, order=order, rows_per_chunk=rows_per_chunk)
+
+    def sample_conditional(self, x: torch.Tensor, sample_vars, *, seed: int | None = None, order=None,
+                           rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, D)`` int64: the variables `sample_vars` (the forms `integrate_vars` takes; one set per call) of every row drawn
+        exactly from ``p(x_S | x_O)``; observed entries are returned untouched.  `order`: a permutation of the sampled
+        variables (``ValueError`` otherwise; default `tree_order` restricted to them).  An entry at a sampled variable is
+        ignored whatever it holds.  A row whose evidence has no mass gets -1 in every sampled column.
+
+        DIFFERENT from `HipCircuit.sample_conditional`: there a negative entry of ``x`` marks, row by row, one more variable to
+        draw.  Here the sampled set is ONE per call (which folds are mixed is a property of the call), so a negative entry at
+        a variable outside `sample_vars` cannot be drawn as well: it is absent evidence, and that row gets -1 in every sampled
+        column (its other entries come back as given).  To draw it, put the variable into `sample_vars`."""
+        from .squared_sampling import sample_conditional
+
+        return sample_conditional(self, x, sample_vars, seed=seed, order=order, rows_per_chunk=rows_per_chunk)

@@ -1568,6 +1568,35 @@ int ck_squared_mixed_fwd(const float* full, const float* cst, const float* rank1
                          const float* w1, const float* w2, const int32_t* wfold, float* mid, float* out, int n, int B, int Ki, int Ko,
                          int stages, int rows_per_block, int complex_values, void* stream);
 
+/* ---- sampling squared circuits ("Sampling squared circuits"; additive, ABI 51) ------------------------
+ * One step of the autoregressive sampler of p(x) = |c(x)|^2 / Z for B rows: the derivative G of the root of the product circuit
+ * c (x) conj(c) with respect to the K^2 squared units of the input fold of ONE variable v, walked from the root down the L
+ * ancestors of that fold, then log m_b(s) = log sum_kl G_b[k][l] a_k(s) conj(a_l(s)) for ALL C states of v -- what the reference
+ * obtains from C evaluations of integrate(multiply(c, conjugate(c)), scope=M) (symbolic/functional.py:161-258, :259-593), one per
+ * state -- and, on request, a draw from it.  At a sum / CP-T ancestor (forward O = W P W^T) the gradient of the Hadamard product P
+ * is W^T G W: the two TensorDot stages of ck_squared_mixed_fwd with the weight matrices read transposed, same order of sums; the
+ * gradient of the child on the path is that plus, in log space, the values of the other children.
+ * levels (device) / levels_host (the same words on the host: shapes and kinds are checked before the launch): L rows of
+ * CK_SQ_PATH_LEVEL_WORDS + 2 max_siblings int64 words, root first:
+ *     [0] CK_SQ_PATH_STAGES if the fold has the two stages (a sum or CP-T layer), else 0 (a Hadamard layer: Ki = Ko)
+ *     [1] weight fold  [2] Ki  [3] Ko  [4] [5] device addresses of the layer's two (F, Ko, Ki) fp32 weight tensors
+ *     [6] the number n of siblings  [7] 0   then n pairs (kind, element offset) read as ck_squared_mixed_fwd reads a child
+ * The top fold is read at unit 0 (G = log 1 there).  table: the input layer's (F, C + 1, K) fp32 table, fold leaf_fold; table_log:
+ * 1 a table of logarithms (Categorical), 0 of linear values (Embedding).  log_m (B, C) fp32, optional: log m_b(s), shifted by the
+ * maximum real part of G, the real part of the quadratic form clamped at 0 before the logarithm (-inf, not NaN).  x_out non-null:
+ * the draw -- inverse CDF over the C states, u = philox_uniform(x0) of philox4x32_10(row0 + b, node, 0, 0, seed) (ck_philox.h; node:
+ * the global fold id of the input fold) -- is written to column var of x_out (B, D) and, for c's next forward, of x (a failed draw:
+ * -1 in x_out, 0 in x); a row with dead[b] != 0, or whose weights are all zero or hold a NaN, draws -1 and sets dead[b].  A path of
+ * 32 units with one output unit at the root takes the register form; every other shape the LDS form, refused with
+ * CK_ERR_UNSUPPORTED where it does not fit.  A workgroup walks rows_per_block rows one after the other and stages every level's
+ * weights again for each: rows_per_block only changes the grid (no reuse of staged weights); results do not depend on it. */
+#define CK_SQ_PATH_LEVEL_WORDS 8
+#define CK_SQ_PATH_STAGES 1
+int ck_squared_path_bwd(const float* full, const float* cst, const float* rank1, const int64_t* levels_host, const int64_t* levels, int L,
+                        int max_siblings, const float* table, int64_t leaf_fold, int C, int K, int table_log, float* log_m, int64_t* x,
+                        int64_t* x_out, int32_t* dead, int D, int var, int node, uint64_t seed, int64_t row0, int B, int rows_per_block,
+                        int complex_values, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
