@@ -16,10 +16,11 @@ Input folds have one variable and are never mixed, so the leaf layer of the prod
 
 Sampling and the posterior of one variable over all its states walk the other way, from the root down to one input fold
 (cirkit_amd/squared_sampling.py: `sample`, `sample_conditional`, `state_log_marginals`, `posterior`), and read the folds beside
-that path by the same three kinds.
+that path by the same three kinds.  The posteriors of a whole SET of variables keep that walk for every fold above the set,
+layer by layer (cirkit_amd/squared_posterior.py: `query_log_marginals`, `posterior_marginals`).
 
 Out of scope: per-row masks (the class of a fold is a property of the call), complex parameter tensors, fusing ``c``'s
-forward with the mixed pass, and a backward.
+forward with the mixed pass, and a backward beyond those walks (no gradients with respect to parameters).
 """
 
 from __future__ import annotations
@@ -87,12 +88,13 @@ class MixedPlan:
         return int(sum(len(m.folds) for m in self.layers))
 
 
-def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None) -> MixedPlan:
+def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None, readers=None) -> MixedPlan:
     """Which folds a call with this mask evaluates at K^2 units, layer by layer in plan order, and the kind tables of their
     children.  `const_available(layer)`: whether the partition-function circuit keeps that layer's squared output in memory;
     an INTEGRATED child without one is evaluated here like a mixed fold (from CONST children: still exact).  `path`: a set of
     ``(layer, fold)`` that needs no value -- the ancestry of one variable, walked downwards by `squared_sampling` -- but whose
-    other children do; the root of the result is then not looked up among the evaluated folds."""
+    other children do; the root of the result is then not looked up among the evaluated folds.  `readers`: a set of
+    ``(layer, fold)`` whose children are read as well (the down folds of `squared_posterior`) while they keep their own class."""
     folds = [l.num_folds for l in plan.layers]
     cls = fold_classes(plan, mask)
     children = [None if l.inputs is None else resolve_fold_index(l.inputs, folds) for l in plan.layers]
@@ -101,6 +103,8 @@ def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None) ->
     on_path: list[set] = [set() for _ in plan.layers]
     for i, f in path:
         need[i].discard(f)
+        on_path[i].add(f)
+    for i, f in readers or ():
         on_path[i].add(f)
     for i in range(len(plan.layers) - 1, -1, -1):  # (children sit below their readers)
         if children[i] is None:
@@ -174,8 +178,9 @@ class HipSquaredCircuit:
     of the masks it has seen.  Refused (``NotImplementedError``, before anything is allocated): complex parameter tensors,
     layers `functional.squared_partition_plan` refuses (Tucker, Kronecker, dense sums of arity > 1), input layers over several
     variables.  `sample`, `sample_conditional`, `state_log_marginals` and `posterior` (exact too; discrete inputs and region
-    graphs that are trees) refuse Gaussian inputs and DAG ancestries.  Not offered: per-row masks, a backward; ``c``'s forward
-    and the mixed pass are separate launches."""
+    graphs that are trees) refuse Gaussian inputs and DAG ancestries; so do `query_log_marginals` and `posterior_marginals`,
+    the posteriors of a whole set of query variables from one pass down the folds above them.  Not offered: per-row masks,
+    leave-one-out conditionals, gradients with respect to parameters; ``c``'s forward and the mixed pass are separate launches."""
 
     def __init__(self, plan_c: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0", rows_per_block: int = 1) -> None:
         from .circuit import HipCircuit
@@ -205,6 +210,9 @@ class HipSquaredCircuit:
         self.last_launches = 0  # launches of `ck_squared_mixed_fwd` in the last call of `log_marginal`
         self.last_mixed_launches = 0  # ... in the last call of `state_log_marginals` / `posterior` / `sample` / `sample_conditional`
         self._sampler = None
+        self._down_plans: dict = {}  # (Q, I) -> `squared_posterior.DownPlan`
+        self.last_down_launches = 0  # launches of `ck_squared_down_bwd` and `ck_squared_down_leaf` in the last call of
+        #                              `query_log_marginals` / `posterior_marginals` (their mixed launches: `last_mixed_launches`)
 
     @property
     def num_variables(self) -> int:
@@ -422,6 +430,34 @@ class HipSquaredCircuit:
         from .squared_sampling import posterior
 
         return posterior(self, x, var, integrate_vars, rows_per_chunk=rows_per_chunk)
+
+    # -- all states of every query variable at once (cirkit_amd/squared_posterior.py) -----------------------------------------------
+    def query_log_marginals(self, x: torch.Tensor, query_vars, integrate_vars=None, *, normalized: bool = True,
+                            return_log_evidence: bool = False, rows_per_chunk: int | None = None):
+        """``(B, |Q|, C)`` fp32: for every query variable ``v`` (the ``Q`` axis in ascending variable order) and every state ``s``,
+        ``log integral of |c(x_O, X_v = s, x_{M - v})|^2`` with ``M = Q + integrate_vars`` integrated out and ``O`` the rest observed
+        -- what `state_log_marginals(x, v, M - v)` returns, for all of ``Q`` from ONE pass down the folds above ``Q`` on top of
+        ``c``'s forward and the mixed launches (`last_mixed_launches`, `last_down_launches`) -- minus ``log Z`` when `normalized`.
+        ``C`` is the largest number of states among the query variables; columns past a variable's own count are ``-inf``.
+        `return_log_evidence`: also ``(B,)`` `log_marginal(x, Q + integrate_vars)` with the same `normalized` (the root of the
+        mixed pass: it costs nothing).  `query_vars` / `integrate_vars` in the forms `log_marginal` takes, one set each per call;
+        entries of ``x`` at ``M`` are ignored, a negative entry at an observed variable makes the row NaN.  ``ValueError`` for an
+        empty ``Q`` or one that meets `integrate_vars`; ``NotImplementedError`` for Gaussian inputs and DAG ancestries, as
+        `state_log_marginals`, whose accuracy it shares: right to about 1e-5 of the row's largest state.  The results do not
+        depend on `rows_per_chunk` or `rows_per_block`."""
+        from .squared_posterior import query_log_marginals
+
+        return query_log_marginals(self, x, query_vars, integrate_vars, normalized=normalized, return_log_evidence=return_log_evidence,
+                                   rows_per_chunk=rows_per_chunk)
+
+    def posterior_marginals(self, x: torch.Tensor, query_vars, integrate_vars=None, *, return_log_evidence: bool = False,
+                            rows_per_chunk: int | None = None):
+        """``(B, |Q|, C)``: ``log p(X_v = s | x_O)`` for every ``v`` in `query_vars` with the other query variables and
+        `integrate_vars` integrated out: `query_log_marginals` normalised over ``s`` per ``(b, v)``, in log space like `posterior`
+        (and with its accuracy).  `return_log_evidence`: also ``(B,)`` ``log p(x_O)``."""
+        from .squared_posterior import posterior_marginals
+
+        return posterior_marginals(self, x, query_vars, integrate_vars, return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
 
     def sample(self, num_samples: int, *, seed: int | None = None, order=None, rows_per_chunk: int | None = None) -> torch.Tensor:
         """``(N, D)`` int64 exact samples of ``p(x) = |c(x)|^2 / Z``, one variable after the other: `order` (a permutation of

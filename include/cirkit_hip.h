@@ -1597,6 +1597,36 @@ int ck_squared_path_bwd(const float* full, const float* cst, const float* rank1,
                         int64_t* x_out, int32_t* dead, int D, int var, int node, uint64_t seed, int64_t row0, int B, int rows_per_block,
                         int complex_values, void* stream);
 
+/* ---- posterior marginals of squared circuits ("Posterior marginals of squared circuits"; additive, ABI 51)
+ * The walk of ck_squared_path_bwd layer by layer, for EVERY fold whose scope meets a set Q of query variables (the down folds):
+ * one call per layer of c that has down folds, from the output layer downwards.  For each of the n down folds of the layer and B
+ * rows it reads the fold's derivative G (Ko^2 values per row in `down`), applies the two transposed TensorDot stages where the
+ * layer has them (stages = 2: dP = W^T G W with w1 / w2 (num_weight_folds, Ko, Ki), same arithmetic and order of sums as the path
+ * launch; stages = 0, a Hadamard layer: Ki = Ko, dP = G), and writes for every child slot h that is a down fold itself
+ *     G_child[b, :] = dP (+) sum over h' != h of value(h')     (log space; Ki^2 values per row in `down`)
+ * with the other children read by kind as ck_squared_mixed_fwd reads them (H - 1 reads in slot order, no subtraction).
+ * folds (device) / folds_host (the same words on the host, checked before the launch): n rows of CK_SQ_DOWN_FOLD_WORDS + 3 H int64:
+ *     [0] weight fold  [1] element offset of the fold's G in `down`, or -1: the output fold, G = log 1 at unit 0, -inf elsewhere
+ *     then H triples (element offset of the child's G in `down` or -1: not a down fold, kind, element offset of the child's value)
+ * down_elems: the size of `down` in elements of the value type; every G must lie inside.  Ki = 32 with Ko = 32, or Ko = 1 on the
+ * output fold, or no stages, takes the register form; every other shape the LDS form, refused with CK_ERR_UNSUPPORTED where it does
+ * not fit.  A workgroup takes one fold and rows_per_block rows one after the other; results do not depend on it.  H <= 8. */
+#define CK_SQ_DOWN_FOLD_WORDS 2
+int ck_squared_down_bwd(const float* full, const float* cst, const float* rank1, float* down, int64_t down_elems, const int64_t* folds_host,
+                        const int64_t* folds, int n, int H, const float* w1, const float* w2, int num_weight_folds, int Ki, int Ko,
+                        int stages, int B, int rows_per_block, int complex_values, void* stream);
+
+/* The leaves of that walk: log_m (B, nq, C_max) fp32, row b, query variable q, state s = log sum_kl G_b^q[k][l] a_k(s) conj(a_l(s)),
+ * the leaf form of ck_squared_path_bwd (shifted by the maximum real part of G, the real part clamped at 0 before the logarithm, a
+ * table of logarithms shifted state by state); columns past a variable's own C are -inf.  vars / vars_host: nq rows of
+ * CK_SQ_DOWN_LEAF_WORDS int64:
+ *     [0] device address of the variable's (C + 1, K) fp32 table  [1] C  [2] K  [3] 1 a table of logarithms, 0 linear values
+ *     [4] element offset of the G of its input fold in `down`, or -1 (the input fold is the output fold)  [5] 0
+ * One workgroup per (variable, row). */
+#define CK_SQ_DOWN_LEAF_WORDS 6
+int ck_squared_down_leaf(const float* down, int64_t down_elems, const int64_t* vars_host, const int64_t* vars, int nq, int C_max,
+                         float* log_m, int B, int complex_values, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
