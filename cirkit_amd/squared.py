@@ -32,9 +32,9 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .plan import Plan, resolve_fold_index
+from .plan import Plan
+from .squared_graph import INTEGRATED, MIXED, OBSERVED, FoldGraph, graph_of
 
-OBSERVED, INTEGRATED, MIXED = 0, 1, 2
 _INPUTS = ("embedding", "categorical", "gaussian")
 _CHUNK_BYTES = 2 << 30  # c's arena + the mixed arena of one chunk of rows
 
@@ -50,19 +50,18 @@ def check_squarable(plan: Plan) -> None:
             raise NotImplementedError(f"HipSquaredCircuit: squaring {l.type!r} layers of arity {l.arity}")
 
 
-def fold_classes(plan: Plan, mask: np.ndarray) -> list[np.ndarray]:
+def put_bounded(cache: dict, key, value, capacity: int):
+    """`value` into `cache`, which then drops its oldest entries beyond `capacity`."""
+    cache[key] = value
+    while len(cache) > capacity:
+        cache.pop(next(iter(cache)))
+    return value
+
+
+def fold_classes(plan: Plan, mask: np.ndarray, graph: FoldGraph | None = None) -> list[np.ndarray]:
     """Per layer of ``c`` the class of every fold -- OBSERVED (scope disjoint from the integrated set), INTEGRATED (scope
-    inside it) or MIXED -- for the ``(D,)`` bool mask of integrated variables; bottom-up from the input layers' variables."""
-    folds = [l.num_folds for l in plan.layers]
-    cls: list[np.ndarray] = []
-    for l in plan.layers:
-        if l.inputs is None:
-            cls.append(np.where(mask[np.asarray(l.scope_idx[:, 0], dtype=np.int64)], INTEGRATED, OBSERVED).astype(np.int8))
-            continue
-        ch = resolve_fold_index(l.inputs, folds)  # (F, H, 2)
-        c = np.stack([np.asarray([cls[int(p)][int(f)] for p, f in row], dtype=np.int8) for row in ch])
-        cls.append(np.where((c == OBSERVED).all(1), OBSERVED, np.where((c == INTEGRATED).all(1), INTEGRATED, MIXED)).astype(np.int8))
-    return cls
+    inside it) or MIXED -- for the ``(D,)`` bool mask of integrated variables, from the variables under each fold."""
+    return graph_of(plan, graph).classes(mask)
 
 
 @dataclass
@@ -88,16 +87,15 @@ class MixedPlan:
         return int(sum(len(m.folds) for m in self.layers))
 
 
-def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None, readers=None) -> MixedPlan:
+def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None, readers=None, graph: FoldGraph | None = None) -> MixedPlan:
     """Which folds a call with this mask evaluates at K^2 units, layer by layer in plan order, and the kind tables of their
     children.  `const_available(layer)`: whether the partition-function circuit keeps that layer's squared output in memory;
     an INTEGRATED child without one is evaluated here like a mixed fold (from CONST children: still exact).  `path`: a set of
     ``(layer, fold)`` that needs no value -- the ancestry of one variable, walked downwards by `squared_sampling` -- but whose
     other children do; the root of the result is then not looked up among the evaluated folds.  `readers`: a set of
     ``(layer, fold)`` whose children are read as well (the down folds of `squared_posterior`) while they keep their own class."""
-    folds = [l.num_folds for l in plan.layers]
-    cls = fold_classes(plan, mask)
-    children = [None if l.inputs is None else resolve_fold_index(l.inputs, folds) for l in plan.layers]
+    graph = graph_of(plan, graph)
+    cls, children = graph.classes(mask), graph.children
     need = [set(np.nonzero(c == MIXED)[0].tolist()) for c in cls]
     path = path or set()
     on_path: list[set] = [set() for _ in plan.layers]
@@ -137,9 +135,48 @@ def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None, re
                 else:
                     kind[j, h], src[j, h] = capi.CK_SQ_CONST, (p, g)
         out.append(MixedLayer(i, fs, kind, src))
-    op, of = (int(v) for v in resolve_fold_index(plan.output, folds).reshape(-1, 2)[0])
+    op, of = graph.top
     rc = int(cls[op][of])
     return MixedPlan(cls, out, (rc, op, pos[op][of] if rc == MIXED and (op, of) not in path else of))
+
+
+@dataclass
+class MixedLaunch:
+    """One launch of `ck_squared_mixed_fwd` at a batch size: its counts, where its output starts in the mixed arena, its tables."""
+
+    layer: int
+    n: int
+    H: int
+    Ki: int
+    Ko: int
+    stages: int
+    base: int
+    kind: torch.Tensor
+    off: torch.Tensor
+    wfold: torch.Tensor
+
+    @property
+    def units2(self) -> int:
+        """Squared units per row of an evaluated fold."""
+        return (self.Ko if self.stages else self.Ki) ** 2
+
+
+@dataclass
+class MixedTables:
+    """The launches of a (mask, batch size) and the mixed arena they fill (`arena` / `mid` None: a caller brings buffers of
+    `total` / `mid_size` values)."""
+
+    key: tuple
+    launches: list[MixedLaunch]
+    where: dict[tuple[int, int], int]  # (layer, fold) -> offset of its block in the mixed arena
+    total: int
+    mid_size: int
+    arena: torch.Tensor | None
+    mid: torch.Tensor | None
+
+    def offset(self, layer: int, fold: int) -> int | None:
+        """Where the mixed pass wrote fold `fold` of layer `layer`, or None: it did not evaluate it."""
+        return self.where.get((layer, fold))
 
 
 def _mask_of(integrate_vars, D: int, what: str = "marginalize") -> np.ndarray:
@@ -210,6 +247,7 @@ class HipSquaredCircuit:
         self.last_launches = 0  # launches of `ck_squared_mixed_fwd` in the last call of `log_marginal`
         self.last_mixed_launches = 0  # ... in the last call of `state_log_marginals` / `posterior` / `sample` / `sample_conditional`
         self._sampler = None
+        self.graph = FoldGraph(self.plan)
         self._down_plans: dict = {}  # (Q, I) -> `squared_posterior.DownPlan`
         self.last_down_launches = 0  # launches of `ck_squared_down_bwd` and `ck_squared_down_leaf` in the last call of
         #                              `query_log_marginals` / `posterior_marginals` (their mixed launches: `last_mixed_launches`)
@@ -249,20 +287,20 @@ class HipSquaredCircuit:
         key = mask.tobytes()
         mp = self._cache.get(key)
         if mp is None:
-            if len(self._cache) >= 16:
-                self._cache.pop(next(iter(self._cache)))
-            self._z_binding()
-            views = self._z_bd.views
-            mp = self._cache[key] = mixed_plan(self.plan, mask, lambda p: views[self._z_of[p]] is not None)
+            mp = put_bounded(self._cache, key, mixed_plan(self.plan, mask, self._const_available(), graph=self.graph), 16)
         return mp
+
+    def _const_available(self):
+        """`mixed_plan`'s test of a layer: whether the partition-function circuit keeps its squared output in memory."""
+        views = self._z_binding().views
+        return lambda p: views[self._z_of[p]] is not None
 
     def _row_bytes(self, mp: MixedPlan) -> int:
         """Bytes per row of c's arena plus the mixed arena (with the shape-generic form's block between the stages)."""
         n = sum(l.num_folds * l.num_output_units for l in self.plan.layers)
         for m in mp.layers:
             l = self.plan.layers[m.layer]
-            ko = l.num_input_units if l.type == "hadamard" else l.num_output_units
-            n += len(m.folds) * (ko * ko + (0 if self._special(l) else l.num_input_units * l.num_output_units))
+            n += len(m.folds) * (self.graph.units(l) ** 2 + (0 if self._special(l) else l.num_input_units * l.num_output_units))
         return n * self._esize
 
     @staticmethod
@@ -273,49 +311,48 @@ class HipSquaredCircuit:
         """How many rows one chunk of `log_marginal` holds by default: c's arena plus the mixed arena at or below 2 GiB."""
         return max(1, _CHUNK_BYTES // self._row_bytes(self.classify(integrate_vars)))
 
-    def _tables(self, mp: MixedPlan, B: int, bd_c, bd_z, alloc: bool = True):
-        """Device tables of a mask at batch size B: per launch (kind, off, wfold), the mixed arena's layout (`alloc` False:
-        its sizes in values, `total` and `mid_size`, for a caller that brings the buffers)."""
+    def child(self, p: int, g: int, K: int, B: int, cls: int, tb: MixedTables | None, bd_c, bd_z) -> tuple[int, int]:
+        """(kind, element offset) of fold `g` of layer `p`, of class `cls`, read at `K` units and batch size `B` by a launch of any
+        of the queries: FULL in the mixed arena of `tb` where the mixed pass evaluated it, else RANK-1 in c's arena where it is
+        OBSERVED, else CONST in the arena of the partition-function circuit."""
+        if self.graph.units(self.plan.layers[p]) != K:
+            raise ValueError("a layer's children do not all have its number of input units")
+        off = None if tb is None else tb.offset(p, g)
+        if off is not None:
+            return capi.CK_SQ_FULL, off
+        if cls == OBSERVED:
+            return capi.CK_SQ_RANK1, bd_c.views[p].storage_offset() + g * B * K
+        return capi.CK_SQ_CONST, bd_z.views[self._z_of[p]].storage_offset() + g * K * K
+
+    def _tables(self, mp: MixedPlan, B: int, bd_c, bd_z, alloc: bool = True) -> MixedTables:
+        """Device tables of a mask at batch size B: per launch (kind, off, wfold), and the mixed arena's layout."""
         key = (B, bd_c.arena.data_ptr(), bd_z.arena.data_ptr(), alloc)  # (an entry without buffers never serves a caller that needs them)
         hit = mp.dev.get(B)
-        if hit is not None and hit["key"] == key:
+        if hit is not None and hit.key == key:
             return hit
-        bases, total, mid = {}, 0, 0
-        for m in mp.layers:
-            l = self.plan.layers[m.layer]
-            ko = l.num_input_units if l.type == "hadamard" else l.num_output_units
-            bases[m.layer] = (total, ko * ko)
-            total += (len(m.folds) * B * ko * ko + 3) // 4 * 4
-            if not self._special(l):
-                mid = max(mid, len(m.folds) * B * l.num_input_units * l.num_output_units)
-        launches = []
-        for m in mp.layers:
-            l = self.plan.layers[m.layer]
-            K = l.num_input_units
-            off = np.zeros(m.kind.shape, dtype=np.int64)
-            for j in range(m.kind.shape[0]):
-                for h in range(m.kind.shape[1]):
-                    p, g = int(m.src[j, h, 0]), int(m.src[j, h, 1])
-                    kd = int(m.kind[j, h])
-                    if kd == capi.CK_SQ_FULL:
-                        if bases[p][1] != K * K:
-                            raise ValueError("a layer's children do not all have its number of input units")
-                        off[j, h] = bases[p][0] + g * B * K * K
-                    elif kd == capi.CK_SQ_RANK1:
-                        off[j, h] = bd_c.views[p].storage_offset() + g * B * K
-                    else:
-                        off[j, h] = bd_z.views[self._z_of[p]].storage_offset() + g * K * K
-            launches.append(dict(
-                layer=m.layer, n=len(m.folds), H=l.arity, Ki=K, Ko=l.num_output_units, stages=0 if l.type == "hadamard" else 2,
-                base=bases[m.layer][0], kind=torch.from_numpy(np.ascontiguousarray(m.kind)).to(self.device),
-                off=torch.from_numpy(off).to(self.device), wfold=torch.from_numpy(m.folds.astype(np.int32)).to(self.device)))
         dt = torch.complex64 if self._complex else torch.float32
-        hit = mp.dev[B] = dict(key=key, launches=launches, total=max(total, 1), mid_size=mid,
-                               arena=torch.empty(max(total, 1), dtype=dt, device=self.device) if alloc else None,
-                               mid=torch.empty(mid, dtype=dt, device=self.device) if mid and alloc else None)
-        if len(mp.dev) > 2:
-            mp.dev.pop(next(iter(mp.dev)))
-        return hit
+        tb = MixedTables(key, [], {}, 0, 0, None, None)
+        for m in mp.layers:
+            l = self.plan.layers[m.layer]
+            ko2 = self.graph.units(l) ** 2
+            tb.where.update(((m.layer, int(f)), tb.total + j * B * ko2) for j, f in enumerate(m.folds))
+            tb.total += (len(m.folds) * B * ko2 + 3) // 4 * 4
+            if not self._special(l):
+                tb.mid_size = max(tb.mid_size, len(m.folds) * B * l.num_input_units * l.num_output_units)
+        for m in mp.layers:
+            l = self.plan.layers[m.layer]
+            rows = [[self.child(p, g, l.num_input_units, B, mp.classes[p][g], tb, bd_c, bd_z) for p, g in self.graph.children[m.layer][f].tolist()]
+                    for f in m.folds]
+            kind, off = np.asarray(rows, dtype=np.int64).reshape(len(m.folds), l.arity, 2).transpose(2, 0, 1)
+            tb.launches.append(MixedLaunch(
+                m.layer, len(m.folds), l.arity, l.num_input_units, l.num_output_units, 0 if l.type == "hadamard" else 2, tb.where[(m.layer, int(m.folds[0]))],
+                torch.from_numpy(np.ascontiguousarray(kind, dtype=np.int32)).to(self.device), torch.from_numpy(np.ascontiguousarray(off)).to(self.device),
+                torch.from_numpy(m.folds.astype(np.int32)).to(self.device)))
+        tb.total = max(tb.total, 1)
+        if alloc:
+            tb.arena = torch.empty(tb.total, dtype=dt, device=self.device)
+            tb.mid = torch.empty(tb.mid_size, dtype=dt, device=self.device) if tb.mid_size else None
+        return put_bounded(mp.dev, B, tb, 2)
 
     def _stage_weights(self, layer: int, Ko: int, Ki: int):
         """The real (F, Ko, Ki) weight blocks of the two TensorDot stages of a sum / CP-T layer of ``c``."""
@@ -332,11 +369,11 @@ class HipSquaredCircuit:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
             for la in launches:
-                w1, w2 = self._stage_weights(la["layer"], la["Ko"], la["Ki"]) if la["stages"] else (None, None)
-                capi.call("ck_squared_mixed_fwd", arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(), la["kind"].data_ptr(),
-                          la["off"].data_ptr(), la["H"], None if w1 is None else w1.data_ptr(), None if w2 is None else w2.data_ptr(),
-                          la["wfold"].data_ptr(), None if mid is None else mid.data_ptr(), arena.data_ptr() + la["base"] * esz,
-                          la["n"], B, la["Ki"], la["Ko"], la["stages"], self.rows_per_block, 1 if self._complex else 0, stream)
+                w1, w2 = self._stage_weights(la.layer, la.Ko, la.Ki) if la.stages else (None, None)
+                capi.call("ck_squared_mixed_fwd", arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(), la.kind.data_ptr(),
+                          la.off.data_ptr(), la.H, None if w1 is None else w1.data_ptr(), None if w2 is None else w2.data_ptr(),
+                          la.wfold.data_ptr(), None if mid is None else mid.data_ptr(), arena.data_ptr() + la.base * esz,
+                          la.n, B, la.Ki, la.Ko, la.stages, self.rows_per_block, 1 if self._complex else 0, stream)
         return len(launches)
 
     def _chunk(self, x: torch.Tensor, mp: MixedPlan) -> torch.Tensor:
@@ -351,14 +388,43 @@ class HipSquaredCircuit:
             return 2 * (y.real if self._complex else y).to(torch.float32)
         bd_z = self._z_binding()
         tb = self._tables(mp, B, bd_c, bd_z)
-        arena = tb["arena"]
-        self.last_launches += self._launch_mixed(tb["launches"], arena, tb["mid"], bd_c, bd_z, B)
-        last = tb["launches"][-1]
-        if last["layer"] != rl:
+        self.last_launches += self._launch_mixed(tb.launches, tb.arena, tb.mid, bd_c, bd_z, B)
+        return self._mixed_root(tb, mp, B).clone()
+
+    def _mixed_root(self, tb: MixedTables, mp: MixedPlan, B: int) -> torch.Tensor:
+        """(B,) fp32: the MIXED output fold as the last launch of the mixed pass left it -- the unnormalised log evidence."""
+        last, (_, rl, rf) = tb.launches[-1], mp.root
+        if last.layer != rl:
             raise RuntimeError("HipSquaredCircuit: the output fold is not in the last evaluated layer")
-        ko2 = last["Ko"] ** 2 if last["stages"] else last["Ki"] ** 2
-        y = arena[last["base"]: last["base"] + last["n"] * B * ko2].view(last["n"], B, ko2)[rf, :, 0]
-        return (y.real if self._complex else y).to(torch.float32).clone()
+        y = tb.arena[last.base: last.base + last.n * B * last.units2].view(last.n, B, last.units2)[rf, :, 0]
+        return (y.real if self._complex else y).to(torch.float32)
+
+    def _clean(self, x: torch.Tensor, ignored: np.ndarray) -> tuple[torch.Tensor, torch.Tensor]:
+        """x on the device -- fp32 for Gaussian inputs, else int64 -- with 0 where it is ignored or absent (NaN for Gaussian
+        inputs, else negative); (B,) bool: the rows with an absent OBSERVED entry."""
+        D = self.plan.num_variables
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
+        floating = self.c._float_input
+        x = x.to(self.device).to(torch.float32 if floating else torch.int64)
+        mask = torch.from_numpy(ignored).to(self.device)
+        absent = torch.isnan(x) if floating else x < 0
+        return torch.where(mask | absent, torch.zeros((), dtype=x.dtype, device=self.device), x).contiguous(), (absent & ~mask).any(dim=1)
+
+    @staticmethod
+    def _chunk_rows(rows_per_chunk, row_bytes) -> int:
+        """Rows evaluated at a time: as asked, else what `row_bytes()` bytes per row let into 2 GiB."""
+        step = int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // row_bytes())
+        if step <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+        return step
+
+    def _leaf_table(self, layer: int) -> tuple[torch.Tensor, int, int, int]:
+        """(table, C, K, 1 for a table of logarithms) of an input layer of ``c`` -- after c's forward, which builds the tables."""
+        table = self.c.layers[layer]._table
+        if table.dtype != torch.float32 or not table.is_contiguous():
+            raise NotImplementedError("HipSquaredCircuit: an input table that is not real fp32")
+        return table, int(table.shape[1]) - 1, int(table.shape[2]), 1 if self.plan.layers[layer].type == "categorical" else 0
 
     def log_marginal(self, x: torch.Tensor, integrate_vars=None, *, normalized: bool = True, rows_per_chunk: int | None = None) -> torch.Tensor:
         """``(B,)`` fp32: ``log integral of |c(x_O, x_M)|^2 dx_M`` over the variables ``M = integrate_vars`` (an iterable of
@@ -368,24 +434,16 @@ class HipSquaredCircuit:
         is launched.  `rows_per_chunk`: rows evaluated at a time (default: c's arena plus the mixed arena within 2 GiB); the
         results do not depend on it."""
         D = self.plan.num_variables
-        if x.dim() != 2 or x.shape[1] != D:
+        if x.dim() != 2 or x.shape[1] != D:  # (before a mask is refused)
             raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
         mp = self.classify(integrate_vars)
-        mask = torch.from_numpy(_mask_of(integrate_vars, D)).to(self.device)
-        x = x.to(self.device)
-        floating = self.c._float_input
-        x = x.to(torch.float32 if floating else torch.int64)
-        absent = torch.isnan(x) if floating else x < 0
-        bad = (absent & ~mask).any(dim=1)
-        x = torch.where(mask | absent, torch.zeros((), dtype=x.dtype, device=self.device), x)
+        x, bad = self._clean(x, _mask_of(integrate_vars, D))
         B = int(x.shape[0])
-        step = int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // self._row_bytes(mp))
-        if step <= 0:
-            raise ValueError("rows_per_chunk must be positive")
+        step = self._chunk_rows(rows_per_chunk, lambda: self._row_bytes(mp))
         self.last_launches = 0
         out = torch.empty(B, dtype=torch.float32, device=self.device)
         for r0 in range(0, B, step):
-            out[r0: r0 + step] = self._chunk(x[r0: r0 + step].contiguous(), mp)
+            out[r0: r0 + step] = self._chunk(x[r0: r0 + step], mp)
         if normalized:
             out = out - self._root_of_z()
         return torch.where(bad, torch.full((), float("nan"), device=self.device), out)

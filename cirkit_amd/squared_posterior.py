@@ -28,8 +28,9 @@ import torch
 
 from . import _capi as capi
 from .plan import Plan
-from .squared import INTEGRATED, MIXED, OBSERVED, _CHUNK_BYTES, MixedPlan, _mask_of, mixed_plan
-from .squared_sampling import _children, _output_fold, _readers, path_plan, sampler, scope_bits
+from .squared import INTEGRATED, MIXED, MixedPlan, MixedTables, _mask_of, mixed_plan, put_bounded
+from .squared_graph import FoldGraph, graph_of
+from .squared_sampling import sampler
 
 _HEAD = capi.CK_SQ_DOWN_FOLD_WORDS
 _LEAF = capi.CK_SQ_DOWN_LEAF_WORDS
@@ -53,36 +54,55 @@ class DownPlan:
     top: tuple[int, int]  # the output fold
     layers: list[DownLayer]  # output layer first
     leaves: list[tuple[int, int]]  # per query variable, the input fold that reads it
-    dev: dict = field(default_factory=dict)  # batch size -> bound tables
+    dev: dict = field(default_factory=dict)  # batch size -> `DownTables`
 
 
-def host_plan(plan: Plan, qvars, mask: np.ndarray, const_available=None, readers=None, bits=None) -> DownPlan:
+@dataclass
+class DownLaunch:
+    """One launch of `ck_squared_down_bwd` at a batch size: the fold rows on the host and on the device, counts, weights."""
+
+    layer: int
+    host: np.ndarray
+    dev: torch.Tensor
+    n: int
+    H: int
+    Ki: int
+    Ko: int
+    stages: int
+    w1: torch.Tensor | None
+    w2: torch.Tensor | None
+
+
+@dataclass
+class DownTables:
+    key: tuple
+    launches: list[DownLaunch]
+    total: int  # values of the down arena
+    vars_host: np.ndarray  # the variable rows of the leaf launch
+    vars_dev: torch.Tensor
+
+
+def host_plan(plan: Plan, qvars, mask: np.ndarray, const_available=None, graph: FoldGraph | None = None) -> DownPlan:
     """The down folds of the query variables `qvars`, the mixed plan of ``M`` = `mask` (which holds them) and the layers to
     launch.  ``NotImplementedError`` where `path_plan` raises it: a variable read by several input folds, a fold above a query
     variable with several readers."""
+    graph = graph_of(plan, graph)
     qvars = sorted(int(v) for v in qvars)
-    readers = _readers(plan) if readers is None else readers
-    leaves = [path_plan(plan, v, readers).leaf for v in qvars]  # (the refusals come before anything is built)
+    leaves = [graph.path(v).leaf for v in qvars]  # (the refusals come before anything is built)
     qbits = sum(1 << v for v in qvars)
-    bits = scope_bits(plan) if bits is None else bits
-    down = {(p, f) for p, row in enumerate(bits) for f, b in enumerate(row) if b & qbits}
-    mp = mixed_plan(plan, mask, const_available, readers=down)
-    children = _children(plan)
+    down = {(p, f) for p, row in enumerate(graph.bits) for f, b in enumerate(row) if b & qbits}
+    mp = mixed_plan(plan, mask, const_available, readers=down, graph=graph)
     layers = []
     for i in range(len(plan.layers) - 1, -1, -1):  # (children sit below their readers)
         fs = sorted(f for p, f in down if p == i)
-        if fs and children[i] is not None:
-            layers.append(DownLayer(i, fs, np.stack([children[i][f] for f in fs]).astype(np.int64)))
-    return DownPlan(qvars, mask, mp, down, _output_fold(plan), layers, leaves)
-
-
-def _units(l) -> int:
-    return l.num_input_units if l.type == "hadamard" else l.num_output_units
+        if fs and graph.children[i] is not None:
+            layers.append(DownLayer(i, fs, np.stack([graph.children[i][f] for f in fs]).astype(np.int64)))
+    return DownPlan(qvars, mask, mp, down, graph.top, layers, leaves)
 
 
 def down_row_values(sq, dp: DownPlan) -> int:
     """Values per row of the down arena: K^2 for every down fold but the output fold."""
-    return sum(_units(sq.plan.layers[p]) ** 2 for p, f in dp.down if (p, f) != dp.top)
+    return sum(sq.graph.units(sq.plan.layers[p]) ** 2 for p, f in dp.down if (p, f) != dp.top)
 
 
 def row_bytes(sq, dp: DownPlan) -> int:
@@ -92,7 +112,7 @@ def row_bytes(sq, dp: DownPlan) -> int:
 
 def plan_of(sq, query_vars, integrate_vars) -> DownPlan:
     """The `DownPlan` of a call, cached on (Q, I)."""
-    sm = sampler(sq)  # (Gaussian inputs are refused here)
+    sampler(sq)  # (Gaussian inputs are refused here)
     D = sq.plan.num_variables
     q = _mask_of(query_vars, D, "query")
     m = _mask_of(integrate_vars, D)
@@ -105,48 +125,31 @@ def plan_of(sq, query_vars, integrate_vars) -> DownPlan:
     if dp is None:
         qvars = np.nonzero(q)[0].tolist()
         for v in qvars:  # (the refusals come before the partition-function circuit is evaluated)
-            sm.path(v)
-        views = sq._z_binding().views
-        dp = host_plan(sq.plan, qvars, q | m, lambda p: views[sq._z_of[p]] is not None, sm.readers, sm.bits)
-        if len(sq._down_plans) >= 8:
-            sq._down_plans.pop(next(iter(sq._down_plans)))
-        sq._down_plans[key] = dp
+            sq.graph.path(v)
+        dp = put_bounded(sq._down_plans, key, host_plan(sq.plan, qvars, q | m, sq._const_available(), sq.graph), 8)
     return dp
 
 
-def _leaf_tables(sq, dp: DownPlan):
-    """Per query variable (table, C, K, table of logarithms, fold) of its input layer -- after c's forward, which builds the tables."""
-    sm = sampler(sq)
-    out = []
-    for v, (pl, fl) in zip(dp.qvars, dp.leaves):
-        table = sq.c.layers[pl]._table
-        if table.dtype != torch.float32 or not table.is_contiguous():
-            raise NotImplementedError("HipSquaredCircuit: an input table that is not real fp32")
-        if int(table.shape[1]) - 1 != sm.num_states(v):
-            raise RuntimeError(f"HipSquaredCircuit: the table of variable {v} has {int(table.shape[1]) - 1} states, its layer {sm.num_states(v)}")
-        out.append((table, int(table.shape[1]) - 1, int(table.shape[2]), 1 if sq.plan.layers[pl].type == "categorical" else 0, fl))
-    return out
-
-
-def bind(sq, dp: DownPlan, B: int, bd_c, bd_z, tb) -> dict:
+def bind(sq, dp: DownPlan, B: int, bd_c, bd_z, tb: MixedTables) -> DownTables:
     """The fold tables of every launch and the variable table of the leaf launch at batch size B, on the host and on the
     device, and the layout of the down arena.  `tb`: `sq._tables` of the mixed plan at this batch size."""
     layers = sq.plan.layers
     weights = {dl.layer: sq._stage_weights(dl.layer, layers[dl.layer].num_output_units, layers[dl.layer].num_input_units)
                for dl in dp.layers if layers[dl.layer].type != "hadamard"}
-    leaf = _leaf_tables(sq, dp)
-    key = (bd_c.arena.data_ptr(), bd_z.arena.data_ptr(), tb["arena"].data_ptr(), tuple(w.data_ptr() for ws in weights.values() for w in ws),
+    leaf = [sq._leaf_table(pl) for pl, _ in dp.leaves]  # (after c's forward, which builds the tables)
+    for v, t in zip(dp.qvars, leaf):
+        if t[1] != sq.graph.num_states(v):
+            raise RuntimeError(f"HipSquaredCircuit: the table of variable {v} has {t[1]} states, its layer {sq.graph.num_states(v)}")
+    key = (bd_c.arena.data_ptr(), bd_z.arena.data_ptr(), tb.arena.data_ptr(), tuple(w.data_ptr() for ws in weights.values() for w in ws),
            tuple(t[0].data_ptr() for t in leaf))
     hit = dp.dev.get(B)
-    if hit is not None and hit["key"] == key:
+    if hit is not None and hit.key == key:
         return hit
     off, total = {}, 0
     for p, f in sorted(dp.down):
         if (p, f) != dp.top:
             off[(p, f)] = total
-            total += (B * _units(layers[p]) ** 2 + 3) // 4 * 4
-    bases = {la["layer"]: la["base"] for la in tb["launches"]}
-    pos = {m.layer: {int(f): j for j, f in enumerate(m.folds)} for m in dp.mixed.layers}
+            total += (B * sq.graph.units(layers[p]) ** 2 + 3) // 4 * 4
     cls = dp.mixed.classes
     launches = []
     for dl in dp.layers:
@@ -156,31 +159,19 @@ def bind(sq, dp: DownPlan, B: int, bd_c, bd_z, tb) -> dict:
         for j, f in enumerate(dl.folds):
             row = host[j]
             row[0], row[1] = f, off.get((dl.layer, f), -1)
-            is_down = [(int(p), int(g)) in dp.down for p, g in dl.children[j]]
-            for h, (p, g) in enumerate(dl.children[j]):
-                p, g = int(p), int(g)
-                if _units(layers[p]) != K:
-                    raise ValueError("a layer's children do not all have its number of input units")
+            is_down = [(p, g) in dp.down for p, g in dl.children[j].tolist()]
+            for h, (p, g) in enumerate(dl.children[j].tolist()):
+                kd, o = sq.child(p, g, K, B, cls[p][g], tb, bd_c, bd_z)
                 if sum(is_down) - is_down[h] == 0:
                     kd, o = capi.CK_SQ_CONST, 0  # (no other slot is a down fold: this child's value is never read)
-                elif g in pos.get(p, {}):
-                    kd, o = capi.CK_SQ_FULL, bases[p] + pos[p][g] * B * K * K
-                elif cls[p][g] == OBSERVED:
-                    kd, o = capi.CK_SQ_RANK1, bd_c.views[p].storage_offset() + g * B * K
-                else:
-                    kd, o = capi.CK_SQ_CONST, bd_z.views[sq._z_of[p]].storage_offset() + g * K * K
                 row[_HEAD + 3 * h: _HEAD + 3 * h + 3] = (off[(p, g)] if is_down[h] else -1, kd, o)
         w1, w2 = weights.get(dl.layer, (None, None))
-        launches.append(dict(layer=dl.layer, host=host, dev=torch.from_numpy(host).to(sq.device), n=len(dl.folds), H=H, Ki=K,
-                             Ko=l.num_output_units if w1 is not None else K, stages=2 if w1 is not None else 0, w1=w1, w2=w2))
+        launches.append(DownLaunch(dl.layer, host, torch.from_numpy(host).to(sq.device), len(dl.folds), H, K,
+                                   l.num_output_units if w1 is not None else K, 2 if w1 is not None else 0, w1, w2))
     vars_host = np.zeros((len(leaf), _LEAF), dtype=np.int64)
-    for j, ((table, C, K, tlog, fl), lf) in enumerate(zip(leaf, dp.leaves)):
-        vars_host[j, :5] = (table.data_ptr() + fl * (C + 1) * K * 4, C, K, tlog, off.get(lf, -1))
-    hit = dp.dev[B] = dict(key=key, launches=launches, total=max(total, 1), vars_host=vars_host,
-                           vars_dev=torch.from_numpy(vars_host).to(sq.device))
-    if len(dp.dev) > 2:
-        dp.dev.pop(next(iter(dp.dev)))
-    return hit
+    for j, ((table, C, K, tlog), lf) in enumerate(zip(leaf, dp.leaves)):
+        vars_host[j, :5] = (table.data_ptr() + lf[1] * (C + 1) * K * 4, C, K, tlog, off.get(lf, -1))
+    return put_bounded(dp.dev, B, DownTables(key, launches, max(total, 1), vars_host, torch.from_numpy(vars_host).to(sq.device)), 2)
 
 
 def _down_arena(sq, n: int) -> torch.Tensor:
@@ -201,53 +192,44 @@ def _chunk(sq, dp: DownPlan, xw: torch.Tensor, out: torch.Tensor, ev: torch.Tens
     mark("c_forward")
     bd_z = sq._z_binding()
     tb = sq._tables(dp.mixed, B, bd_c, bd_z)
-    arena = tb["arena"]
-    sq.last_mixed_launches += sq._launch_mixed(tb["launches"], arena, tb["mid"], bd_c, bd_z, B)
+    arena = tb.arena
+    sq.last_mixed_launches += sq._launch_mixed(tb.launches, arena, tb.mid, bd_c, bd_z, B)
     mark("mixed")
-    rc, rl, rf = dp.mixed.root
+    rc = dp.mixed.root[0]
     if rc == INTEGRATED:
         ev.copy_(sq._root_of_z().expand(B))
     elif rc == MIXED:
-        last = tb["launches"][-1]
-        if last["layer"] != rl:
-            raise RuntimeError("HipSquaredCircuit: the output fold is not in the last evaluated layer")
-        ko2 = last["Ko"] ** 2 if last["stages"] else last["Ki"] ** 2
-        y = arena[last["base"]: last["base"] + last["n"] * B * ko2].view(last["n"], B, ko2)[rf, :, 0]
-        ev.copy_((y.real if sq._complex else y).to(torch.float32))
+        ev.copy_(sq._mixed_root(tb, dp.mixed, B))
     else:
         raise RuntimeError("HipSquaredCircuit: the output fold holds no query variable")
     bt = bind(sq, dp, B, bd_c, bd_z, tb)
-    down = _down_arena(sq, bt["total"])
+    down = _down_arena(sq, bt.total)
     stream = torch.cuda.current_stream(sq.device).cuda_stream
     cplx = 1 if sq._complex else 0
     with torch.cuda.device(sq.device):
-        for la in bt["launches"]:
+        for la in bt.launches:
             capi.call("ck_squared_down_bwd", arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(), down.data_ptr(), down.numel(),
-                      la["host"].ctypes.data, la["dev"].data_ptr(), la["n"], la["H"], None if la["w1"] is None else la["w1"].data_ptr(),
-                      None if la["w2"] is None else la["w2"].data_ptr(), 0 if la["w1"] is None else int(la["w1"].shape[0]), la["Ki"],
-                      la["Ko"], la["stages"], B, sq.rows_per_block, cplx, stream)
+                      la.host.ctypes.data, la.dev.data_ptr(), la.n, la.H, None if la.w1 is None else la.w1.data_ptr(),
+                      None if la.w2 is None else la.w2.data_ptr(), 0 if la.w1 is None else int(la.w1.shape[0]), la.Ki,
+                      la.Ko, la.stages, B, sq.rows_per_block, cplx, stream)
         mark("down")
-        capi.call("ck_squared_down_leaf", down.data_ptr(), down.numel(), bt["vars_host"].ctypes.data, bt["vars_dev"].data_ptr(),
+        capi.call("ck_squared_down_leaf", down.data_ptr(), down.numel(), bt.vars_host.ctypes.data, bt.vars_dev.data_ptr(),
                   len(dp.qvars), int(out.shape[2]), out.data_ptr(), B, cplx, stream)
     mark("leaf")
-    sq.last_down_launches += len(bt["launches"]) + 1
+    sq.last_down_launches += len(bt.launches) + 1
 
 
 def chunk_rows(sq, dp: DownPlan, rows_per_chunk=None) -> int:
-    step = int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // row_bytes(sq, dp))
-    if step <= 0:
-        raise ValueError("rows_per_chunk must be positive")
-    return step
+    return sq._chunk_rows(rows_per_chunk, lambda: row_bytes(sq, dp))
 
 
 def query_log_marginals(sq, x, query_vars, integrate_vars=None, *, normalized=True, return_log_evidence=False, rows_per_chunk=None,
                         mark=None):
     dp = plan_of(sq, query_vars, integrate_vars)
-    sm = sampler(sq)
-    xw, bad = sm.clean(x, dp.mask)
+    xw, bad = sq._clean(x, dp.mask)
     B = int(xw.shape[0])
     step = chunk_rows(sq, dp, rows_per_chunk)
-    C = max(sm.num_states(v) for v in dp.qvars)
+    C = max(sq.graph.num_states(v) for v in dp.qvars)
     out = torch.empty((B, len(dp.qvars), C), dtype=torch.float32, device=sq.device)
     ev = torch.empty(B, dtype=torch.float32, device=sq.device)
     sq.last_mixed_launches = 0

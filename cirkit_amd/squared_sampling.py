@@ -28,115 +28,10 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .plan import Plan, resolve_fold_index
-from .squared import INTEGRATED, MIXED, OBSERVED, _CHUNK_BYTES, MixedPlan, _mask_of, mixed_plan
+from .squared import INTEGRATED, MIXED, MixedPlan, _mask_of, mixed_plan, put_bounded
+from .squared_graph import PathLevel, PathPlan, fold_class, mask_bits, path_plan, scope_bits, tree_order  # noqa: F401 (also for callers)
 
 _HEAD = capi.CK_SQ_PATH_LEVEL_WORDS
-
-
-@dataclass
-class PathLevel:
-    """One ancestor of a variable: fold `fold` of layer `layer`, which reads the fold below it on the path in child slot
-    `slot` and the `siblings` ``(layer, fold)`` in its other slots."""
-
-    layer: int
-    fold: int
-    slot: int
-    siblings: list[tuple[int, int]]
-
-
-@dataclass
-class PathPlan:
-    var: int
-    leaf: tuple[int, int]  # the input fold that reads the variable
-    levels: list[PathLevel]  # root first
-
-    def folds(self) -> set[tuple[int, int]]:
-        return {self.leaf} | {(lv.layer, lv.fold) for lv in self.levels}
-
-
-def _children(plan: Plan):
-    folds = [l.num_folds for l in plan.layers]
-    return [None if l.inputs is None else resolve_fold_index(l.inputs, folds) for l in plan.layers]
-
-
-def _output_fold(plan: Plan) -> tuple[int, int]:
-    p, f = resolve_fold_index(plan.output, [l.num_folds for l in plan.layers]).reshape(-1, 2)[0]
-    return int(p), int(f)
-
-
-def _readers(plan: Plan) -> dict[tuple[int, int], list[tuple[int, int, int]]]:
-    """``(layer, fold)`` -> the ``(layer, fold, slot)`` that read it."""
-    out: dict[tuple[int, int], list[tuple[int, int, int]]] = {}
-    for i, ch in enumerate(_children(plan)):
-        if ch is None:
-            continue
-        for f in range(ch.shape[0]):
-            for h in range(ch.shape[1]):
-                out.setdefault((int(ch[f, h, 0]), int(ch[f, h, 1])), []).append((i, f, h))
-    return out
-
-
-def tree_order(plan: Plan) -> list[int]:
-    """The variables in the order a depth-first walk of the fold tree below the output meets them.  Sampling in this order,
-    every sibling of a fold on the path of the variable being drawn is entirely drawn or entirely still to draw."""
-    children = _children(plan)
-    order: list[int] = []
-    seen: set[int] = set()
-    stack = [_output_fold(plan)]
-    while stack:
-        p, f = stack.pop()
-        if children[p] is None:
-            for v in plan.layers[p].scope_idx[f]:
-                if int(v) not in seen:
-                    seen.add(int(v))
-                    order.append(int(v))
-            continue
-        stack.extend((int(q), int(g)) for q, g in children[p][f][::-1])
-    return order
-
-
-def path_plan(plan: Plan, var: int, readers=None) -> PathPlan:
-    """The ancestry of a variable, root first.  ``NotImplementedError`` unless it is a path: one input fold reads the
-    variable and every fold on the way up has exactly one reader, up to the output fold (a region graph that is a tree)."""
-    readers = _readers(plan) if readers is None else readers
-    leaves = [(i, f) for i, l in enumerate(plan.layers) if l.inputs is None
-              for f in range(l.num_folds) if int(var) in (int(v) for v in l.scope_idx[f])]
-    if len(leaves) != 1:
-        raise NotImplementedError(f"HipSquaredCircuit: variable {var} is read by {len(leaves)} input folds; sampling and all-state "
-                                  "conditionals walk ONE path from the root to the variable (region graphs that are trees)")
-    top = _output_fold(plan)
-    levels: list[PathLevel] = []
-    cur = leaves[0]
-    children = _children(plan)
-    while cur != top:
-        rd = readers.get(cur, [])
-        if len(rd) != 1:
-            raise NotImplementedError(f"HipSquaredCircuit: fold {cur[1]} of layer {cur[0]} above variable {var} has {len(rd)} readers; "
-                                      "sampling and all-state conditionals walk ONE path from the root to the variable (region graphs "
-                                      "that are trees; a DAG such as a QuadGraph or Poon-Domingos is not supported)")
-        i, f, h = rd[0]
-        sib = [(int(p), int(g)) for k, (p, g) in enumerate(children[i][f]) if k != h]
-        levels.append(PathLevel(i, f, h, sib))
-        cur = (i, f)
-    return PathPlan(int(var), leaves[0], levels[::-1])
-
-
-def scope_bits(plan: Plan) -> list[list[int]]:
-    """Per layer, per fold, the variables under it as the bits of an int."""
-    out: list[list[int]] = []
-    for l, ch in zip(plan.layers, _children(plan)):
-        if ch is None:
-            out.append([sum(1 << int(v) for v in row) for row in l.scope_idx])
-        else:
-            row_bits = []
-            for row in ch:
-                b = 0
-                for p, g in row:
-                    b |= out[int(p)][int(g)]
-                row_bits.append(b)
-            out.append(row_bits)
-    return out
 
 
 @dataclass
@@ -154,7 +49,20 @@ class OrderPlan:
     steps: list[StepPlan]
     max_siblings: int
     max_levels: int
-    dev: dict = field(default_factory=dict)  # batch size -> bound tables
+    dev: dict = field(default_factory=dict)  # batch size -> `PathTables`
+
+
+@dataclass
+class PathTables:
+    """The level tables of every step of an order at a batch size, stacked (steps, levels, words) on the host and on the
+    device, the mixed launches of the steps that have any, and one mixed arena for all of them."""
+
+    key: tuple
+    host: np.ndarray
+    dev: torch.Tensor
+    launches: list  # per step a list of `MixedLaunch`, or None
+    arena: torch.Tensor | None
+    mid: torch.Tensor | None
 
 
 def _check_discrete(sq) -> None:
@@ -168,43 +76,23 @@ class _Sampler:
 
     def __init__(self, sq) -> None:
         self.sq = sq
-        self.readers = _readers(sq.plan)
-        self.bits = scope_bits(sq.plan)
-        self.paths: dict[int, PathPlan] = {}
+        self.graph = sq.graph
         self.orders: dict[bytes, OrderPlan] = {}
-        self.fold_base = np.concatenate([[0], np.cumsum([l.num_folds for l in sq.plan.layers])])
-        self._tree: list[int] | None = None
-
-    def tree(self) -> list[int]:
-        if self._tree is None:
-            self._tree = tree_order(self.sq.plan)
-        return self._tree
-
-    def path(self, v: int) -> PathPlan:
-        if v not in self.paths:
-            self.paths[v] = path_plan(self.sq.plan, v, self.readers)
-        return self.paths[v]
 
     # -- host plans ------------------------------------------------------------------------------------------------------------
     def _step(self, v: int, integrated: np.ndarray) -> StepPlan:
         """`integrated`: (D,) bool without v."""
-        sq, path = self.sq, self.path(v)
-        mbits = sum(1 << int(i) for i in np.nonzero(integrated)[0])
-        views = sq._z_binding().views
-        cls, need = [], False
-        for lv in path.levels:
-            row = []
-            for p, g in lv.siblings:
-                b = self.bits[p][g]
-                c = OBSERVED if not (b & mbits) else (INTEGRATED if not (b & ~mbits) else MIXED)
-                need = need or c == MIXED or (c == INTEGRATED and views[sq._z_of[p]] is None)
-                row.append(c)
-            cls.append(row)
+        sq, path = self.sq, self.graph.path(v)
+        mbits = mask_bits(integrated)
+        const = sq._const_available()
+        cls = [[fold_class(self.graph.bits[p][g], mbits) for p, g in lv.siblings] for lv in path.levels]
+        need = any(c == MIXED or (c == INTEGRATED and not const(p))
+                   for lv, row in zip(path.levels, cls) for (p, _), c in zip(lv.siblings, row))
         mp = None
         if need:
             m = integrated.copy()
             m[v] = True
-            mp = mixed_plan(sq.plan, m, lambda p: views[sq._z_of[p]] is not None, path=path.folds())
+            mp = mixed_plan(sq.plan, m, const, path=path.folds(), graph=self.graph)
         return StepPlan(path, cls, mp)
 
     def order_plan(self, order: list[int], integrated: np.ndarray) -> OrderPlan:
@@ -214,17 +102,15 @@ class _Sampler:
         op = self.orders.get(key)
         if op is None:
             for v in order:  # (the refusals come before anything is built)
-                self.path(v)
+                self.graph.path(v)
             left = integrated.copy()
             left[order] = True
             steps = []
             for v in order:
                 left[v] = False
                 steps.append(self._step(v, left))
-            if len(self.orders) >= 8:
-                self.orders.pop(next(iter(self.orders)))
-            op = self.orders[key] = OrderPlan(steps, max([len(lv.siblings) for s in steps for lv in s.path.levels] + [0]),
-                                              max([len(s.path.levels) for s in steps] + [1]))
+            op = put_bounded(self.orders, key, OrderPlan(steps, max([len(lv.siblings) for s in steps for lv in s.path.levels] + [0]),
+                                                         max([len(s.path.levels) for s in steps] + [1])), 8)
         return op
 
     def row_bytes(self, op: OrderPlan) -> int:
@@ -237,9 +123,8 @@ class _Sampler:
         return (n + extra) * sq._esize
 
     # -- device tables -----------------------------------------------------------------------------------------------------------
-    def bind(self, op: OrderPlan, B: int, bd_c, bd_z) -> dict:
-        """The level tables of every step at batch size B, stacked (steps, levels, words) on the host and on the device, the
-        mixed launches of the steps that have any, and one mixed arena for all of them."""
+    def bind(self, op: OrderPlan, B: int, bd_c, bd_z) -> PathTables:
+        """The `PathTables` of an order at batch size B."""
         sq = self.sq
         layers = sq.plan.layers
         weights = {}
@@ -250,21 +135,16 @@ class _Sampler:
                     weights[lv.layer] = sq._stage_weights(lv.layer, l.num_output_units, l.num_input_units)
         key = (bd_c.arena.data_ptr(), bd_z.arena.data_ptr(), tuple(w.data_ptr() for ws in weights.values() for w in ws))
         hit = op.dev.get(B)
-        if hit is not None and hit["key"] == key:
+        if hit is not None and hit.key == key:
             return hit
         W = _HEAD + 2 * op.max_siblings
         host = np.zeros((len(op.steps), op.max_levels, W), dtype=np.int64)
         launches, total, mid = [], 1, 0
         for si, s in enumerate(op.steps):
-            bases, pos = {}, {}
-            if s.mixed is not None:
-                tb = sq._tables(s.mixed, B, bd_c, bd_z, alloc=False)
-                launches.append(tb["launches"])
-                total, mid = max(total, tb["total"]), max(mid, tb["mid_size"])
-                bases = {la["layer"]: la["base"] for la in tb["launches"]}
-                pos = {m.layer: {int(f): j for j, f in enumerate(m.folds)} for m in s.mixed.layers}
-            else:
-                launches.append(None)
+            tb = None if s.mixed is None else sq._tables(s.mixed, B, bd_c, bd_z, alloc=False)
+            launches.append(None if tb is None else tb.launches)
+            if tb is not None:
+                total, mid = max(total, tb.total), max(mid, tb.mid_size)
             for li, lv in enumerate(s.path.levels):
                 l = layers[lv.layer]
                 K = l.num_input_units
@@ -276,23 +156,12 @@ class _Sampler:
                     row[3] = K
                 row[1], row[2], row[6] = lv.fold, K, len(lv.siblings)
                 for h, ((p, g), c) in enumerate(zip(lv.siblings, s.cls[li])):
-                    if layers[p].num_output_units != K:
-                        raise ValueError("a layer's children do not all have its number of input units")
-                    if g in pos.get(p, {}):
-                        kd, off = capi.CK_SQ_FULL, bases[p] + pos[p][g] * B * K * K
-                    elif c == OBSERVED:
-                        kd, off = capi.CK_SQ_RANK1, bd_c.views[p].storage_offset() + g * B * K
-                    else:
-                        kd, off = capi.CK_SQ_CONST, bd_z.views[sq._z_of[p]].storage_offset() + g * K * K
-                    row[_HEAD + 2 * h], row[_HEAD + 2 * h + 1] = kd, off
+                    row[_HEAD + 2 * h: _HEAD + 2 * h + 2] = sq.child(p, g, K, B, c, tb, bd_c, bd_z)
         dt = torch.complex64 if sq._complex else torch.float32
         any_mixed = any(la is not None for la in launches)
-        hit = op.dev[B] = dict(key=key, host=host, dev=torch.from_numpy(host).to(sq.device), launches=launches,
-                               arena=torch.empty(total, dtype=dt, device=sq.device) if any_mixed else None,
-                               mid=torch.empty(mid, dtype=dt, device=sq.device) if mid else None)
-        if len(op.dev) > 2:
-            op.dev.pop(next(iter(op.dev)))
-        return hit
+        return put_bounded(op.dev, B, PathTables(key, host, torch.from_numpy(host).to(sq.device), launches,
+                                                 torch.empty(total, dtype=dt, device=sq.device) if any_mixed else None,
+                                                 torch.empty(mid, dtype=dt, device=sq.device) if mid else None), 2)
 
     # -- the steps ---------------------------------------------------------------------------------------------------------------
     def run(self, op: OrderPlan, xw: torch.Tensor, *, out: torch.Tensor | None = None, dead: torch.Tensor | None = None,
@@ -304,50 +173,24 @@ class _Sampler:
         B, D = int(xw.shape[0]), int(xw.shape[1])
         bd_z = sq._z_binding()
         stream = torch.cuda.current_stream(sq.device).cuda_stream
+        fold_base = self.graph.fold_base
         tb = None
         for si, s in enumerate(op.steps):
             bd_c = sq.c._run(xw)
-            if tb is None or tb["key"][0] != bd_c.arena.data_ptr():
+            if tb is None or tb.key[0] != bd_c.arena.data_ptr():
                 tb = self.bind(op, B, bd_c, bd_z)
-            arena = tb["arena"]
-            if tb["launches"][si] is not None:
-                sq.last_mixed_launches += sq._launch_mixed(tb["launches"][si], arena, tb["mid"], bd_c, bd_z, B)
+            arena = tb.arena
+            if tb.launches[si] is not None:
+                sq.last_mixed_launches += sq._launch_mixed(tb.launches[si], arena, tb.mid, bd_c, bd_z, B)
             pl, fl = s.path.leaf
-            layer = sq.c.layers[pl]
-            table = layer._table
-            C = int(table.shape[1]) - 1
-            if table.dtype != torch.float32 or not table.is_contiguous():
-                raise NotImplementedError("HipSquaredCircuit: an input table that is not real fp32")
+            table, C, K, tlog = sq._leaf_table(pl)
             L = len(s.path.levels)
             with torch.cuda.device(sq.device):
                 capi.call("ck_squared_path_bwd", None if arena is None else arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(),
-                          tb["host"][si].ctypes.data if L else None, tb["dev"][si].data_ptr() if L else None, L, op.max_siblings,
-                          table.data_ptr(), fl, C, int(table.shape[2]), 1 if sq.plan.layers[pl].type == "categorical" else 0,
-                          None if log_m is None else log_m.data_ptr(), xw.data_ptr(), None if out is None else out.data_ptr(),
-                          None if dead is None else dead.data_ptr(), D, s.path.var, int(self.fold_base[pl]) + fl, seed, row0, B,
-                          sq.rows_per_block, 1 if sq._complex else 0, stream)
-
-    def num_states(self, v: int) -> int:
-        pl, _ = self.path(v).leaf
-        cfg = self.sq.plan.layers[pl].config
-        return int(cfg.get("num_states", cfg.get("num_categories", 0)))
-
-    def clean(self, x: torch.Tensor, ignored: np.ndarray):
-        """x on the device as int64 with 0 where it is ignored or absent; (B,) bool: rows with an absent OBSERVED entry."""
-        sq = self.sq
-        D = sq.plan.num_variables
-        if x.dim() != 2 or x.shape[1] != D:
-            raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
-        x = x.to(sq.device).to(torch.int64)
-        mask = torch.from_numpy(ignored).to(sq.device)
-        absent = x < 0
-        return torch.where(mask | absent, torch.zeros((), dtype=torch.int64, device=sq.device), x).contiguous(), (absent & ~mask).any(dim=1)
-
-    def chunk_rows(self, op: OrderPlan, rows_per_chunk) -> int:
-        step = int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // self.row_bytes(op))
-        if step <= 0:
-            raise ValueError("rows_per_chunk must be positive")
-        return step
+                          tb.host[si].ctypes.data if L else None, tb.dev[si].data_ptr() if L else None, L, op.max_siblings,
+                          table.data_ptr(), fl, C, K, tlog, None if log_m is None else log_m.data_ptr(), xw.data_ptr(),
+                          None if out is None else out.data_ptr(), None if dead is None else dead.data_ptr(), D, s.path.var,
+                          int(fold_base[pl]) + fl, seed, row0, B, sq.rows_per_block, 1 if sq._complex else 0, stream)
 
 
 def sampler(sq) -> _Sampler:
@@ -369,10 +212,10 @@ def state_log_marginals(sq, x, var, integrate_vars=None, *, normalized=True, row
     op = sm.order_plan([var], mask)
     ignored = mask.copy()
     ignored[var] = True
-    xw, bad = sm.clean(x, ignored)
+    xw, bad = sq._clean(x, ignored)
     B = int(xw.shape[0])
-    out = torch.empty((B, sm.num_states(var)), dtype=torch.float32, device=sq.device)
-    step = sm.chunk_rows(op, rows_per_chunk)
+    out = torch.empty((B, sq.graph.num_states(var)), dtype=torch.float32, device=sq.device)
+    step = sq._chunk_rows(rows_per_chunk, lambda: sm.row_bytes(op))
     sq.last_mixed_launches = 0
     for r0 in range(0, B, step):
         sm.run(op, xw[r0: r0 + step], log_m=out[r0: r0 + step])
@@ -393,11 +236,11 @@ def sample_conditional(sq, x, sample_vars, *, seed=None, order=None, rows_per_ch
     D = sq.plan.num_variables
     drawn = _mask_of(sample_vars, D, "sample")
     if order is None:
-        order = [v for v in sm.tree() if drawn[v]]
+        order = [v for v in sq.graph.tree_order() if drawn[v]]
     order = [int(v) for v in order]
     if sorted(order) != np.nonzero(drawn)[0].tolist():
         raise ValueError("order must be a permutation of the sampled variables")
-    xw, bad = sm.clean(x, drawn)
+    xw, bad = sq._clean(x, drawn)
     out = x.to(sq.device).to(torch.int64).clone()
     if not order:
         return out
@@ -405,7 +248,7 @@ def sample_conditional(sq, x, sample_vars, *, seed=None, order=None, rows_per_ch
     op = sm.order_plan(order, np.zeros(D, dtype=bool))
     dead = bad.to(torch.int32).contiguous()
     B = int(xw.shape[0])
-    step = sm.chunk_rows(op, rows_per_chunk)
+    step = sq._chunk_rows(rows_per_chunk, lambda: sm.row_bytes(op))
     sq.last_mixed_launches = 0
     for r0 in range(0, B, step):
         sm.run(op, xw[r0: r0 + step], out=out[r0: r0 + step], dead=dead[r0: r0 + step], seed=seed, row0=r0)

@@ -46,10 +46,10 @@ def _kinds_read(sq):
     kinds = set()
     for dp in sq._down_plans.values():
         for bt in dp.dev.values():
-            for la in bt["launches"]:
-                for row in la["host"]:
-                    down = [int(row[2 + 3 * h]) >= 0 for h in range(la["H"])]
-                    kinds |= {int(row[3 + 3 * h]) for h in range(la["H"]) if sum(down) - down[h] > 0}
+            for la in bt.launches:
+                for row in la.host:
+                    down = [int(row[2 + 3 * h]) >= 0 for h in range(la.H)]
+                    kinds |= {int(row[3 + 3 * h]) for h in range(la.H) if sum(down) - down[h] > 0}
     return kinds
 
 

@@ -93,7 +93,7 @@ def _kinds_read(sq):
     kinds = set()
     for op in sampler(sq).orders.values():
         for tb in op.dev.values():
-            for row in tb["host"].reshape(-1, tb["host"].shape[-1]):
+            for row in tb.host.reshape(-1, tb.host.shape[-1]):
                 kinds |= {int(k) for k in row[8: 8 + 2 * int(row[6]): 2]}
     return kinds
 
