@@ -216,8 +216,9 @@ class HipSquaredCircuit:
     layers `functional.squared_partition_plan` refuses (Tucker, Kronecker, dense sums of arity > 1), input layers over several
     variables.  `sample`, `sample_conditional`, `state_log_marginals` and `posterior` (exact too; discrete inputs and region
     graphs that are trees) refuse Gaussian inputs and DAG ancestries; so do `query_log_marginals` and `posterior_marginals`,
-    the posteriors of a whole set of query variables from one pass down the folds above them.  Not offered: per-row masks,
-    leave-one-out conditionals, gradients with respect to parameters; ``c``'s forward and the mixed pass are separate launches."""
+    the posteriors of a whole set of query variables from one pass down the folds above them, and `leave_one_out_log_marginals`,
+    `leave_one_out` and `conditional_log_probs`, every variable given all the others from one K-sized pass over ``c`` itself.  Not
+    offered: per-row masks, gradients with respect to parameters; ``c``'s forward and the mixed pass are separate launches."""
 
     def __init__(self, plan_c: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0", rows_per_block: int = 1) -> None:
         from .circuit import HipCircuit
@@ -251,6 +252,9 @@ class HipSquaredCircuit:
         self._down_plans: dict = {}  # (Q, I) -> `squared_posterior.DownPlan`
         self.last_down_launches = 0  # launches of `ck_squared_down_bwd` and `ck_squared_down_leaf` in the last call of
         #                              `query_log_marginals` / `posterior_marginals` (their mixed launches: `last_mixed_launches`)
+        self._loo_plans: dict = {}  # Q -> `squared_loo.LooPlan`
+        self._loo_buf = None  # the derivative arena of the leave-one-out pass, grown to the largest call
+        self.last_loo_launches = 0  # launches of `ck_squared_loo_down` and `ck_squared_loo_leaf` in the last leave-one-out call
 
     @property
     def num_variables(self) -> int:
@@ -516,6 +520,40 @@ class HipSquaredCircuit:
         from .squared_posterior import posterior_marginals
 
         return posterior_marginals(self, x, query_vars, integrate_vars, return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
+
+    # -- every variable given all the others (cirkit_amd/squared_loo.py) -------------------------------------------------------------
+    def leave_one_out_log_marginals(self, x: torch.Tensor, query_vars=None, *, normalized: bool = True,
+                                    rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, |Q|, C)`` fp32: ``log |c(x_{-v}, X_v = s)|^2`` for every query variable ``v`` (the ``Q`` axis in ascending variable
+        order; None: every variable) and every state ``s``, with EVERY other entry of the row observed, the other query variables
+        included -- `log_prob` of the row with ``x_v = s``, for all ``v`` and ``s`` from one K-sized derivative pass over ``c`` itself on
+        top of ``c``'s forward (`last_loo_launches`: one launch per layer with a fold above ``Q``, one for the leaves) -- minus
+        ``log Z`` when `normalized`.  ``C`` is the largest number of states among the query variables; columns past a variable's
+        own count are ``-inf``.  A negative entry anywhere in a row, at a query variable too, makes that row NaN.  ``ValueError``
+        for an empty ``Q``; ``NotImplementedError`` for Gaussian inputs and DAG ancestries, before anything is allocated.  The
+        results do not depend on `rows_per_chunk`.  Accuracy: a state is a sum of ``K`` signed terms, right to about 1e-6 of its
+        row's largest state ("Leave-one-out conditionals of squared circuits").
+
+        Out of scope: integrated variables (the derivative is then not rank-1: `posterior_marginals`), per-row masks, fusing the
+        pass with ``c``'s forward."""
+        from .squared_loo import leave_one_out_log_marginals
+
+        return leave_one_out_log_marginals(self, x, query_vars, normalized=normalized, rows_per_chunk=rows_per_chunk)
+
+    def leave_one_out(self, x: torch.Tensor, query_vars=None, *, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, |Q|, C)``: ``log p(X_v = s | x_{-v})``, `leave_one_out_log_marginals` normalised over ``s`` inside the leaf launch.
+        A (row, variable) without any leave-one-out mass is NaN."""
+        from .squared_loo import leave_one_out
+
+        return leave_one_out(self, x, query_vars, rows_per_chunk=rows_per_chunk)
+
+    def conditional_log_probs(self, x: torch.Tensor, *, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, D)``: ``log p(x_v | x_{-v})`` of every entry of every row, without the ``(B, D, C)`` table; ``.sum(1)`` is the
+        pseudo-log-likelihood.  An observed state without mass is ``-inf``; a (row, variable) without any leave-one-out mass, and
+        every entry of a row with a negative entry, is NaN."""
+        from .squared_loo import conditional_log_probs
+
+        return conditional_log_probs(self, x, rows_per_chunk=rows_per_chunk)
 
     def sample(self, num_samples: int, *, seed: int | None = None, order=None, rows_per_chunk: int | None = None) -> torch.Tensor:
         """``(N, D)`` int64 exact samples of ``p(x) = |c(x)|^2 / Z``, one variable after the other: `order` (a permutation of

@@ -14,8 +14,8 @@ per layer of ``c`` that has down folds, from the output layer downwards, and one
 folds included; nothing is released before the call ends.
 
 Refused as `state_log_marginals` refuses: Gaussian inputs, and ancestries that are not paths (`path_plan`).  Out of scope:
-leave-one-out conditionals (the other query variables observed: ``G`` is rank-1 there and the ``K^2`` form loses the small states
-in fp32), per-row masks, DAG region graphs, complex parameter tensors, fusing ``c``'s forward or the mixed pass with the down
+leave-one-out conditionals (the other query variables observed: ``G`` is rank-1 there and has a K-sized pass of its own,
+cirkit_amd/squared_loo.py; DESIGN.md section 11, "Leave-one-out conditionals of squared circuits"), per-row masks, DAG region graphs, complex parameter tensors, fusing ``c``'s forward or the mixed pass with the down
 pass, gradients with respect to parameters.
 """
 

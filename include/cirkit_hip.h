@@ -1627,6 +1627,45 @@ int ck_squared_down_bwd(const float* full, const float* cst, const float* rank1,
 int ck_squared_down_leaf(const float* down, int64_t down_elems, const int64_t* vars_host, const int64_t* vars, int nq, int C_max,
                          float* log_m, int B, int complex_values, void* stream);
 
+/* ---- leave-one-out conditionals of squared circuits ("Leave-one-out conditionals of squared circuits";
+ * additive, ABI 51).  Replaces: nothing -- the reference has no such query.
+ * With every variable but v observed, |c(x_-v, s)|^2 = |sum_k g_k a_k(s)|^2 with g = dc(x)/du for the K units u of the input fold
+ * of v: ONE pass over c itself, K values per row and fold.  The pass carries D = log dc/du as a signed logarithm (float, or
+ * complex64 whose argument is a multiple of pi: the parameters are real).  One call per layer of c that has down folds (folds
+ * whose scope holds a query variable), from the output layer downwards; for each of its n down folds and B rows
+ *     w != NULL (num_weight_folds, Ko, Ki), real and signed:  P_i = log sum_k W[k][i] exp(D_k), shifted by the row's largest finite
+ *         Re D_k and summed in linear space on the real part; the argument is pi where the sum is negative, the value -inf where
+ *         the sum is exactly 0
+ *     w == NULL, a Hadamard layer (Ki = Ko):  P = D
+ * and for every child slot h that is a down fold itself
+ *     D_child[b, :] = P + sum over h' != h of value(h')      (Ki values per row in `values`, c's arena, read in slot order)
+ * never the total minus the child's own value.  Every child is written exactly once (trees only): `der` needs no initialisation.
+ * folds (device) / folds_host (the same words on the host, checked against value_elems and der_elems before the launch): n rows of
+ * CK_SQ_LOO_FOLD_WORDS + 2 H int64:
+ *     [0] weight fold  [1] element offset of the fold's D in `der` (Ko values per row), or -1: the output fold, log 1 at unit 0
+ *     then H pairs (element offset of the child's D in `der` or -1: not a down fold, element offset of the child's value)
+ * form 0: Ki = 32 with Ko = 32, or Ko = 1 on the output fold, and every offset a multiple of 16 bytes, takes the register-tile form
+ * (32 rows per wave, the fold's matrix staged once per workgroup, the contraction on v_mfma_f32_32x32x2_f32 in exact fp32); every
+ * other shape the VALU form, refused with CK_ERR_UNSUPPORTED where the matrix does not fit in LDS.  form 1: the VALU form whatever
+ * the shape (measurements).  A row's result does not depend on its place in a tile or on B.  H <= 8. */
+#define CK_SQ_LOO_FOLD_WORDS 2
+int ck_squared_loo_down(const float* values, int64_t value_elems, float* der, int64_t der_elems, const int64_t* folds_host,
+                        const int64_t* folds, int n, int H, const float* w, int num_weight_folds, int Ki, int Ko, int B,
+                        int complex_values, int form, void* stream);
+
+/* The leaves of that pass, one launch for all query variables: A(s) = sum_k Re exp(D_k - m) a_k(s) over the variable's own table,
+ * log m(s) = 2 (log |A(s)| + m), -inf where A(s) = 0; a table of logarithms is shifted state by state.  vars / vars_host: nq rows
+ * of CK_SQ_LOO_LEAF_WORDS int64:
+ *     [0] device address of the variable's (C + 1, K) fp32 table  [1] C  [2] K  [3] 1 a table of logarithms, 0 linear values
+ *     [4] element offset of the D of its input fold in `der`, or -1 (the input fold is the output fold)  [5] its column of x
+ * mode 0: out (B, nq, C_max) = log m;  mode 1: the same minus its logsumexp over the states (a row without mass: NaN);  columns
+ * past a variable's own C are -inf.  mode 2: out (B, nq) = log m(x[b, column]) - logsumexp over the states, x (B, D) int64 (an
+ * entry outside 0 .. C - 1 reads the nearest state: the caller masks such rows).  One workgroup per (variable, tile of rows); the
+ * table is staged once per workgroup and 256 states; CK_ERR_UNSUPPORTED where one row and the table do not fit in LDS. */
+#define CK_SQ_LOO_LEAF_WORDS 6
+int ck_squared_loo_leaf(const float* der, int64_t der_elems, const int64_t* vars_host, const int64_t* vars, int nq, int C_max,
+                        const int64_t* x, int D, float* out, int mode, int B, int complex_values, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
