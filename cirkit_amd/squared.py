@@ -12,7 +12,10 @@ the set ``M`` of a call, into one of three classes (`fold_classes`):
 * MIXED -- its scope meets both: only these folds are evaluated at ``K^2`` units per row, by `ck_squared_mixed_fwd`
   (cirkit_amd/csrc/ck_sqmar.hip; kind FULL), one launch per layer of ``c`` that has any.
 
-Input folds have one variable and are never mixed, so the leaf layer of the product circuit is never materialised.
+Under point evidence an input fold has one variable and is never mixed, so the leaf layer of the product circuit is never
+materialised.  Soft and interval evidence (cirkit_amd/squared_soft.py: `soft_evidence_log_prob`, `interval_log_prob`, `log_cdf`)
+add a third state of a variable -- a weight per state: the input folds of those variables are evaluated too, as weighted Gram
+matrices (`ck_squared_soft_leaf`, cirkit_amd/csrc/ck_sqsoft.hip), and read by the same launches as FULL children.
 
 Sampling and the posterior of one variable over all its states walk the other way, from the root down to one input fold
 (cirkit_amd/squared_sampling.py: `sample`, `sample_conditional`, `state_log_marginals`, `posterior`), and read the folds beside
@@ -33,7 +36,7 @@ import torch
 
 from . import _capi as capi
 from .plan import Plan
-from .squared_graph import INTEGRATED, MIXED, OBSERVED, FoldGraph, graph_of
+from .squared_graph import INTEGRATED, MIXED, OBSERVED, FoldGraph, graph_of, mask_bits
 
 _INPUTS = ("embedding", "categorical", "gaussian")
 _CHUNK_BYTES = 2 << 30  # c's arena + the mixed arena of one chunk of rows
@@ -76,26 +79,45 @@ class MixedLayer:
 
 
 @dataclass
+class SoftLeaf:
+    """The evaluated input folds of one input layer of ``c`` under soft or interval evidence: per fold its variable and that
+    variable's position among the soft variables in ascending order (the ``S`` axis of ``log_lik``)."""
+
+    layer: int
+    folds: np.ndarray  # (n,) folds of the layer, ascending
+    var: np.ndarray  # (n,)
+    pos: np.ndarray  # (n,)
+
+
+@dataclass
 class MixedPlan:
     classes: list[np.ndarray]
     layers: list[MixedLayer]
     root: tuple[int, int, int]  # (class of the output fold, layer, fold -- or position among the evaluated folds when MIXED)
     dev: dict = field(default_factory=dict)  # batch size -> device tables
+    leaves: list[SoftLeaf] = field(default_factory=list)  # (soft evidence only)
 
     @property
     def num_mixed(self) -> int:
         return int(sum(len(m.folds) for m in self.layers))
 
 
-def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None, readers=None, graph: FoldGraph | None = None) -> MixedPlan:
+def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None, readers=None, graph: FoldGraph | None = None,
+               soft: np.ndarray | None = None) -> MixedPlan:
     """Which folds a call with this mask evaluates at K^2 units, layer by layer in plan order, and the kind tables of their
     children.  `const_available(layer)`: whether the partition-function circuit keeps that layer's squared output in memory;
     an INTEGRATED child without one is evaluated here like a mixed fold (from CONST children: still exact).  `path`: a set of
     ``(layer, fold)`` that needs no value -- the ancestry of one variable, walked downwards by `squared_sampling` -- but whose
     other children do; the root of the result is then not looked up among the evaluated folds.  `readers`: a set of
-    ``(layer, fold)`` whose children are read as well (the down folds of `squared_posterior`) while they keep their own class."""
+    ``(layer, fold)`` whose children are read as well (the down folds of `squared_posterior`) while they keep their own class.
+    `soft`: a ``(D,)`` bool mask of variables that carry a weight per state (disjoint from `mask`); every fold whose scope
+    meets it is evaluated, INPUT folds too: those form `MixedPlan.leaves`, one record per input layer, and their readers see
+    them as FULL children."""
     graph = graph_of(plan, graph)
     cls, children = graph.classes(mask), graph.children
+    if soft is not None:
+        sbits = mask_bits(soft)
+        cls = [np.where(np.asarray([bool(b & sbits) for b in row]), np.int8(MIXED), c) for row, c in zip(graph.bits, cls)]
     need = [set(np.nonzero(c == MIXED)[0].tolist()) for c in cls]
     path = path or set()
     on_path: list[set] = [set() for _ in plan.layers]
@@ -118,11 +140,16 @@ def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None, re
                     need[p].add(g)
     out: list[MixedLayer] = []
     pos: list[dict[int, int]] = [{} for _ in plan.layers]
+    leaves: list[SoftLeaf] = []
     for i, l in enumerate(plan.layers):
         if not need[i]:
             continue
         fs = np.asarray(sorted(need[i]), dtype=np.int64)
         pos[i] = {int(f): j for j, f in enumerate(fs)}
+        if children[i] is None:  # (only with `soft`: an input fold is otherwise OBSERVED or INTEGRATED)
+            var = np.asarray([int(l.scope_idx[f][0]) for f in fs], dtype=np.int64)
+            leaves.append(SoftLeaf(i, fs, var, np.cumsum(soft)[var] - 1))
+            continue
         kind = np.zeros((len(fs), l.arity), dtype=np.int32)
         src = np.zeros((len(fs), l.arity, 2), dtype=np.int64)
         for j, f in enumerate(fs):
@@ -137,7 +164,7 @@ def mixed_plan(plan: Plan, mask: np.ndarray, const_available=None, path=None, re
         out.append(MixedLayer(i, fs, kind, src))
     op, of = graph.top
     rc = int(cls[op][of])
-    return MixedPlan(cls, out, (rc, op, pos[op][of] if rc == MIXED and (op, of) not in path else of))
+    return MixedPlan(cls, out, (rc, op, pos[op][of] if rc == MIXED and (op, of) not in path else of), leaves=leaves)
 
 
 @dataclass
@@ -173,6 +200,7 @@ class MixedTables:
     mid_size: int
     arena: torch.Tensor | None
     mid: torch.Tensor | None
+    leaves: list = field(default_factory=list)  # `squared_soft.SoftLaunch`: the leaf launches of soft evidence, before `launches`
 
     def offset(self, layer: int, fold: int) -> int | None:
         """Where the mixed pass wrote fold `fold` of layer `layer`, or None: it did not evaluate it."""
@@ -217,7 +245,9 @@ class HipSquaredCircuit:
     variables.  `sample`, `sample_conditional`, `state_log_marginals` and `posterior` (exact too; discrete inputs and region
     graphs that are trees) refuse Gaussian inputs and DAG ancestries; so do `query_log_marginals` and `posterior_marginals`,
     the posteriors of a whole set of query variables from one pass down the folds above them, and `leave_one_out_log_marginals`,
-    `leave_one_out` and `conditional_log_probs`, every variable given all the others from one K-sized pass over ``c`` itself.  Not
+    `leave_one_out` and `conditional_log_probs`, every variable given all the others from one K-sized pass over ``c`` itself.
+    `soft_evidence_log_prob`, `interval_log_prob` and `log_cdf` put a weight per state, or a box, on any set of discrete variables
+    (DAG region graphs included; Gaussian variables stay hard evidence or integrated).  Not
     offered: per-row masks, gradients with respect to parameters; ``c``'s forward and the mixed pass are separate launches."""
 
     def __init__(self, plan_c: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0", rows_per_block: int = 1) -> None:
@@ -255,6 +285,9 @@ class HipSquaredCircuit:
         self._loo_plans: dict = {}  # Q -> `squared_loo.LooPlan`
         self._loo_buf = None  # the derivative arena of the leave-one-out pass, grown to the largest call
         self.last_loo_launches = 0  # launches of `ck_squared_loo_down` and `ck_squared_loo_leaf` in the last leave-one-out call
+        self._soft_plans: dict = {}  # (M, S) -> `MixedPlan` with leaves
+        self._soft_side = None  # (parameter state, input layer -> (F, K) column maxima of its table of logarithms)
+        self.last_soft_launches = 0  # launches of `ck_squared_soft_leaf` in the last soft / interval call (its mixed launches: `last_launches`)
 
     @property
     def num_variables(self) -> int:
@@ -305,6 +338,7 @@ class HipSquaredCircuit:
         for m in mp.layers:
             l = self.plan.layers[m.layer]
             n += len(m.folds) * (self.graph.units(l) ** 2 + (0 if self._special(l) else l.num_input_units * l.num_output_units))
+        n += sum(len(lf.folds) * self.graph.units(self.plan.layers[lf.layer]) ** 2 for lf in mp.leaves)  # the weighted Gram blocks
         return n * self._esize
 
     @staticmethod
@@ -343,6 +377,10 @@ class HipSquaredCircuit:
             tb.total += (len(m.folds) * B * ko2 + 3) // 4 * 4
             if not self._special(l):
                 tb.mid_size = max(tb.mid_size, len(m.folds) * B * l.num_input_units * l.num_output_units)
+        if mp.leaves:
+            from .squared_soft import bind_leaves
+
+            bind_leaves(self, mp, tb, B)
         for m in mp.layers:
             l = self.plan.layers[m.layer]
             rows = [[self.child(p, g, l.num_input_units, B, mp.classes[p][g], tb, bd_c, bd_z) for p, g in self.graph.children[m.layer][f].tolist()]
@@ -554,6 +592,51 @@ class HipSquaredCircuit:
         from .squared_loo import conditional_log_probs
 
         return conditional_log_probs(self, x, rows_per_chunk=rows_per_chunk)
+
+    # -- a weight per state, a box (cirkit_amd/squared_soft.py) ------------------------------------------------------------------------
+    def soft_evidence_log_prob(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, integrate_vars=None,
+                               normalized: bool = True, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B,)`` fp32: ``log sum_{x_S, x_M} |c(x_O, x_S, x_M)|^2 prod_{v in S} lambda[n, v, x_v]``, minus ``log Z`` when
+        `normalized`: soft (likelihood, virtual) evidence on the variables ``S = soft_vars``, ``M = integrate_vars`` integrated out,
+        the others observed at ``x``.  `log_lik`: ``(B, |S|, C)`` floating point, ``log lambda``, the ``S`` axis in ascending variable
+        order; ``C`` at least the largest state count among ``S``, entries past a variable's own count are never read; ``-inf`` is
+        weight 0 (a variable whose read entries are all ``-inf`` makes the row ``-inf``, not NaN); a NaN or ``+inf`` in a read
+        entry makes that row alone NaN.  `soft_vars` / `integrate_vars` in the forms `log_marginal` takes, one set each per call
+        and disjoint (``ValueError``); `soft_vars` None: every variable not integrated; an empty soft set is a ``ValueError``.
+        `x`: required when a variable is in neither set (``ValueError``), ignored at the others; a negative entry at an observed
+        variable makes the row NaN.  ``NotImplementedError``, before anything is allocated, for a soft variable under a Gaussian
+        layer (Gaussian variables stay hard evidence or integrated).  DAG region graphs are fine: one bottom-up pass, c's
+        forward, one `ck_squared_soft_leaf` launch per input layer with a soft fold (`last_soft_launches`) and the mixed launches
+        of every fold whose scope meets ``S`` or both ``M`` and its complement (`last_launches`).  The results do not depend on
+        `rows_per_chunk` (default: c's arena plus the mixed arena, ``|S| K^2`` values per row for the leaves alone, within 2 GiB)
+        or `rows_per_block`.
+
+        Out of scope: posteriors, sampling and MPE under soft evidence, fusing the leaf Gram into the first product layer,
+        the Gram's symmetry, Gaussian boxes, per-row soft sets, gradients."""
+        from .squared_soft import soft_evidence_log_prob
+
+        return soft_evidence_log_prob(self, log_lik, x, soft_vars=soft_vars, integrate_vars=integrate_vars, normalized=normalized,
+                                      rows_per_chunk=rows_per_chunk)
+
+    def interval_log_prob(self, lo: torch.Tensor, hi: torch.Tensor, x: torch.Tensor | None = None, *, box_vars=None, integrate_vars=None,
+                          normalized: bool = True, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B,)`` fp32: the log mass of the box ``lo <= x_v <= hi`` over ``v in box_vars`` (inclusive on both sides), with
+        `integrate_vars` integrated out and the others observed at ``x`` -- the 0/1 case of `soft_evidence_log_prob`, read from the
+        bounds themselves by the same leaf launch: no ``(B, S, C)`` tensor is built and the states outside a row's bounds are
+        skipped.  `lo`, `hi`: ``(B, D)`` integer, read at `box_vars` only and clamped into ``0 .. C_v - 1``; an empty interval
+        gives ``-inf``; ``lo < 0 and hi < 0`` means the full range, `HipCircuit.interval_log_prob`'s sentinel.  `box_vars` None:
+        every variable not integrated.  Sets, `x`, refusals, chunking and the launch counters as in `soft_evidence_log_prob`."""
+        from .squared_soft import interval_log_prob
+
+        return interval_log_prob(self, lo, hi, x, box_vars=box_vars, integrate_vars=integrate_vars, normalized=normalized,
+                                 rows_per_chunk=rows_per_chunk)
+
+    def log_cdf(self, x: torch.Tensor, *, integrate_vars=None, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B,)``: ``log P(X_v <= x_v for every v not integrated)``: `interval_log_prob` of ``[0, x]`` over all those variables,
+        normalised."""
+        from .squared_soft import log_cdf
+
+        return log_cdf(self, x, integrate_vars=integrate_vars, rows_per_chunk=rows_per_chunk)
 
     def sample(self, num_samples: int, *, seed: int | None = None, order=None, rows_per_chunk: int | None = None) -> torch.Tensor:
         """``(N, D)`` int64 exact samples of ``p(x) = |c(x)|^2 / Z``, one variable after the other: `order` (a permutation of

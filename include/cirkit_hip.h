@@ -1666,6 +1666,31 @@ int ck_squared_loo_down(const float* values, int64_t value_elems, float* der, in
 int ck_squared_loo_leaf(const float* der, int64_t der_elems, const int64_t* vars_host, const int64_t* vars, int nq, int C_max,
                         const int64_t* x, int D, float* out, int mode, int B, int complex_values, void* stream);
 
+/* ---- soft and interval evidence of squared circuits ("Soft and interval evidence of squared circuits";
+ * additive, ABI 51) ----
+ * The leaves of Z(lambda)[b] = sum_x |c(x)|^2 prod_{v in S} lambda[b, v, x_v]: for the n input folds of ONE input layer of c that read
+ * a soft variable and B rows, the logarithm of the weighted Gram matrix of the fold's table,
+ *     out[j, b, k K + l] = log sum_{s < C} lambda_b(s) e_k(s) e_l(s)
+ * K^2 values per row in the element format and unit order of ck_squared_mixed_fwd's FULL children (unit k of c slow): fp32 under
+ * lse-sum (complex_values 0), complex64 under complex-lse-sum (1: argument pi where the sum is negative; -inf where it is exactly 0).
+ * The reference has no such query; the unweighted Gram at batch 1 is the input layer of the partition-function circuit.
+ * table (num_folds, C + 1, K) fp32, the input layer's table (row C, the layer's integral row, is not read); table_log 1: a table of
+ * logarithms (Categorical), shifted unit by unit by unit_max (num_folds, K), the clamped maximum of every unit's column over the C
+ * states -- required then; 0: linear values (Embedding), unit_max is not read.  tab (device) / tab_host (the same words on the host,
+ * checked before the launch): n pairs of int32 (fold of the table, column).
+ * Soft evidence: log_lik (B, S, C_lik >= C) fp32, row b of fold j reads log lambda at [b, column, 0 .. C - 1]; lo = hi = NULL.  The
+ * weights are shifted by the clamped maximum m_b of those C entries: all -inf gives -inf, not NaN; a NaN or +inf among them makes
+ * that row's block NaN.  Interval evidence: log_lik = NULL, lo / hi (B, D) int64, lambda_b(s) = [lo <= s <= hi] at [b, column]: both
+ * negative is the full range, else clamped into 0 .. C - 1, lo > hi is empty (-inf); states outside the bounds are skipped.
+ * K = 32 with form 0 contracts on v_mfma_f32_32x32x2_f32 in exact fp32: the table is staged through LDS in slabs of 128 states
+ * (exponentiated where it holds logarithms), a wave carries 4 rows across the slabs, a workgroup 16 rows per walk and
+ * rows_per_block rows (rounded up to 16) in all -- the table is staged once per workgroup where it is a single slab.  Every other K,
+ * and form 1 (measurements), takes a plain VALU form, one row at a time, refused with CK_ERR_UNSUPPORTED for K > 64.  A row's result
+ * does not depend on its place in a workgroup, on rows_per_block or on B. */
+int ck_squared_soft_leaf(const float* table, int num_folds, int C, int K, int table_log, const float* unit_max, const int32_t* tab_host,
+                         const int32_t* tab, int n, const float* log_lik, int S, int C_lik, const int64_t* lo, const int64_t* hi, int D,
+                         float* out, int B, int rows_per_block, int complex_values, int form, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
