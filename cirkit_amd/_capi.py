@@ -379,6 +379,9 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_squared_loo_down": [_p, _l, _p, _l, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p],
     "ck_squared_loo_leaf": [_p, _l, _p, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p],
     "ck_squared_soft_leaf": [_p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i, _i, _i, _i, _p],
+    "ck_squared_soft_down_leaf": [_p, _l, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _p],
+    "ck_squared_path_soft_bwd": [_p, _p, _p, _p, _p, _i, _i, _p, _l, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, C.c_uint64, _l,
+                                 _i, _i, _i, _p],
     "ck_em_job_blocks": [_i, _l, _i],
     "ck_em_update": [_p, _p, _i, _f, _f, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],

@@ -32,6 +32,8 @@ struct SpArgs {
   uint32_t node, seed_lo, seed_hi;
   int64_t row0;
   int B, R, maxK;
+  const float* lam;  // log weights of the variable's states under soft evidence, row b at lam + b lam_row; null: none
+  int64_t lam_row;
 };
 
 template <class T>
@@ -89,10 +91,12 @@ __device__ __forceinline__ void sp_dead_row(const SpArgs<T>& a, int64_t b, int t
 
 // The leaf: log m_b(s) = log max(0, sum_kl e[k][l] a_k(s) a_l(s)) + gmax for every state s, e = Re exp(G - gmax) in LDS (real
 // parameters: a is real and only the real part of the quadratic form is left); a table of logarithms is shifted by its
-// maximum over the units state by state.  Then, with a batch to draw into, the inverse CDF over the states.
+// maximum over the units state by state.  Under soft evidence (`lam`) the state's own log weight is added.  Then, with a batch to
+// draw into, the inverse CDF over the states.
 template <class T>
 __device__ __forceinline__ void sp_leaf(const SpArgs<T>& a, int64_t b, const float* e, float* av, float* lm, float* red, float gmax, int t) {
   const int K = a.K, C = a.C;
+  const float* lam = a.lam ? a.lam + b * a.lam_row : nullptr;
   for (int s0 = 0; s0 < C; s0 += kSpStates) {
     const int n = C - s0 < kSpStates ? C - s0 : kSpStates;
     __syncthreads();  // (e is written, av is free)
@@ -118,6 +122,7 @@ __device__ __forceinline__ void sp_leaf(const SpArgs<T>& a, int64_t b, const flo
       }
       acc = acc < 0.f ? 0.f : acc;  // (cancellation can leave -1e-9: that is a zero, not a NaN; a NaN stays one)
       lm[s0 + t] = logf(acc) + gmax + 2.f * tm;
+      if (lam) lm[s0 + t] += lam[s0 + t];
     }
   }
   __syncthreads();

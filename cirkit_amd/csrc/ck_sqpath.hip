@@ -138,9 +138,8 @@ int sp_dispatch(const A& a, size_t lds, size_t fixed, void* stream) {
 }
 
 template <class S, class S32>
-int sp_launch(const SpArgs<typename S::T>& a, bool all32, void* stream) {
+int sp_launch(const SpArgs<typename S::T>& a, bool all32, const char* who, void* stream) {
   using T = typename S::T;
-  const char* who = "ck_squared_path_bwd";
   if (all32) {
     const size_t lds = sp_leaf_floats(a.C, 32) * sizeof(float);
     if (lds + sizeof(Td32Lds<S32>) > 160 * 1024) return ck::fail(CK_ERR_UNSUPPORTED, "%s: C=%d states do not fit in LDS", who, a.C);
@@ -153,13 +152,11 @@ int sp_launch(const SpArgs<typename S::T>& a, bool all32, void* stream) {
   return sp_dispatch<sp_path_kernel<S>>(a, lds, 0, stream);
 }
 
-}  // namespace
-
-extern "C" int ck_squared_path_bwd(const float* full, const float* cst, const float* rank1, const int64_t* levels_host, const int64_t* levels,
-                                   int L, int max_siblings, const float* table, int64_t leaf_fold, int C, int K, int table_log, float* log_m,
-                                   int64_t* x, int64_t* x_out, int32_t* dead, int D, int var, int node, uint64_t seed, int64_t row0, int B,
-                                   int rows_per_block, int complex_values, void* stream) {
-  const char* who = "ck_squared_path_bwd";
+// what both entries do; lam: the log weights of the variable's own states, row b at lam + b lam_row, or null
+int sp_entry(const char* who, const float* full, const float* cst, const float* rank1, const int64_t* levels_host, const int64_t* levels,
+             int L, int max_siblings, const float* table, int64_t leaf_fold, int C, int K, int table_log, const float* lam,
+             int64_t lam_row, float* log_m, int64_t* x, int64_t* x_out, int32_t* dead, int D, int var, int node, uint64_t seed,
+             int64_t row0, int B, int rows_per_block, int complex_values, void* stream) {
   CK_REQUIRE(table && (log_m || x_out), "%s: null pointer", who);
   CK_REQUIRE(L == 0 || (levels_host && levels), "%s: null pointer (levels)", who);
   CK_REQUIRE(!x_out || (x && dead), "%s: null pointer (a draw needs x, x_out and dead)", who);
@@ -193,10 +190,35 @@ extern "C" int ck_squared_path_bwd(const float* full, const float* cst, const fl
   const auto args = [&](auto* f, auto* c, auto* r) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(f)>>;
     return SpArgs<T>{f, c, r, levels, L, max_siblings, tab, C, K, table_log, log_m, x_out ? x : nullptr, x_out, dead, D, var,
-                     static_cast<uint32_t>(node), static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), row0, B, rows_per_block, maxK};
+                     static_cast<uint32_t>(node), static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), row0, B, rows_per_block, maxK,
+                     lam, lam_row};
   };
   if (complex_values)
     return sp_launch<TdC, TdC32>(args(reinterpret_cast<const c32*>(full), reinterpret_cast<const c32*>(cst), reinterpret_cast<const c32*>(rank1)),
-                                 all32, stream);
-  return sp_launch<TdR, TdR32>(args(full, cst, rank1), all32, stream);
+                                 all32, who, stream);
+  return sp_launch<TdR, TdR32>(args(full, cst, rank1), all32, who, stream);
+}
+
+}  // namespace
+
+extern "C" int ck_squared_path_bwd(const float* full, const float* cst, const float* rank1, const int64_t* levels_host, const int64_t* levels,
+                                   int L, int max_siblings, const float* table, int64_t leaf_fold, int C, int K, int table_log, float* log_m,
+                                   int64_t* x, int64_t* x_out, int32_t* dead, int D, int var, int node, uint64_t seed, int64_t row0, int B,
+                                   int rows_per_block, int complex_values, void* stream) {
+  return sp_entry("ck_squared_path_bwd", full, cst, rank1, levels_host, levels, L, max_siblings, table, leaf_fold, C, K, table_log, nullptr, 0,
+                  log_m, x, x_out, dead, D, var, node, seed, row0, B, rows_per_block, complex_values, stream);
+}
+
+// the same walk under soft evidence: the variable's own log weights log_lik[b, pos, :] are added to log m before it is written and drawn from
+extern "C" int ck_squared_path_soft_bwd(const float* full, const float* cst, const float* rank1, const int64_t* levels_host,
+                                        const int64_t* levels, int L, int max_siblings, const float* table, int64_t leaf_fold, int C, int K,
+                                        int table_log, const float* log_lik, int S, int C_lik, int pos, float* log_m, int64_t* x,
+                                        int64_t* x_out, int32_t* dead, int D, int var, int node, uint64_t seed, int64_t row0, int B,
+                                        int rows_per_block, int complex_values, void* stream) {
+  const char* who = "ck_squared_path_soft_bwd";
+  CK_REQUIRE(log_lik, "%s: null pointer (log_lik)", who);
+  CK_REQUIRE(S > 0 && pos >= 0 && pos < S && C_lik >= C, "%s: position %d of %d, log_lik has %d states, the variable %d", who, pos, S, C_lik, C);
+  return sp_entry(who, full, cst, rank1, levels_host, levels, L, max_siblings, table, leaf_fold, C, K, table_log,
+                  log_lik + static_cast<int64_t>(pos) * C_lik, static_cast<int64_t>(S) * C_lik, log_m, x, x_out, dead, D, var, node, seed, row0,
+                  B, rows_per_block, complex_values, stream);
 }

@@ -247,7 +247,9 @@ class HipSquaredCircuit:
     the posteriors of a whole set of query variables from one pass down the folds above them, and `leave_one_out_log_marginals`,
     `leave_one_out` and `conditional_log_probs`, every variable given all the others from one K-sized pass over ``c`` itself.
     `soft_evidence_log_prob`, `interval_log_prob` and `log_cdf` put a weight per state, or a box, on any set of discrete variables
-    (DAG region graphs included; Gaussian variables stay hard evidence or integrated).  Not
+    (DAG region graphs included; Gaussian variables stay hard evidence or integrated); `soft_query_log_marginals`,
+    `soft_posterior_marginals` and `sample_soft` give the posteriors of all soft variables and exact joint draws under that
+    evidence (trees only, as `posterior_marginals`).  Not
     offered: per-row masks, gradients with respect to parameters; ``c``'s forward and the mixed pass are separate launches."""
 
     def __init__(self, plan_c: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0", rows_per_block: int = 1) -> None:
@@ -288,6 +290,7 @@ class HipSquaredCircuit:
         self._soft_plans: dict = {}  # (M, S) -> `MixedPlan` with leaves
         self._soft_side = None  # (parameter state, input layer -> (F, K) column maxima of its table of logarithms)
         self.last_soft_launches = 0  # launches of `ck_squared_soft_leaf` in the last soft / interval call (its mixed launches: `last_launches`)
+        self._soft_down_plans: dict = {}  # (I, S) -> `squared_posterior.DownPlan` over a soft mixed plan (squared_soft_posterior.py)
 
     @property
     def num_variables(self) -> int:
@@ -611,12 +614,62 @@ class HipSquaredCircuit:
         `rows_per_chunk` (default: c's arena plus the mixed arena, ``|S| K^2`` values per row for the leaves alone, within 2 GiB)
         or `rows_per_block`.
 
-        Out of scope: posteriors, sampling and MPE under soft evidence, fusing the leaf Gram into the first product layer,
-        the Gram's symmetry, Gaussian boxes, per-row soft sets, gradients."""
+        Posteriors and sampling under the same evidence: `soft_posterior_marginals`, `sample_soft`.  Out of scope: MPE under soft
+        evidence, fusing the leaf Gram into the first product layer, the Gram's symmetry, Gaussian boxes, per-row soft sets,
+        gradients."""
         from .squared_soft import soft_evidence_log_prob
 
         return soft_evidence_log_prob(self, log_lik, x, soft_vars=soft_vars, integrate_vars=integrate_vars, normalized=normalized,
                                       rows_per_chunk=rows_per_chunk)
+
+    # -- posteriors and sampling under soft evidence (cirkit_amd/squared_soft_posterior.py) ------------------------------------------
+    def soft_query_log_marginals(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, integrate_vars=None,
+                                 normalized: bool = True, return_log_evidence: bool = False, rows_per_chunk: int | None = None):
+        """``(B, |S|, C_max)`` fp32: for every soft variable ``v`` (the ``S`` axis in ascending variable order) and every state ``s``,
+        ``log lambda_v(s) + log sum_{x: x_v = s} |c(x)|^2 prod_{u in S - v} lambda_u(x_u)`` with `integrate_vars` summed out and the
+        rest observed at ``x``, minus ``log Z`` when `normalized`: the joint of ``X_v = s`` and the soft evidence.  ``C_max`` is the
+        largest state count among ``S``; columns past a variable's own count are ``-inf``.  `return_log_evidence`: also ``(B,)``
+        what `soft_evidence_log_prob` returns, from the root of the same pass at no extra launch.  `log_lik`, the sets, `x`, the
+        refusals and the NaN rows as in `soft_evidence_log_prob`; in addition ``NotImplementedError`` for Gaussian inputs and, as
+        `posterior_marginals`, for a soft variable read by several input folds or below a fold with several readers (DAG region
+        graphs).  One pass: ``c``'s forward, the leaf Gram launches (`last_soft_launches`), the mixed launches (`last_launches`), one
+        `ck_squared_down_bwd` per layer with a fold above ``S`` and one `ck_squared_soft_down_leaf` (`last_down_launches`).  The
+        results do not depend on `rows_per_chunk` (default: c's arena, the mixed arena with its leaf blocks and the down arena
+        within 2 GiB) or `rows_per_block`.  Accuracy as `query_log_marginals`: right to about 1e-5 of the row's largest state.
+
+        Out of scope: MPE under soft evidence (not tractable here), variables without a weight (pass ``log_lik = 0`` for them),
+        boxes read from their bounds (pass 0 / ``-inf`` weights), per-row soft sets, Gaussian inputs, gradients."""
+        from .squared_soft_posterior import soft_query_log_marginals
+
+        return soft_query_log_marginals(self, log_lik, x, soft_vars=soft_vars, integrate_vars=integrate_vars, normalized=normalized,
+                                        return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
+
+    def soft_posterior_marginals(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, integrate_vars=None,
+                                 return_log_evidence: bool = False, rows_per_chunk: int | None = None):
+        """``(B, |S|, C_max)``: ``log p(X_v = s | lambda, x_O)`` for every soft variable at once: `soft_query_log_marginals`
+        normalised over ``s`` per ``(b, v)``.  A (row, variable) without mass is NaN.  `return_log_evidence`: also ``(B,)`` the
+        normalised log evidence of `soft_evidence_log_prob`."""
+        from .squared_soft_posterior import soft_posterior_marginals
+
+        return soft_posterior_marginals(self, log_lik, x, soft_vars=soft_vars, integrate_vars=integrate_vars,
+                                        return_log_evidence=return_log_evidence, rows_per_chunk=rows_per_chunk)
+
+    def sample_soft(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, integrate_vars=None,
+                    seed: int | None = None, order=None, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, D)`` int64: the soft variables of every row drawn exactly from ``p(x_S | lambda, x_O)``, proportional to
+        ``|c(x)|^2 prod_v lambda_v(x_v)`` with `integrate_vars` summed out; observed entries are returned untouched, integrated
+        columns as given (0 where `x` is None).  With 0 / ``-inf`` weights this is exact truncated sampling.  `order`: a
+        permutation of the soft variables (``ValueError`` otherwise; default `tree_order` restricted to them); an order that
+        leaves a fold beside a variable's path with some soft variables drawn and others not is a ``NotImplementedError``, raised
+        while planning (`tree_order` never does).  `seed` and the Philox counters as `sample_conditional`: the draws depend on the
+        seed and the order only.  A row without mass, with an absent observed entry or with a NaN / ``+inf`` among its read weights
+        gets -1 in every soft column.  Per chunk one soft bottom-up pass (`last_soft_launches`, `last_launches`), then per variable
+        ``c``'s forward and one `ck_squared_path_soft_bwd` launch (`last_mixed_launches`: the steps' own mixed launches, 0 in
+        `tree_order` without integrated variables)."""
+        from .squared_soft_posterior import sample_soft
+
+        return sample_soft(self, log_lik, x, soft_vars=soft_vars, integrate_vars=integrate_vars, seed=seed, order=order,
+                           rows_per_chunk=rows_per_chunk)
 
     def interval_log_prob(self, lo: torch.Tensor, hi: torch.Tensor, x: torch.Tensor | None = None, *, box_vars=None, integrate_vars=None,
                           normalized: bool = True, rows_per_chunk: int | None = None) -> torch.Tensor:

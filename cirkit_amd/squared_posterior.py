@@ -82,16 +82,19 @@ class DownTables:
     vars_dev: torch.Tensor
 
 
-def host_plan(plan: Plan, qvars, mask: np.ndarray, const_available=None, graph: FoldGraph | None = None) -> DownPlan:
+def host_plan(plan: Plan, qvars, mask: np.ndarray, const_available=None, graph: FoldGraph | None = None,
+              soft: np.ndarray | None = None) -> DownPlan:
     """The down folds of the query variables `qvars`, the mixed plan of ``M`` = `mask` (which holds them) and the layers to
     launch.  ``NotImplementedError`` where `path_plan` raises it: a variable read by several input folds, a fold above a query
-    variable with several readers."""
+    variable with several readers.  `soft` (cirkit_amd/squared_soft_posterior.py): the query variables carry a weight per state
+    instead of being integrated -- `mask` then holds the integrated variables alone and the mixed plan is the soft one, leaves
+    included."""
     graph = graph_of(plan, graph)
     qvars = sorted(int(v) for v in qvars)
     leaves = [graph.path(v).leaf for v in qvars]  # (the refusals come before anything is built)
     qbits = sum(1 << v for v in qvars)
     down = {(p, f) for p, row in enumerate(graph.bits) for f, b in enumerate(row) if b & qbits}
-    mp = mixed_plan(plan, mask, const_available, readers=down, graph=graph)
+    mp = mixed_plan(plan, mask, const_available, readers=down, graph=graph, soft=soft)
     layers = []
     for i in range(len(plan.layers) - 1, -1, -1):  # (children sit below their readers)
         fs = sorted(f for p, f in down if p == i)
@@ -130,9 +133,10 @@ def plan_of(sq, query_vars, integrate_vars) -> DownPlan:
     return dp
 
 
-def bind(sq, dp: DownPlan, B: int, bd_c, bd_z, tb: MixedTables) -> DownTables:
+def bind(sq, dp: DownPlan, B: int, bd_c, bd_z, tb: MixedTables, positions=None) -> DownTables:
     """The fold tables of every launch and the variable table of the leaf launch at batch size B, on the host and on the
-    device, and the layout of the down arena.  `tb`: `sq._tables` of the mixed plan at this batch size."""
+    device, and the layout of the down arena.  `tb`: `sq._tables` of the mixed plan at this batch size.  `positions`: per query
+    variable its position on the ``S`` axis of ``log_lik``, word 5 of its row (`ck_squared_soft_down_leaf`); None leaves it 0."""
     layers = sq.plan.layers
     weights = {dl.layer: sq._stage_weights(dl.layer, layers[dl.layer].num_output_units, layers[dl.layer].num_input_units)
                for dl in dp.layers if layers[dl.layer].type != "hadamard"}
@@ -171,6 +175,8 @@ def bind(sq, dp: DownPlan, B: int, bd_c, bd_z, tb: MixedTables) -> DownTables:
     vars_host = np.zeros((len(leaf), _LEAF), dtype=np.int64)
     for j, ((table, C, K, tlog), lf) in enumerate(zip(leaf, dp.leaves)):
         vars_host[j, :5] = (table.data_ptr() + lf[1] * (C + 1) * K * 4, C, K, tlog, off.get(lf, -1))
+    if positions is not None:
+        vars_host[:, 5] = positions
     return put_bounded(dp.dev, B, DownTables(key, launches, max(total, 1), vars_host, torch.from_numpy(vars_host).to(sq.device)), 2)
 
 
@@ -181,6 +187,17 @@ def _down_arena(sq, n: int) -> torch.Tensor:
         sq._down_buf = None
         a = sq._down_buf = torch.empty(n, dtype=torch.complex64 if sq._complex else torch.float32, device=sq.device)
     return a
+
+
+def launch_down(sq, bt: DownTables, arena: torch.Tensor, down: torch.Tensor, bd_c, bd_z, B: int) -> None:
+    """The `ck_squared_down_bwd` launches of `bt`, output layer first, over the mixed arena `arena` into the down arena `down`."""
+    stream = torch.cuda.current_stream(sq.device).cuda_stream
+    with torch.cuda.device(sq.device):
+        for la in bt.launches:
+            capi.call("ck_squared_down_bwd", arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(), down.data_ptr(), down.numel(),
+                      la.host.ctypes.data, la.dev.data_ptr(), la.n, la.H, None if la.w1 is None else la.w1.data_ptr(),
+                      None if la.w2 is None else la.w2.data_ptr(), 0 if la.w1 is None else int(la.w1.shape[0]), la.Ki,
+                      la.Ko, la.stages, B, sq.rows_per_block, 1 if sq._complex else 0, stream)
 
 
 def _chunk(sq, dp: DownPlan, xw: torch.Tensor, out: torch.Tensor, ev: torch.Tensor, mark=None) -> None:
@@ -206,13 +223,9 @@ def _chunk(sq, dp: DownPlan, xw: torch.Tensor, out: torch.Tensor, ev: torch.Tens
     down = _down_arena(sq, bt.total)
     stream = torch.cuda.current_stream(sq.device).cuda_stream
     cplx = 1 if sq._complex else 0
+    launch_down(sq, bt, arena, down, bd_c, bd_z, B)
+    mark("down")
     with torch.cuda.device(sq.device):
-        for la in bt.launches:
-            capi.call("ck_squared_down_bwd", arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(), down.data_ptr(), down.numel(),
-                      la.host.ctypes.data, la.dev.data_ptr(), la.n, la.H, None if la.w1 is None else la.w1.data_ptr(),
-                      None if la.w2 is None else la.w2.data_ptr(), 0 if la.w1 is None else int(la.w1.shape[0]), la.Ki,
-                      la.Ko, la.stages, B, sq.rows_per_block, cplx, stream)
-        mark("down")
         capi.call("ck_squared_down_leaf", down.data_ptr(), down.numel(), bt.vars_host.ctypes.data, bt.vars_dev.data_ptr(),
                   len(dp.qvars), int(out.shape[2]), out.data_ptr(), B, cplx, stream)
     mark("leaf")

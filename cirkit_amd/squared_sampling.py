@@ -32,12 +32,13 @@ from .squared import INTEGRATED, MIXED, MixedPlan, _mask_of, mixed_plan, put_bou
 from .squared_graph import PathLevel, PathPlan, fold_class, mask_bits, path_plan, scope_bits, tree_order  # noqa: F401 (also for callers)
 
 _HEAD = capi.CK_SQ_PATH_LEVEL_WORDS
+UNDRAWN = 3  # beside OBSERVED / INTEGRATED / MIXED: a sibling whose soft variables are all still to draw (`sample_soft`)
 
 
 @dataclass
 class StepPlan:
-    """One step: the path of its variable, per (level, sibling) the class of the sibling for the step's integrated set, and
-    the mixed folds (if any) the siblings need evaluated first."""
+    """One step: the path of its variable, per (level, sibling) the class of the sibling for the step's integrated set (UNDRAWN:
+    read from the soft pass of the chunk), and the mixed folds (if any) the siblings need evaluated first."""
 
     path: PathPlan
     cls: list[list[int]]
@@ -50,6 +51,7 @@ class OrderPlan:
     max_siblings: int
     max_levels: int
     dev: dict = field(default_factory=dict)  # batch size -> `PathTables`
+    soft_pos: dict | None = None  # (`sample_soft`) variable -> its position on the S axis of log_lik
 
 
 @dataclass
@@ -63,6 +65,8 @@ class PathTables:
     launches: list  # per step a list of `MixedLaunch`, or None
     arena: torch.Tensor | None
     mid: torch.Tensor | None
+    base: int = 0  # (`sample_soft`) where the steps' own mixed folds start in `arena`: behind the soft pass's
+    soft: object = None  # (`sample_soft`) the `MixedTables` of the soft pass, without buffers of its own
 
 
 def _check_discrete(sq) -> None:
@@ -80,12 +84,26 @@ class _Sampler:
         self.orders: dict[bytes, OrderPlan] = {}
 
     # -- host plans ------------------------------------------------------------------------------------------------------------
-    def _step(self, v: int, integrated: np.ndarray) -> StepPlan:
-        """`integrated`: (D,) bool without v."""
+    def _step(self, v: int, integrated: np.ndarray, undrawn: np.ndarray | None = None, drawn: np.ndarray | None = None) -> StepPlan:
+        """`integrated`: (D,) bool without v.  `undrawn` / `drawn` (`sample_soft`): the soft variables still to draw after v and
+        those drawn before it.  A sibling that holds undrawn ones and no drawn one is UNDRAWN: its value is the soft pass's.  One
+        that holds no undrawn one is classified against `integrated` as ever.  One that holds both is refused."""
         sq, path = self.sq, self.graph.path(v)
         mbits = mask_bits(integrated)
+        ubits = 0 if undrawn is None else mask_bits(undrawn)
+        dbits = 0 if drawn is None else mask_bits(drawn)
         const = sq._const_available()
-        cls = [[fold_class(self.graph.bits[p][g], mbits) for p, g in lv.siblings] for lv in path.levels]
+        cls = []
+        for lv in path.levels:
+            row = []
+            for p, g in lv.siblings:
+                b = self.graph.bits[p][g]
+                if b & ubits and b & dbits:
+                    raise NotImplementedError(f"HipSquaredCircuit.sample_soft: when variable {v} is drawn, fold {g} of layer {p} beside its "
+                                              "path holds soft variables that are drawn and others that are not; the order must draw "
+                                              "all soft variables of a sibling before or after the variable (tree_order does)")
+                row.append(UNDRAWN if b & ubits else fold_class(b, mbits))
+            cls.append(row)
         need = any(c == MIXED or (c == INTEGRATED and not const(p))
                    for lv, row in zip(path.levels, cls) for (p, _), c in zip(lv.siblings, row))
         mp = None
@@ -95,36 +113,50 @@ class _Sampler:
             mp = mixed_plan(sq.plan, m, const, path=path.folds(), graph=self.graph)
         return StepPlan(path, cls, mp)
 
-    def order_plan(self, order: list[int], integrated: np.ndarray) -> OrderPlan:
+    def order_plan(self, order: list[int], integrated: np.ndarray, soft: np.ndarray | None = None) -> OrderPlan:
         """The steps of drawing `order` one variable after the other; `integrated`: what stays integrated out throughout
-        (nothing, for the samplers).  Cached on the bytes of both."""
+        (nothing, for the samplers).  `soft` (`sample_soft`): `order` is a permutation of these variables, which carry a weight
+        per state: the ones still to draw are not integrated but read from the soft pass.  Cached on the bytes of all three."""
         key = np.asarray(order, dtype=np.int64).tobytes() + b"|" + np.packbits(integrated).tobytes()
+        if soft is not None:
+            key += b"|soft|" + np.packbits(soft).tobytes()
         op = self.orders.get(key)
         if op is None:
             for v in order:  # (the refusals come before anything is built)
                 self.graph.path(v)
             left = integrated.copy()
-            left[order] = True
             steps = []
-            for v in order:
-                left[v] = False
-                steps.append(self._step(v, left))
+            if soft is None:
+                left[order] = True
+                for v in order:
+                    left[v] = False
+                    steps.append(self._step(v, left))
+            else:
+                undrawn, drawn = soft.copy(), np.zeros_like(soft)
+                for v in order:
+                    undrawn[v] = False
+                    steps.append(self._step(v, left, undrawn, drawn))
+                    drawn[v] = True
             op = put_bounded(self.orders, key, OrderPlan(steps, max([len(lv.siblings) for s in steps for lv in s.path.levels] + [0]),
                                                          max([len(s.path.levels) for s in steps] + [1])), 8)
+            if soft is not None:
+                op.soft_pos = {int(v): j for j, v in enumerate(np.nonzero(soft)[0])}
         return op
 
-    def row_bytes(self, op: OrderPlan) -> int:
+    def row_bytes(self, op: OrderPlan, soft: MixedPlan | None = None) -> int:
+        """Bytes per row of c's arena and the largest mixed arena of a step; with `soft`, the soft pass's arena in front of it."""
         sq = self.sq
         n = sum(l.num_folds * l.num_output_units for l in sq.plan.layers)
         extra = 0
         for s in op.steps:
             if s.mixed is not None:
                 extra = max(extra, sq._row_bytes(s.mixed) // sq._esize - n)
-        return (n + extra) * sq._esize
+        return (n + extra) * sq._esize + (0 if soft is None else sq._row_bytes(soft) - n * sq._esize)
 
     # -- device tables -----------------------------------------------------------------------------------------------------------
-    def bind(self, op: OrderPlan, B: int, bd_c, bd_z) -> PathTables:
-        """The `PathTables` of an order at batch size B."""
+    def bind(self, op: OrderPlan, B: int, bd_c, bd_z, soft: MixedPlan | None = None) -> PathTables:
+        """The `PathTables` of an order at batch size B.  `soft` (`sample_soft`): the mixed plan of the chunk's soft pass; its
+        arena is the front of the one arena the path launches read, the steps' own mixed folds lie behind it (`PathTables.base`)."""
         sq = self.sq
         layers = sq.plan.layers
         weights = {}
@@ -140,6 +172,10 @@ class _Sampler:
         W = _HEAD + 2 * op.max_siblings
         host = np.zeros((len(op.steps), op.max_levels, W), dtype=np.int64)
         launches, total, mid = [], 1, 0
+        stb = None if soft is None else sq._tables(soft, B, bd_c, bd_z, alloc=False)
+        base = 0 if stb is None else (stb.total + 3) // 4 * 4
+        if stb is not None:
+            mid = stb.mid_size
         for si, s in enumerate(op.steps):
             tb = None if s.mixed is None else sq._tables(s.mixed, B, bd_c, bd_z, alloc=False)
             launches.append(None if tb is None else tb.launches)
@@ -156,19 +192,30 @@ class _Sampler:
                     row[3] = K
                 row[1], row[2], row[6] = lv.fold, K, len(lv.siblings)
                 for h, ((p, g), c) in enumerate(zip(lv.siblings, s.cls[li])):
-                    row[_HEAD + 2 * h: _HEAD + 2 * h + 2] = sq.child(p, g, K, B, c, tb, bd_c, bd_z)
+                    if c == UNDRAWN:  # the soft pass evaluated it (its scope meets the soft set): FULL in the front of the arena
+                        kd, o = sq.child(p, g, K, B, MIXED, stb, bd_c, bd_z)
+                        if kd != capi.CK_SQ_FULL:
+                            raise RuntimeError(f"HipSquaredCircuit: the soft pass did not evaluate fold {g} of layer {p}")
+                    else:
+                        kd, o = sq.child(p, g, K, B, c, tb, bd_c, bd_z)
+                        o += base if kd == capi.CK_SQ_FULL else 0
+                    row[_HEAD + 2 * h: _HEAD + 2 * h + 2] = (kd, o)
         dt = torch.complex64 if sq._complex else torch.float32
-        any_mixed = any(la is not None for la in launches)
+        any_mixed = stb is not None or any(la is not None for la in launches)
         return put_bounded(op.dev, B, PathTables(key, host, torch.from_numpy(host).to(sq.device), launches,
-                                                 torch.empty(total, dtype=dt, device=sq.device) if any_mixed else None,
-                                                 torch.empty(mid, dtype=dt, device=sq.device) if mid else None), 2)
+                                                 torch.empty(base + total, dtype=dt, device=sq.device) if any_mixed else None,
+                                                 torch.empty(mid, dtype=dt, device=sq.device) if mid else None, base, stb), 2)
 
     # -- the steps ---------------------------------------------------------------------------------------------------------------
     def run(self, op: OrderPlan, xw: torch.Tensor, *, out: torch.Tensor | None = None, dead: torch.Tensor | None = None,
-            log_m: torch.Tensor | None = None, seed: int = 0, row0: int = 0) -> None:
+            log_m: torch.Tensor | None = None, seed: int = 0, row0: int = 0, soft: MixedPlan | None = None,
+            log_lik: torch.Tensor | None = None) -> None:
         """Every step of `op` on the rows `xw` (B, D) int64, contiguous, negative entries cleaned: c's forward, the mixed
         launches the step needs, the path launch -- which writes ``log m`` into `log_m` (B, C) and / or draws into column v
-        of `out` and of `xw` itself, so that the next forward reads the draw.  Nothing here waits for the device."""
+        of `out` and of `xw` itself, so that the next forward reads the draw.  Nothing here waits for the device.
+        `soft`, `log_lik` (B, S, C) fp32 (`sample_soft`): behind the first forward -- nothing is drawn yet -- the soft pass of
+        the chunk runs once into the front of the arena, which stays alive over the steps; every path launch then adds the
+        weights of its own variable (`ck_squared_path_soft_bwd`)."""
         sq = self.sq
         B, D = int(xw.shape[0]), int(xw.shape[1])
         bd_z = sq._z_binding()
@@ -178,19 +225,32 @@ class _Sampler:
         for si, s in enumerate(op.steps):
             bd_c = sq.c._run(xw)
             if tb is None or tb.key[0] != bd_c.arena.data_ptr():
-                tb = self.bind(op, B, bd_c, bd_z)
+                if soft is not None and si > 0:
+                    raise RuntimeError("HipSquaredCircuit: c's arena moved between two steps of a chunk; the soft pass's values are gone")
+                tb = self.bind(op, B, bd_c, bd_z, soft)
             arena = tb.arena
+            if soft is not None and si == 0:
+                from .squared_soft import launch_leaves
+
+                sq.last_soft_launches += launch_leaves(sq, tb.soft, B, log_lik, None, None, arena=arena)
+                sq.last_launches += sq._launch_mixed(tb.soft.launches, arena, tb.mid, bd_c, bd_z, B)
             if tb.launches[si] is not None:
-                sq.last_mixed_launches += sq._launch_mixed(tb.launches[si], arena, tb.mid, bd_c, bd_z, B)
+                sq.last_mixed_launches += sq._launch_mixed(tb.launches[si], arena[tb.base:] if tb.base else arena, tb.mid, bd_c, bd_z, B)
             pl, fl = s.path.leaf
             table, C, K, tlog = sq._leaf_table(pl)
             L = len(s.path.levels)
+            head = (None if arena is None else arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(),
+                    tb.host[si].ctypes.data if L else None, tb.dev[si].data_ptr() if L else None, L, op.max_siblings,
+                    table.data_ptr(), fl, C, K, tlog)
+            tail = (None if log_m is None else log_m.data_ptr(), xw.data_ptr(),
+                    None if out is None else out.data_ptr(), None if dead is None else dead.data_ptr(), D, s.path.var,
+                    int(fold_base[pl]) + fl, seed, row0, B, sq.rows_per_block, 1 if sq._complex else 0, stream)
             with torch.cuda.device(sq.device):
-                capi.call("ck_squared_path_bwd", None if arena is None else arena.data_ptr(), bd_z.arena.data_ptr(), bd_c.arena.data_ptr(),
-                          tb.host[si].ctypes.data if L else None, tb.dev[si].data_ptr() if L else None, L, op.max_siblings,
-                          table.data_ptr(), fl, C, K, tlog, None if log_m is None else log_m.data_ptr(), xw.data_ptr(),
-                          None if out is None else out.data_ptr(), None if dead is None else dead.data_ptr(), D, s.path.var,
-                          int(fold_base[pl]) + fl, seed, row0, B, sq.rows_per_block, 1 if sq._complex else 0, stream)
+                if soft is None:
+                    capi.call("ck_squared_path_bwd", *head, *tail)
+                else:
+                    capi.call("ck_squared_path_soft_bwd", *head, log_lik.data_ptr(), int(log_lik.shape[1]), int(log_lik.shape[2]),
+                              op.soft_pos[s.path.var], *tail)
 
 
 def sampler(sq) -> _Sampler:

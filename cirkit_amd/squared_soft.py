@@ -12,9 +12,9 @@ the mixed pass of `log_marginal` reads as a FULL child (`squared.mixed_plan` wit
 evaluated, nothing else changes.  A box ``lo <= x_v <= hi`` is the 0/1 case of the same leaf launch, read from the bounds
 themselves: no ``(B, S, C)`` tensor is built.  The reference has no such query, as for `HipCircuit`'s soft and interval evidence.
 
-Out of scope: posteriors, sampling and MPE under soft evidence; fusing the leaf Gram into the first product layer, so that the
-``|S| K^2`` block of a row is never written; exploiting the Gram's symmetry; Gaussian boxes (Gaussian variables stay hard evidence
-or integrated); per-row soft sets; gradients.
+Posteriors and sampling under soft evidence: cirkit_amd/squared_soft_posterior.py.  Out of scope: MPE under soft evidence; fusing
+the leaf Gram into the first product layer, so that the ``|S| K^2`` block of a row is never written; exploiting the Gram's
+symmetry; Gaussian boxes (Gaussian variables stay hard evidence or integrated); per-row soft sets; gradients.
 """
 
 from __future__ import annotations
@@ -105,9 +105,11 @@ def unit_maxima(sq) -> dict:
     return sq._soft_side[1]
 
 
-def launch_leaves(sq, tb: MixedTables, B: int, log_lik, lo, hi, form: int = 0) -> int:
-    """The leaf launches of `tb` into its arena -- soft evidence from `log_lik` (B, S, C) fp32, or a box from `lo` / `hi`
-    (B, D) int64; how many there were.  `form` 1 forces the plain form (scripts/bench_squared_soft.py)."""
+def launch_leaves(sq, tb: MixedTables, B: int, log_lik, lo, hi, form: int = 0, arena: torch.Tensor | None = None) -> int:
+    """The leaf launches of `tb` into its arena (or `arena`, where the caller brings one) -- soft evidence from `log_lik`
+    (B, S, C) fp32, or a box from `lo` / `hi` (B, D) int64; how many there were.  `form` 1 forces the plain form
+    (scripts/bench_squared_soft.py)."""
+    arena = tb.arena if arena is None else arena
     side = unit_maxima(sq)
     stream = torch.cuda.current_stream(sq.device).cuda_stream
     with torch.cuda.device(sq.device):
@@ -123,7 +125,7 @@ def launch_leaves(sq, tb: MixedTables, B: int, log_lik, lo, hi, form: int = 0) -
                       (la.by_pos if soft else la.by_var).ctypes.data, (la.by_pos_dev if soft else la.by_var_dev).data_ptr(), la.n,
                       log_lik.data_ptr() if soft else None, int(log_lik.shape[1]) if soft else 0, int(log_lik.shape[2]) if soft else 0,
                       None if soft else lo.data_ptr(), None if soft else hi.data_ptr(), 0 if soft else int(lo.shape[1]),
-                      tb.arena.data_ptr() + la.base * sq._esize, B, sq.rows_per_block, 1 if sq._complex else 0, form, stream)
+                      arena.data_ptr() + la.base * sq._esize, B, sq.rows_per_block, 1 if sq._complex else 0, form, stream)
     return len(tb.leaves)
 
 
@@ -174,29 +176,42 @@ def _evaluate(sq, mp: MixedPlan, xw, bad, B: int, pieces, normalized: bool, rows
     return torch.where(bad, torch.full((), float("nan"), device=sq.device), out)
 
 
-def soft_evidence_log_prob(sq, log_lik, x=None, *, soft_vars=None, integrate_vars=None, normalized=True, rows_per_chunk=None,
-                           form: int = 0) -> torch.Tensor:
+def soft_weights(sq, log_lik, soft: np.ndarray):
+    """What every query under soft evidence checks of ``log_lik`` (rank, dtype, the ``S`` axis, enough states) before anything is
+    allocated: the batch size and `pieces(r0, r1)`, which gives the rows r0 .. r1 on the device as contiguous fp32 and the rows
+    among them with a NaN or ``+inf`` in a read entry (those rows alone are NaN)."""
     from .soft_evidence import check_arguments
 
-    soft, integrate = _sets(sq, soft_vars, integrate_vars, "soft evidence")
     ids = np.nonzero(soft)[0].tolist()
-    check_arguments(sq.plan, log_lik, None, ids)  # (rank, dtype, S; x is checked against this circuit's own rules below)
+    check_arguments(sq.plan, log_lik, None, ids)  # (rank, dtype, S; x is checked against this circuit's own rules)
     B, _, Cl = (int(n) for n in log_lik.shape)
     counts = np.asarray([states_of(sq.graph, v) for v in ids])
     if Cl < counts.max():
         raise ValueError(f"log_lik has {Cl} states, the soft variables have up to {int(counts.max())}")
-    xw, bad = _rows(sq, x, B, soft, integrate)
-    mp = soft_plan(sq, integrate, soft)
     read = None  # the entries a row reads, where the soft variables do not all have C states
     if (counts != Cl).any():
         read = torch.from_numpy(np.arange(Cl)[None, :] < counts[:, None]).to(sq.device)
 
     def pieces(r0, r1):
         ll = log_lik[r0:r1].to(sq.device).to(torch.float32).contiguous()
-        wrong = torch.isnan(ll) | (ll == float("inf"))  # (a NaN or +inf in a read entry: that row alone is NaN)
+        wrong = torch.isnan(ll) | (ll == float("inf"))
         if read is not None:
             wrong &= read
-        return ll, None, None, wrong.flatten(1).any(dim=1)
+        return ll, wrong.flatten(1).any(dim=1)
+
+    return B, int(counts.max()), pieces
+
+
+def soft_evidence_log_prob(sq, log_lik, x=None, *, soft_vars=None, integrate_vars=None, normalized=True, rows_per_chunk=None,
+                           form: int = 0) -> torch.Tensor:
+    soft, integrate = _sets(sq, soft_vars, integrate_vars, "soft evidence")
+    B, _, weights = soft_weights(sq, log_lik, soft)
+    xw, bad = _rows(sq, x, B, soft, integrate)
+    mp = soft_plan(sq, integrate, soft)
+
+    def pieces(r0, r1):
+        ll, wrong = weights(r0, r1)
+        return ll, None, None, wrong
 
     return _evaluate(sq, mp, xw, bad, B, pieces, normalized, rows_per_chunk, form)
 

@@ -1691,6 +1691,34 @@ int ck_squared_soft_leaf(const float* table, int num_folds, int C, int K, int ta
                          const int32_t* tab, int n, const float* log_lik, int S, int C_lik, const int64_t* lo, const int64_t* hi, int D,
                          float* out, int B, int rows_per_block, int complex_values, int form, void* stream);
 
+/* ---- posteriors and sampling under soft evidence of squared circuits ("Posteriors and sampling under soft
+ * evidence of squared circuits"; additive, ABI 51).  Replaces: nothing -- the reference has no such query.
+ * The leaves of ck_squared_down_bwd's walk over a SOFT bottom-up pass: the G that reaches the input fold of a soft variable holds
+ * the weight of every other variable and not its own, so
+ *     log_m[b, q, s] = log_lik[b, pos_q, s] + log max(0, sum_kl e[k][l] a_k(s) a_l(s)) + gmax (+ 2 tm_s),   e = Re exp(G - gmax),
+ * with the shifts and the clamp of ck_squared_down_leaf; columns past a variable's own C are -inf.  vars / vars_host: the rows of
+ * ck_squared_down_leaf with [5] = pos_q, the variable's position on the S axis of log_lik (B, S, C_lik) fp32; every C <= C_lik,
+ * every position inside S, every offset inside down_elems (checked on the host words before the launch).
+ * form 1, and every K != 32: the plain form -- ck_squared_down_leaf's arithmetic with the weight added, a workgroup takes one
+ * variable and rows_per_block rows one after the other; CK_ERR_UNSUPPORTED above 160 KiB of LDS.  form 0 with every K = 32 and the
+ * tables of the launch ALL of logarithms or ALL of linear values (a launch that mixes the two takes the plain form): the quadratic
+ * form on v_mfma_f32_32x32x2_f32 in exact fp32.  A workgroup takes one variable and rows_per_block rows (rounded up to 16) and
+ * stages the variable's table once per slab of 128 states (a table of logarithms exponentiated with its per-state shift tm_s,
+ * states past C as zeros); a wave takes a row, holds e as the A operands of the 16 steps and computes D[l][s] = sum_k e[l][k] a_k(s)
+ * per tile of 32 states; lane (s, half) then holds 16 of the 32 l of its state: m(s) = sum_l a_l(s) D[l][s] is 16 FMAs in registers
+ * and one add across the halves.  A row's result does not depend on its place in a workgroup, on B or on rows_per_block. */
+int ck_squared_soft_down_leaf(const float* down, int64_t down_elems, const int64_t* vars_host, const int64_t* vars, int nq, int C_max,
+                              const float* log_lik, int S, int C_lik, float* log_m, int B, int rows_per_block, int complex_values,
+                              int form, void* stream);
+
+/* ck_squared_path_bwd with the log weight of the variable's own states added before log_m is written and before the draw:
+ * log_lik (B, S, C_lik >= C) fp32, row b reads [b, pos, 0 .. C - 1].  Everything else as ck_squared_path_bwd, kernels included. */
+int ck_squared_path_soft_bwd(const float* full, const float* cst, const float* rank1, const int64_t* levels_host, const int64_t* levels,
+                             int L, int max_siblings, const float* table, int64_t leaf_fold, int C, int K, int table_log,
+                             const float* log_lik, int S, int C_lik, int pos, float* log_m, int64_t* x, int64_t* x_out, int32_t* dead,
+                             int D, int var, int node, uint64_t seed, int64_t row0, int B, int rows_per_block, int complex_values,
+                             void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
