@@ -26,6 +26,7 @@ CK_UNARY_CLAMP = 5
 CK_UNARY_SOFTPLUS = 6
 CK_SQ_FULL, CK_SQ_CONST, CK_SQ_RANK1 = range(3)  # child kinds of ck_squared_mixed_fwd
 CK_SQ_PATH_LEVEL_WORDS, CK_SQ_PATH_STAGES = 8, 1  # a level of ck_squared_path_bwd
+CK_SQ_STEP_LEAF_WORDS = 8  # a step of ck_squared_path_steps
 CK_SQ_DOWN_FOLD_WORDS, CK_SQ_DOWN_LEAF_WORDS = 2, 6  # a fold of ck_squared_down_bwd, a variable of ck_squared_down_leaf
 CK_SQ_LOO_FOLD_WORDS, CK_SQ_LOO_LEAF_WORDS = 2, 6  # a fold of ck_squared_loo_down, a variable of ck_squared_loo_leaf
 CK_SQ_LOO_TABLE, CK_SQ_LOO_NORMALISED, CK_SQ_LOO_ENTRY = range(3)  # modes of ck_squared_loo_leaf
@@ -382,6 +383,7 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_squared_soft_down_leaf": [_p, _l, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _p],
     "ck_squared_path_soft_bwd": [_p, _p, _p, _p, _p, _i, _i, _p, _l, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _i, _i, C.c_uint64, _l,
                                  _i, _i, _i, _p],
+    "ck_squared_path_steps": [_p, _p, _p, _p, _p, _l, _i, _p, _p, _i, _i, _p, _i, _p, _p, _l, _l, _p, _l, _l, _p, _l, _l, _i, _i, _i, _i, _p],
     "ck_em_job_blocks": [_i, _l, _i],
     "ck_em_update": [_p, _p, _i, _f, _f, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],

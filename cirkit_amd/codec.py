@@ -1,7 +1,8 @@
 """Lossless compression with a circuit: `compress` / `decompress` ("Autoregressive conditionals and
 coding").
 
-The model side is `HipCircuit.coding_tables`: per row and step of an order of the variables, the integer cumulative
+The model side is `HipCircuit.coding_tables`, or `HipSquaredCircuit.coding_tables` for a squared circuit ``|c(x)|^2 / Z`` (order
+``None`` is then its `tree_order`; `compress` / `decompress` take either class): per row and step of an order of the variables, the integer cumulative
 frequency table of ``p(X_{order[i]} | x_{order[:i]})``.  The coder side is here: a range ANS coder (Duda's rANS in its
 64-bit-state, 32-bit-renormalisation form) in numpy, one stream per row, vectorised over the rows, with no GPU dependency --
 it takes its tables through a provider callable ``tables(step, x_so_far) -> (B, C + 1)``, so the CPU tests drive it from the
@@ -155,10 +156,20 @@ def ideal_bits(counts: np.ndarray, precision: int) -> np.ndarray:
 
 
 # -- the circuit as the provider ----------------------------------------------------------------------------------------------
+def _squared(hc) -> bool:
+    from .squared import HipSquaredCircuit
+
+    return isinstance(hc, HipSquaredCircuit)
+
+
 def _order(hc: "HipCircuit", order) -> list[int]:
     from .autoregressive import check_order
     from .topdown import variable_kinds
 
+    if _squared(hc):  # (a permutation of all variables; None: `tree_order`)
+        from .squared_autoregressive import check_query
+
+        return check_query(hc, order, None)[2]
     return check_order(variable_kinds(hc.plan), hc.plan.num_variables, order)
 
 
@@ -167,6 +178,13 @@ def _check(hc: "HipCircuit", order, precision: int) -> list[int]:
     from .sampling import check_plan
     from .topdown import variable_kinds
 
+    if _squared(hc):  # (Gaussian inputs and ancestries that are no paths are refused by `check_query`; every input is discrete)
+        from .squared_autoregressive import check_query
+
+        ids = check_query(hc, order, None, None, precision)[2]
+        if len(ids) > max_steps(precision):
+            raise ValueError(f"{len(ids)} symbols per row exceed the {max_steps(precision)} that precision {precision} bounds")
+        return ids
     check_plan(hc.user_plan)
     ids = _order(hc, order)
     if any("gaussian" in variable_kinds(hc.plan)[v] for v in ids):

@@ -1,5 +1,5 @@
 // What the walks down a squared circuit share (ck_sqpath.hip: one path, root to one input fold, in one launch; ck_sqdown.hip: every
-// fold above a set of query variables, one launch per layer): the siblings of a fold read by kind (sp_siblings), one transposed
+// fold above a set of query variables, one launch per layer; ck_sqar.hip: the paths of many steps of an order in one launch): the siblings of a fold read by kind (sp_siblings), one transposed
 // TensorDot stage between two LDS blocks (sp_stage) and the leaf form over all states of a variable (sp_leaf), with their
 // helpers.  Carved out of ck_sqpath.hip as ck_td.h was out of ck_backward_c.hip; every translation unit gets its own copy.
 #pragma once

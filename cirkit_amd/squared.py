@@ -249,7 +249,10 @@ class HipSquaredCircuit:
     `soft_evidence_log_prob`, `interval_log_prob` and `log_cdf` put a weight per state, or a box, on any set of discrete variables
     (DAG region graphs included; Gaussian variables stay hard evidence or integrated); `soft_query_log_marginals`,
     `soft_posterior_marginals` and `sample_soft` give the posteriors of all soft variables and exact joint draws under that
-    evidence (trees only, as `posterior_marginals`).  Not
+    evidence (trees only, as `posterior_marginals`).
+    `autoregressive_conditionals`, `autoregressive_log_probs` and `coding_tables` give the chain rule along an order for rows that
+    are known -- one forward of ``c`` and one launch for all steps in `tree_order` -- and cirkit_amd/codec.py compresses with them
+    (discrete inputs, trees).  Not
     offered: per-row masks, gradients with respect to parameters; ``c``'s forward and the mixed pass are separate launches."""
 
     def __init__(self, plan_c: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0", rows_per_block: int = 1) -> None:
@@ -715,3 +718,40 @@ class HipSquaredCircuit:
         from .squared_sampling import sample_conditional
 
         return sample_conditional(self, x, sample_vars, seed=seed, order=order, rows_per_chunk=rows_per_chunk)
+
+    # -- the chain rule along an order, coding (cirkit_amd/squared_autoregressive.py) ----------------------------------------------
+    def autoregressive_conditionals(self, x: torch.Tensor, order=None, *, positions=None, integrate_vars=None,
+                                    rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, P, C)`` fp32: ``[b, j, s] = log p(X_{order[i]} = s | x_{order[:i]})`` at ``i = positions[j]``, every row
+        normalised over ``s`` by its own logsumexp as `posterior` does; columns past a variable's own state count are -inf.
+        `order`: a permutation of the variables outside `integrate_vars` (``ValueError`` otherwise; default `tree_order`
+        restricted to them); `integrate_vars`: one set per call, integrated out at every step; `positions`: the steps wanted
+        (None: all; ids, a range or a bool mask over the steps).  Per chunk of rows ONE forward of ``c`` and, in `tree_order`,
+        ONE launch over (row, step) (`last_mixed_launches` stays 0); a step whose siblings the order splits runs its mixed
+        launches and its own launch.  A row with a negative or out-of-range entry at a variable that a selected step observes
+        is NaN in every entry; a prefix without mass gives NaN.  Accuracy: that of `posterior`.  The results do not depend
+        on `rows_per_chunk` or `rows_per_block`.  ``NotImplementedError``: Gaussian inputs, ancestries that are not paths."""
+        from .squared_autoregressive import autoregressive_conditionals
+
+        return autoregressive_conditionals(self, x, order, positions=positions, integrate_vars=integrate_vars, rows_per_chunk=rows_per_chunk)
+
+    def autoregressive_log_probs(self, x: torch.Tensor, order=None, *, positions=None, integrate_vars=None,
+                                 rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, P)`` fp32: ``log p(x_{order[i]} | x_{order[:i]})`` of the row's own states, formed inside the leaf as
+        ``log m(x_v) - logsumexp_s log m(s)``: no ``(B, P, C)`` tensor exists.  Over all steps the columns sum to
+        ``log_prob(x)`` (nothing integrated).  Arguments, refusals and edge rows as `autoregressive_conditionals`; the entry at
+        the last selected step's own variable is read too."""
+        from .squared_autoregressive import autoregressive_log_probs
+
+        return autoregressive_log_probs(self, x, order, positions=positions, integrate_vars=integrate_vars, rows_per_chunk=rows_per_chunk)
+
+    def coding_tables(self, x: torch.Tensor, order=None, *, positions=None, integrate_vars=None, precision: int = 16,
+                      rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, P, C + 1)`` int32 cumulative frequency tables of `autoregressive_conditionals` at ``2**precision`` counts, the
+        contract of `HipCircuit.coding_tables`: ``[..., 0] = 0``, ``[..., C] = 2**precision``, every state of the step's
+        variable at least one count (`ck_ar_quantise` on ``exp`` of the conditionals, a chunk of steps at a time).  A NaN row
+        gets the uniform table.  What cirkit_amd/codec.py codes with."""
+        from .squared_autoregressive import coding_tables
+
+        return coding_tables(self, x, order, positions=positions, integrate_vars=integrate_vars, precision=precision,
+                             rows_per_chunk=rows_per_chunk)

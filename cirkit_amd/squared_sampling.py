@@ -67,6 +67,7 @@ class PathTables:
     mid: torch.Tensor | None
     base: int = 0  # (`sample_soft`) where the steps' own mixed folds start in `arena`: behind the soft pass's
     soft: object = None  # (`sample_soft`) the `MixedTables` of the soft pass, without buffers of its own
+    leaf: object = None  # (squared_autoregressive.py) the per-step leaf words of `ck_squared_path_steps`: (key, host, device)
 
 
 def _check_discrete(sq) -> None:

@@ -1719,6 +1719,30 @@ int ck_squared_path_soft_bwd(const float* full, const float* cst, const float* r
                              int D, int var, int node, uint64_t seed, int64_t row0, int B, int rows_per_block, int complex_values,
                              void* stream);
 
+/* ---- autoregressive conditionals of squared circuits ("Autoregressive conditionals and coding of squared
+ * circuits"; additive, ABI 51) ----
+ * The walk of ck_squared_path_bwd for num_steps steps of an order of the variables in ONE launch: workgroup (row tile, step)
+ * walks the path of the step's variable on the rows of the tile, same device functions in the same order, so log m is that
+ * entry's bit for bit.  Nothing is drawn; x (B, D) is only read.
+ * levels / levels_host: the level tables of the steps, step s at word s step_stride, each as ck_squared_path_bwd takes it.
+ * leaf / leaf_host: per step CK_SQ_STEP_LEAF_WORDS int64:
+ *     [0] device address of the input layer's (F, C + 1, K) fp32 table  [1] the input fold  [2] C  [3] K
+ *     [4] 1 a table of logarithms, 0 of linear values  [5] the variable  [6] the number L of levels  [7] 0
+ * Every step step0 .. step0 + num_steps - 1 is checked on the host words before anything is launched.  A step takes the 32-unit
+ * form or the shape-generic one by ck_squared_path_bwd's rule; where the steps differ there is one launch per form, and a
+ * workgroup whose step takes the other form returns at once.
+ * Outputs, each optional, column j = step - step0, fp32:
+ *     log_m    [b lm_row + j lm_step + s]  log m_b(s), s < C; -inf for C <= s < C_max
+ *     cond     [b cd_row + j cd_step + s]  log m_b(s) - logsumexp_s log m_b(s); -inf past C; NaN where no state has mass
+ *     log_prob [b lp_row + j lp_step]      cond at s = x[b, var]
+ * bad (B,) int32 or null: rows that are NaN in every entry of every output. */
+#define CK_SQ_STEP_LEAF_WORDS 8
+int ck_squared_path_steps(const float* full, const float* cst, const float* rank1, const int64_t* levels_host, const int64_t* levels,
+                          int64_t step_stride, int max_siblings, const int64_t* leaf_host, const int64_t* leaf, int step0, int num_steps,
+                          const int64_t* x, int D, const int32_t* bad, float* log_m, int64_t lm_row, int64_t lm_step, float* cond,
+                          int64_t cd_row, int64_t cd_step, float* log_prob, int64_t lp_row, int64_t lp_step, int C_max, int B,
+                          int rows_per_block, int complex_values, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
