@@ -36,7 +36,7 @@ from . import _capi as capi
 from .circuit import HipCircuit
 from .layers import (HipCategoricalLayer, HipCPTLayer, HipGaussianLayer, HipHadamardLayer, HipKroneckerLayer, HipSumLayer,
                      HipTuckerLayer)
-from .plan import Plan
+from .plan import Plan, resolve_fold_index
 from .train_state import DeviceOptState, FlatBuffers, TrainerSurface
 
 if TYPE_CHECKING:
@@ -343,9 +343,11 @@ class HipTrainer(TrainerSurface):
         layer-wise: every activation stays in the arena."""
         return self.circuit.log_likelihood_sum(x)
 
-    def _backward(self, B: int, gB: float, seed: torch.Tensor | None, with_opt: bool = False) -> None:
+    def _backward(self, B: int, gB: float, seed, with_opt: bool = False) -> None:
         """The backward launch list over the activations of the LAST forward at batch size B: gradients of
-        ``sum_b seed[b] * log p(x_b)`` (seed None: of ``-(1 / gB) sum_b log p(x_b)``) into `self.grads`."""
+        ``sum_b seed[b] * log p(x_b)`` (seed None: of ``-(1 / gB) sum_b log p(x_b)``) into `self.grads`.  A root of K units
+        (a class-conditional circuit) takes a seed of B x K values -- a tensor, or a callable ``seed(view, stream)`` that
+        writes the root's (B, K) gradient view itself; layer-wise form only."""
         c = self.circuit
         bd = c._bind(B)
         st = self._bind_backward(B)
@@ -358,13 +360,18 @@ class HipTrainer(TrainerSurface):
         for p in st.need_zero:
             capi.call("ck_fill_f32", gviews[p].data_ptr(), gviews[p].numel(), 0.0, stream)
         po, fo = int(c._out_pairs[0, 0]), int(c._out_pairs[0, 1])
-        if c.layers[po].num_output_units != 1:
+        units = c.layers[po].num_output_units
+        if units != 1 and seed is None:
             raise NotImplementedError("training needs a scalar output unit")
         capi.call("ck_fill_f32", gviews[po].data_ptr(), gviews[po].numel(), 0.0, stream)
         if seed is None:
             capi.call("ck_fill_f32", gviews[po][fo].data_ptr(), B, -1.0 / gB, stream)
+        elif callable(seed):  # (the class head, cirkit_amd/classification.py: it writes the (B, units) seed in place)
+            seed(gviews[po][fo], stream)
         else:  # (an arbitrary gradient of the outputs: `HipCircuitModule` under autograd)
-            gviews[po][fo].reshape(-1)[:B].copy_(seed.reshape(-1))
+            if seed.numel() != B * units:
+                raise ValueError(f"the seed holds {seed.numel()} values, the root has {B} rows of {units} units")
+            gviews[po][fo].reshape(-1).copy_(seed.reshape(-1))
         for i in range(len(c.layers) - 1, -1, -1):
             l = c.layers[i]
             if isinstance(l, (HipCategoricalLayer, HipGaussianLayer)):
@@ -538,11 +545,15 @@ class _CircuitFunction(torch.autograd.Function):
     def forward(ctx, module, x, *params):
         tr = module._trainer
         with torch.cuda.device(tr.device):
-            tr._forward(x)  # the training forward (what the backward needs stays on the device)
+            po, fo = int(tr.circuit._out_pairs[0, 0]), int(tr.circuit._out_pairs[0, 1])
+            units = tr.circuit.layers[po].num_output_units
+            if units == 1:
+                tr._forward(x)  # the training forward (what the backward needs stays on the device)
+            else:  # (K output units: the layer-wise forward as it is, there is no log-likelihood sum to take)
+                tr.circuit._run(x)
             B = int(x.shape[0])
             bd = tr.circuit._bind(B)
-            po, fo = int(tr.circuit._out_pairs[0, 0]), int(tr.circuit._out_pairs[0, 1])
-            y = bd.views[po][fo].reshape(B, 1, 1).clone()
+            y = bd.views[po][fo].reshape(B, 1, units).clone()
         module._generation += 1
         ctx.module, ctx.B, ctx.generation = module, B, module._generation
         return y
@@ -565,15 +576,20 @@ class HipCircuitModule(torch.nn.Module):
         m = HipCircuitModule(plan, tensors);  opt = torch.optim.Adam(m.parameters(), lr=0.01)
         loss = -m(batch).mean();  loss.backward();  opt.step()          # notebooks/learning-a-circuit.ipynb, cell 18
 
-    `forward` is the layer-wise HIP forward (``(B, 1, 1)`` log-likelihoods like ``TorchCircuit.forward``), `backward` the
+    `forward` is the layer-wise HIP forward (``(B, 1, K)`` log-likelihoods like ``TorchCircuit.forward``), `backward` the
     launch list of cirkit_amd/csrc/ck_backward.hip (`HipTrainer`), for ANY gradient of the outputs.  The parameters are
     ``nn.Parameter``s over the trainer's own storage (one flat buffer), so any torch optimizer updates the circuit in place.
     One forward at a time: its activations live in one arena, `backward` must run before the next `forward`.  Same
-    coverage as `HipTrainer` (real lse-sum circuits with one scalar output)."""
+    coverage as `HipTrainer` (real lse-sum circuits with one output fold); a root of K > 1 units -- a class-conditional
+    circuit, notebooks/generative-vs-discriminative-circuit.ipynb: ``F.cross_entropy(m(x)[:, 0, :], y).backward()`` --
+    always runs the layer-wise form."""
 
     def __init__(self, plan: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0") -> None:
         super().__init__()
-        self._trainer = HipTrainer(plan, tensors, device=device, optimizer="sgd", lr=0.0, jobs=False)  # (any output gradient)
+        out = resolve_fold_index(plan.output, [l.num_folds for l in plan.layers]).reshape(-1, 2)
+        multi = any(plan.layers[int(p)].num_output_units != 1 for p in out[:, 0])
+        self._trainer = HipTrainer(plan, tensors, device=device, optimizer="sgd", lr=0.0, jobs=False,
+                                   fused=False if multi else None)  # (any output gradient)
         self._names = list(self._trainer.plan.tensors)
         self._generation = 0
         self.params = torch.nn.ParameterList([torch.nn.Parameter(self._trainer.circuit.store[n]) for n in self._names])

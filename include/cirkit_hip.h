@@ -1018,6 +1018,32 @@ int ck_opt_tick(ck_opt_state* state, int32_t* flag, int32_t* sticky, void* strea
  * (notebooks/learning-a-circuit.ipynb cell 20: `circuit(batch).sum()`).  out_dev is overwritten. */
 int ck_ll_sum(const float* ll, int64_t B, int64_t stride, double* out_dev, void* stream);
 
+/* ---------------------------------------------------------------- classification ("Classification";
+ * additive, ABI 51) ---- */
+/* The class head of a class-conditional circuit (cirkit_amd/csrc/ck_class.hip): what the reference's
+ * notebooks/generative-vs-discriminative-circuit.ipynb does in torch on the (B, 1, C) output of the circuit -- its loss cells
+ * (the class-conditional NLL `-log p(x | y)`, the cross-entropy `log p(x | y) - logsumexp_c log p(x | c)`, with a prior), the
+ * autograd of those back to the circuit's output, and `argmax` over the classes of an IntegrateQuery result
+ * (cirkit/backend/torch/queries.py:19-184) for prediction with missing features.
+ *
+ * x: (B, stride) fp32, the root fold's block in the arena; the first C <= stride columns are the classes l_bc = log p(x_b | c).
+ * labels (B) int64 or NULL (no row labelled): 0 .. C-1 labelled, -1 unlabelled, anything else raises *bad_flag (and the row
+ * counts as dead).  log_prior (C) fp32, normalised, -inf allowed, or NULL (uniform).  With j = l + log_prior,
+ * e_b = logsumexp_c j_bc, q = j - e:
+ *   gen_b = j_{b,y} (labelled) | e_b (unlabelled),  disc_b = q_{b,y} | 0,  L = -inv_gb sum_b (w_gen gen_b + w_disc disc_b);
+ *   seed (B, stride) <- dL/dl: -inv_gb [w_gen d(c,y) + w_disc (d(c,y) - exp q)] | -inv_gb w_gen exp q; exactly 0 where
+ *   j = -inf, on dead rows (e not finite, a NaN in the row, a labelled row with j_{b,y} = -inf) and on the columns >= C;
+ *   log_post (B, C) <- q (NaN where e is not finite);  pred (B) <- argmax_c q, lowest c on ties (-1 where e is not finite);
+ *   log_evid (B) <- e = log p(x_b) (-inf for an impossible row, NaN for a row holding a NaN or +inf);
+ *   stats (CK_CLASS_NUM_STATS, fp64) <- [sum gen, sum disc, live rows, labelled live rows, correct among them, dead rows],
+ *   summed in a fixed order (per-workgroup partials, then one small launch over them): equal inputs give equal bits.
+ * Every output may be NULL; `partials` (CK_CLASS_MAX_BLOCKS * CK_CLASS_NUM_STATS doubles of scratch) goes with `stats`. */
+#define CK_CLASS_NUM_STATS 6
+#define CK_CLASS_MAX_BLOCKS 256
+int ck_class_head(const float* x, int B, int C, int stride, const int64_t* labels, const float* log_prior, float w_gen, float w_disc,
+                  float inv_gb, float* seed, float* log_post, float* log_evid, int64_t* pred, double* stats, double* partials,
+                  int32_t* bad_flag, void* stream);
+
 /* ---------------------------------------------------------------- program (launch list) ---- */
 /* A program records the exact sequence of the calls above for one (plan, batch size) and replays
  * it with ONE host call -- the native replacement for the per-batch Python interpreter loop
