@@ -200,6 +200,7 @@ SAMPLE_LAYER_DTYPE = [("type", "<i4"), ("F", "<i4"), ("H", "<i4"), ("Ki", "<i4")
 CK_SAMPLE_CATEGORICAL, CK_SAMPLE_GAUSSIAN, CK_SAMPLE_SUM, CK_SAMPLE_CPT, CK_SAMPLE_TUCKER, CK_SAMPLE_HADAMARD, CK_SAMPLE_KRONECKER = range(7)
 CK_SAMPLE_MAX_LDS = 65536
 CK_CLASS_NUM_STATS, CK_CLASS_MAX_BLOCKS = 6, 256  # ck_class_head: the statistics, and the partials its caller lends
+CK_MI_MAX_COUNTS, CK_MI_MAX_ROWS, CK_MI_MAX_STATES = 1 << 28, 1 << 24, 256  # ck_mi_pairs: the counts it stores, its rows and states
 CK_EM_ROW_SOFTMAX, CK_EM_ROW_LINEAR, CK_EM_MIXING, CK_EM_GAUSSIAN, CK_EM_BINOMIAL = range(5)
 NSUM_JOB_DTYPE = [("out", "<u8"), ("in_off", "<i4"), ("n_in", "<i4")]
 CAT_JOB_DTYPE = [("x", "<u8"), ("theta", "<u8"), ("table", "<u8"), ("dtheta", "<u8"), ("theta_out", "<u8"), ("m1", "<u8"), ("m2", "<u8"),
@@ -393,6 +394,9 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_opt_tick": [_p, _p, _p, _p],
     "ck_ll_sum": [_p, _l, _l, _p, _p],
     "ck_class_head": [_p, _i, _i, _i, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p],
+    "ck_mi_stage": [_p, _i, _l, _i, _i, _i, _p, _l, _p, _p],
+    "ck_mi_marginals": [_p, _l, _i, _l, _i, C.c_double, _p, _p, _p],
+    "ck_mi_pairs": [_p, _l, _i, _l, _i, C.c_double, _p, _p, _p, _p],
     "ck_program_begin": [C.POINTER(_p)],
     "ck_program_end": [_p],
     "ck_program_num_ops": [_p],

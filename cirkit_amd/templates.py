@@ -24,7 +24,8 @@ fixtures extracted from the real reference:
                            (utils/algorithms.py:71-97, graph/folding.py:62-298, torch/compiler.py:335-506)
 
 Binomial input layers are built here as well (round 1; outside SURVEY.md section 8's f1 list -- kept because committed
-plan fixtures use them, not extended).  The Chow-Liu structure learner of round 1 is gone (out of scope).
+plan fixtures use them, not extended).  A Chow-Liu tree learned from data (`structure.chow_liu_predecessors`) becomes a
+hidden Chow-Liu tree region graph in `tree_to_region_graph` ("Structure learning").
 """
 
 from __future__ import annotations
@@ -36,6 +37,7 @@ from typing import Any
 import numpy as np
 
 from .plan import IDX_ARRAY, IDX_NONE, IDX_UNSQ0, IDX_UNSQ1, FoldIndex, LayerSpec, ParamGraph, ParamNode, Plan
+from .structure import chow_liu_predecessors
 
 
 # ---------------------------------------------------------------------------------------------
@@ -366,6 +368,44 @@ def linear_tree(num_variables: int, *, num_repetitions: int = 1, ordering: list[
             b.ins[ptn] = [leaf, nxt]
             node = nxt
     return b.graph(root)
+
+
+def tree_to_region_graph(predecessors) -> RegionGraph:
+    """Hidden Chow-Liu tree region graph of a rooted tree over the variables (templates/region_graph/algorithms/
+    utils.py:66-131): every variable with children gets a partition over itself and ALL its descendants, whose inputs are
+    its own leaf region and one region per child subtree (in variable order), and a region above that partition; childless
+    variables are leaf regions feeding their parent's partition.  Nodes are created in the reference's order (partitions
+    by variable, then per variable its leaf region and its inner region), which fixes the layer order.  The tree comes from
+    `structure.chow_liu_predecessors`."""
+    tree = [int(p) for p in predecessors]
+    n = len(tree)
+    roots = [v for v in range(n) if tree[v] == -1]
+    if len(roots) != 1:
+        raise ValueError("the predecessors must describe ONE rooted tree")
+    below: list[set[int]] = [set() for _ in range(n)]
+    for v in range(n):
+        u = tree[v]
+        while u != -1:
+            below[u].add(v)
+            u = tree[u]
+    b = _RGBuilder()
+    part = {u: b.new(False, below[u] | {u}) for u in range(n) if below[u]}
+    top: dict[int, int] = {}
+    for v in range(n):
+        leaf = b.new(True, [v])
+        up = tree[v]
+        if v not in part:
+            top[v] = leaf
+            if up != -1:
+                b.ins.setdefault(part[up], []).append(leaf)
+            continue
+        b.ins.setdefault(part[v], []).append(leaf)
+        rgn = b.new(True, below[v] | {v})
+        top[v] = rgn
+        b.ins.setdefault(rgn, []).append(part[v])
+        if up != -1:
+            b.ins.setdefault(part[up], []).append(rgn)
+    return b.graph(top[roots[0]])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -869,11 +909,18 @@ def tabular_data(
     semiring: str = "lse-sum",
 ) -> Plan:
     """``data_modalities.tabular_data`` (:165-305) followed by ``compile(fold=True, optimize=True)``.
-    `input_layers` is one ``{'name': ..., 'args': {...}}`` dict or a list with one per feature."""
+    `input_layers` is one ``{'name': ..., 'args': {...}}`` dict or a list with one per feature.  ``'chow-liu-tree'`` learns
+    its structure from `data` (rows x features): categorical data on a ROCm device has its mutual information computed
+    there, anything else on the host (`structure.chow_liu_predecessors`)."""
     if region_graph == "chow-liu-tree":
-        raise NotImplementedError("structure learning (region_graph='chow-liu-tree') is outside this backend's scope: compile the "
-                                  "circuit with cirkit and pass the compiled TorchCircuit to cirkit_amd.pipeline.compile")
-    if region_graph == "random-binary-tree":
+        if data is None:  # (the reference raises ValueError here; tests/test_templates.py pins this class)
+            raise NotImplementedError("learning a structure (region_graph='chow-liu-tree') needs the data it is learned from: pass `data=`")
+        single = isinstance(input_layers, dict)
+        pred = chow_liu_predecessors(
+            data, input_layers["name"] if single else [d["name"] for d in input_layers],
+            num_categories=input_layers["args"]["num_categories"] if single and input_layers["name"] == "categorical" else None)
+        rg = tree_to_region_graph(pred)
+    elif region_graph == "random-binary-tree":
         if num_features is None:
             if data is None:
                 raise ValueError(f"You must pass `num_features=` if you ask for {region_graph}.")

@@ -1044,6 +1044,30 @@ int ck_class_head(const float* x, int B, int C, int stride, const int64_t* label
                   float inv_gb, float* seed, float* log_post, float* log_evid, int64_t* pred, double* stats, double* partials,
                   int32_t* bad_flag, void* stream);
 
+/* ---------------------------------------------------------------- structure learning ("Structure
+ * learning"; additive, ABI 51) ---- */
+/* Pairwise mutual information of categorical columns (cirkit_amd/csrc/ck_mi.hip): `_categorical_mutual_info` of the reference
+ * (templates/region_graph/algorithms/chow_liu.py:107-151) without its (D, D, C^2) count tensor.  N <= 2^24 rows, C <= 256
+ * states; `ldn`, the row stride of the staged copy, covers N and is a multiple of 16.
+ * ck_mi_stage: x (N, D) row-major int64 (is_int64) or int32 -> codes (D, ldn) uint8, codes[d, n] = x[n, d] / divisor (the
+ *   reference's `num_bins` rescaling).  An entry outside [0, num_categories) raises *bad_flag and is staged as 0.  The caller
+ *   zeroes `codes` first: the columns n >= N of the copy must hold valid codes.
+ * ck_mi_marginals: hist (D, C) int64 (may be NULL) <- the counts of every state; logm (D, C) fp64 <-
+ *   log((count + C alpha) / (N + C^2 alpha)), the reference's smoothed marginal.
+ * ck_mi_pairs: 32 x 32 tiles of the Gram matrix of the one-hot encoding on v_mfma_f32_32x32x16_bf16 (0/1 operands, fp32
+ *   accumulation: exact), upper triangle only, and exactly one of
+ *     mi (D, D) fp64: mi[i, j] = mi[j, i] <- sum_ab joint (log joint - logm[i, a] - logm[j, b]), joint = (count + alpha) /
+ *       (N + C^2 alpha), over the C^2 real cells, for i != j (the diagonal is left as the caller set it); reduced in a fixed
+ *       order, no atomics: equal inputs give equal bits;
+ *     counts (D, D, C, C) int64 <- counts[i, j, a, b] = #{n : x[n, i] = a, x[n, j] = b}, at most CK_MI_MAX_COUNTS elements. */
+#define CK_MI_MAX_COUNTS (1 << 28)
+int ck_mi_stage(const void* x, int is_int64, int64_t N, int D, int num_categories, int divisor, uint8_t* codes, int64_t ldn,
+                int32_t* bad_flag, void* stream);
+int ck_mi_marginals(const uint8_t* codes, int64_t N, int D, int64_t ldn, int C, double alpha, int64_t* hist, double* logm,
+                    void* stream);
+int ck_mi_pairs(const uint8_t* codes, int64_t N, int D, int64_t ldn, int C, double alpha, const double* logm, double* mi,
+                int64_t* counts, void* stream);
+
 /* ---------------------------------------------------------------- program (launch list) ---- */
 /* A program records the exact sequence of the calls above for one (plan, batch size) and replays
  * it with ONE host call -- the native replacement for the per-batch Python interpreter loop
