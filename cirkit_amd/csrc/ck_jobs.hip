@@ -735,6 +735,14 @@ __global__ void __launch_bounds__(256)
 // d w_r[n] = sum_b seed p_r e_r[n] / y_r,  d c_r = sum_b seed exp(o_r - M) / Y -- per-workgroup partial sums, the last arrival adds
 // them in workgroup order and applies the softmax parameterisations.  One wave per row, lane = input unit.
 constexpr int kRootMax = 16;
+// w (d - <w, d>) of a softmax row held one entry per lane, the dot product and the difference in DOUBLE ("The softmax
+// backward's dot product is formed in double"): where the weight sits on one entry the row is what the subtraction leaves.
+__device__ __forceinline__ float softmax_bwd_lane(float w, float d) {
+  double s = static_cast<double>(w) * static_cast<double>(d);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  return static_cast<float>(static_cast<double>(w) * (static_cast<double>(d) - s));
+}
 __global__ void __launch_bounds__(256) jobs_root_kernel(const ck_root_launch a) {
   __shared__ float red[4][kRootMax * kU + kRootMax];
   __shared__ double red_ll[4];
@@ -872,8 +880,7 @@ __global__ void __launch_bounds__(256) jobs_root_kernel(const ck_root_launch a) 
   // softmax behind every weight row (wave w takes folds w, w + 4, ...) ...
   for (int r = wave; r < R; r += 4) {
     const float w = a.w[r][lane], d = tot[r * kU + lane];
-    const float s = ck::wave_sum(w * d);
-    const float g = w * (d - s);
+    const float g = softmax_bwd_lane(w, d);
     if (a.mode == 1) {
       a.dtheta_w[r][lane] = g;
     } else {
@@ -894,8 +901,7 @@ __global__ void __launch_bounds__(256) jobs_root_kernel(const ck_root_launch a) 
   if (a.c != nullptr && wave == 0) {
     const bool on = lane < R;
     const float c = on ? a.c[lane] : 0.f, d = on ? tot[R * kU + lane] : 0.f;
-    const float s = ck::wave_sum(c * d);
-    const float g = c * (d - s);
+    const float g = softmax_bwd_lane(c, d);
     if (a.mode == 1) {
       if (on) a.dtheta_c[lane] = g;
     } else {
@@ -921,8 +927,8 @@ __global__ void __launch_bounds__(256) jobs_root_kernel(const ck_root_launch a) 
 // ONE workgroup: G = the sum of the fold's gradient blocks; dT[c, :] = sum over the rows with x_b = c of G[b, :] (the scatter-add
 // autograd performs for the advanced indexing) -- rows counting-sorted by category in LDS (integer atomics), every category
 // owned by one wave, plain row loads eight at a time, no float atomics --; then through the log-softmax:
-// d theta[k, c] = dT[c, k] - p[k, c] sum_c' dT[c', k]  (nodes.py:764-783), with p = exp(theta - lse) and lse read off the forward's
-// table.  mode 2: the optimizer's update of theta and the next step's (C + 1, 64) table, transposed through LDS.
+// d theta[k, c] = dT[c, k] - p[k, c] sum_c' dT[c', k]  (nodes.py:764-783), with p = exp(table[c, k]), the log-probabilities of the
+// forward's table.  mode 2: the optimizer's update of theta and the next step's (C + 1, 64) table, transposed through LDS.
 constexpr int kCatRows = 512;   // rows sorted at a time (LDS: two workgroups per CU at 256 categories)
 constexpr int kHS = 65;         // row stride of the (C + 1, 64) histogram in LDS
 __global__ void __launch_bounds__(1024)
@@ -1037,7 +1043,7 @@ __global__ void __launch_bounds__(1024)
     __syncthreads();
   }
   if (CK_CAT_LAB & 2) return;
-  // column sums over the C categories (the integral row C carries no parameter) and the forward's log-normalisers
+  // column sums over the C categories (the integral row C carries no parameter)
   {
     float t = 0.f;
     for (int c = wave; c < C; c += 16) t += hist[c * kHS + lane];
@@ -1049,30 +1055,35 @@ __global__ void __launch_bounds__(1024)
 #pragma unroll
     for (int w = 0; w < 16; ++w) t += red[w * kU + threadIdx.x];
     tk[threadIdx.x] = t;
-    lse[threadIdx.x] = J.theta[static_cast<int64_t>(threadIdx.x) * C] - J.table[threadIdx.x];  // theta[k, 0] - log p[k, 0]
   }
   __syncthreads();
   const int n = kU * C;
-  // (four entries per thread and pass, every load of a pass issued before its arithmetic: a pass is one memory round trip)
+  // hist[c, k] <- d theta[k, c] = dT[c, k] - p[k, c] tk[k], in the table's own order (coalesced): p = exp(table[c, k]), the
+  // log-probability the forward gathered, needs no normaliser.  (Recovering one as theta[k, 0] - table[0, k] lost 1e-5 of p where
+  // category 0 lies far below the row's maximum, and is NaN where it has no mass: tests/test_gpu_jobs.py, the spread logits.
+  // Requesting the table before the column sums, sixteen entries per thread, was slower: LAB_NOTES.md, "Job kernels".)
+  for (int e0 = threadIdx.x; e0 < n; e0 += 4096) {
+    float lp[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) lp[u] = e0 + 1024 * u < n ? *ck::as_global(J.table + e0 + 1024 * u) : 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = e0 + 1024 * u;
+      if (e < n) hist[(e >> 6) * kHS + (e & 63)] -= __expf(lp[u]) * tk[e & 63];
+    }
+  }
+  __syncthreads();
   if (J.mode != 2) {
-    for (int e0 = threadIdx.x; e0 < n; e0 += 4096) {
-      float th[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) th[u] = e0 + 1024 * u < n ? *ck::as_global(J.theta + e0 + 1024 * u) : 0.f;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = e0 + 1024 * u;
-        if (e < n) {
-          const int k = unit_of(e), c = e - k * C;
-          *ck::as_global(J.dtheta + e) = hist[c * kHS + k] - __expf(th[u] - lse[k]) * tk[k];
-        }
-      }
+    for (int e = threadIdx.x; e < n; e += 1024) {
+      const int k = unit_of(e), c = e - k * C;
+      *ck::as_global(J.dtheta + e) = hist[c * kHS + k];
     }
     return;
   }
   const ck_opt_state os = *opt;
   const OptK ok = opt_k(os);
   if (os.skip_now) return;
+  // (four entries per thread and pass, every load of a pass issued before its arithmetic: a pass is one memory round trip)
   for (int e0 = threadIdx.x; e0 < n; e0 += 4096) {
     float th[4], a[4], b[4];
 #pragma unroll
@@ -1087,8 +1098,7 @@ __global__ void __launch_bounds__(1024)
       const int e = e0 + 1024 * u;
       if (e < n) {
         const int k = unit_of(e), c = e - k * C;
-        const float g = hist[c * kHS + k] - __expf(th[u] - lse[k]) * tk[k];
-        const float t = opt_update(ok, th[u], g, a[u], b[u]);
+        const float t = opt_update(ok, th[u], hist[c * kHS + k], a[u], b[u]);
         *ck::as_global(J.theta_out + e) = t;
         if (os.kind) {
           *ck::as_global(J.m1 + e) = a[u];

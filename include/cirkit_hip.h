@@ -965,8 +965,8 @@ typedef struct ck_root_launch {
 int ck_jobs_root(const ck_root_launch* a, void* stream);
 /* One fold of a TorchCategoricalLayer with 64 units and probs = softmax(theta) (layers/input.py:399-412, nodes.py:764-783), backward:
  * G = the sum of the n_g blocks pool[g_off ..], x the (B) int32 column of the staged batch (-1 = marginalised), theta (64, C) the
- * logits, table (C + 1, 64) the log-probabilities the forward gathered from.  mode 1: dtheta (64, C) <- the gradient of the
- * logits; mode 2: the optimizer's update of theta_out / m1 / m2 in place and table_out <- the next step's table (rows < C). */
+ * logits, table (C + 1, 64) the log-probabilities the forward gathered from (p = exp(table); theta itself is not read).  mode 1:
+ * dtheta (64, C) <- the gradient of the logits; mode 2: the optimizer's update of theta_out / m1 / m2 in place and table_out <- the next step's table (rows < C). */
 typedef struct ck_cat_job {
   const int32_t* x;
   const float* theta;

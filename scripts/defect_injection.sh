@@ -2,13 +2,14 @@
 # Prove that the gradient tests bite: build a lab copy of the library with a defect injected (scripts/lab_build.sh, selected by
 # CIRKIT_HIP_LIB) and run the tests that must see it: they must FAIL.  Exit 0 when every defect was caught.
 #   bash scripts/defect_injection.sh [defect]   VERDICT r5 #8: a sum job's epilogue scales <W, dW> by (1 + defect) (default 1e-3);
-#                                               the job-form gradient tests (tests/test_training_jobs.py)
+#                                               the job-form gradient tests (tests/test_training_jobs.py) and the sum job's
+#                                               kernel test (tests/test_gpu_jobs.py -k sum64_bwd): both runs must fail
 #   bash scripts/defect_injection.sh layer      the layer backward kernels (CK_BWD_LAB_DEFECT of cirkit_amd/csrc/ck_backward.hip)
 #                                               against tests/test_gpu_layer_backward.py: 1 the tile32 kernel treats the rows beyond B
 #                                               of a ragged tile as live, 2 it stops after a wave's first tile, 3 the register
 #                                               mixing kernel scales dmw by 1 + 1e-3
-# The lab libraries need the objects of a finished build under cirkit_amd/lib/; LAYER_LABS=keep runs libraries that are already
-# under build/lab/ (built where the objects are).
+# The lab libraries need the objects of a finished build under cirkit_amd/lib/; LAYER_LABS=keep (layer) / JOBS_LAB=keep (default
+# path) runs libraries that are already under build/lab/ (built where the objects are).
 set -u
 cd "$(dirname "$0")/.."
 if [ "${1:-}" = "layer" ]; then
@@ -33,11 +34,20 @@ if [ "${1:-}" = "layer" ]; then
   exit $missed
 fi
 DEFECT=${1:-1e-3f}
-bash scripts/lab_build.sh defect cirkit_amd/csrc/ck_jobs.hip -DCK_JOBS_LAB_DEFECT=$DEFECT > /dev/null || exit 2
-CIRKIT_HIP_LIB=$PWD/build/lab/lib_defect.so python -m pytest tests/test_training_jobs.py -q -m gpu -x \
-  -k "shallow_circuit or gradients_match_the_layerwise" > build/lab/defect.log 2>&1
-rc=$?
-grep -E "^E  .*(assert|Error)" build/lab/defect.log | head -6
-tail -3 build/lab/defect.log
-if [ $rc -ne 0 ]; then echo "defect $DEFECT in <W, dW>: CAUGHT (pytest rc $rc)"; exit 0; fi
-echo "defect $DEFECT in <W, dW>: NOT caught"; exit 1
+if [ "${JOBS_LAB:-}" != "keep" ]; then
+  bash scripts/lab_build.sh defect cirkit_amd/csrc/ck_jobs.hip -DCK_JOBS_LAB_DEFECT=$DEFECT > /dev/null || exit 2
+fi
+missed=0
+run_must_fail() {  # <log name> <what> <pytest arguments...>
+  local log=build/lab/$1.log what=$2
+  shift 2
+  CIRKIT_HIP_LIB=$PWD/build/lab/lib_defect.so timeout -k 10 600 python -m pytest "$@" -q -m gpu -x -p no:cacheprovider > "$log" 2>&1
+  local rc=$?
+  grep -E "^E  .*(assert|Error)" "$log" | head -6 | cut -c1-220
+  tail -3 "$log"
+  if [ $rc -eq 1 ]; then echo "defect $DEFECT in <W, dW>, $what: CAUGHT"; else echo "defect $DEFECT in <W, dW>, $what: NOT caught (pytest rc $rc)"; missed=1; fi
+  if [ $rc -gt 1 ]; then exit 2; fi  # (not a test failure: nothing more is started)
+}
+run_must_fail defect "circuit-level tests" tests/test_training_jobs.py -k "shallow_circuit or gradients_match_the_layerwise"
+run_must_fail defect_kernel "kernel test" tests/test_gpu_jobs.py -k sum64_bwd
+exit $missed
