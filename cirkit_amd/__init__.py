@@ -2,7 +2,7 @@
 
 from .plan import Plan, plan_from_torch_circuit  # noqa: F401
 
-__all__ = ["Plan", "plan_from_torch_circuit", "HipCircuit", "HipCircuitStreams", "HipTrainer", "HipCircuitModule", "HipSquaredCircuit", "compile"]
+__all__ = ["Plan", "plan_from_torch_circuit", "HipCircuit", "HipCircuitStreams", "HipTrainer", "HipCircuitModule", "HipSquaredCircuit", "HipHMM", "compile"]
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch/ROCm
@@ -22,6 +22,10 @@ def __getattr__(name):  # lazy: importing the package must not require torch/ROC
         from .squared import HipSquaredCircuit
 
         return HipSquaredCircuit
+    if name == "HipHMM":
+        from .hmm import HipHMM
+
+        return HipHMM
     if name == "compile":
         from .pipeline import compile
 

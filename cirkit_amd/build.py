@@ -23,6 +23,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # which matter because fp32-input MFMA shares the fp32 ALUs with the VALU -- DESIGN.md section 4.2).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]
+# per-file additions: ck_hmm.hip is compiled without packed fp32 instructions (v_pk_mul_f32 and its kin); the host pass of
+# hipcc does not know the feature and says so, the device pass honours it
+FILE_FLAGS = {"ck_hmm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _newer(target: str, deps: list[str]) -> bool:
@@ -46,7 +49,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         objs.append(o)
         if not force and _newer(o, [s] + hdrs):
             continue
-        cmd = [HIPCC, *FLAGS, "-c", s, "-o", o]
+        cmd = [HIPCC, *FLAGS, *FILE_FLAGS.get(os.path.basename(s), []), "-c", s, "-o", o]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((cmd, subprocess.Popen(cmd)))

@@ -1,0 +1,274 @@
+// The forward algorithm of a hidden Markov model in ONE launch ("Hidden Markov models").
+//
+// A chain plan (cirkit_amd/hmm.py: chain_of) is T dependent layers of one fold each, K units wide:
+//     v_s[b, o] = log sum_i W_s[o, i] exp(v_{s-1}[b, i] + e_s[b, i]),   v_{-1} = 0,   result v_{T-1}[b, 0]
+// with e_s[b, :] the row of K log emissions of step s at x[b, var_s] (zeros where that entry is missing).  Layer by layer
+// that is T launches that each write a (B, K) block and read it back; here a workgroup owns 32 rows for the whole chain
+// and the state never leaves the chip.
+//
+// Decomposition.  A workgroup = min(K / 32, 4) waves x 32 rows.  The waves split the UNITS into blocks of 32: wave w
+// owns blocks w, w + waves, ... (NOB of them at most) -- as OUTPUT blocks of a step's contraction and, because the output
+// layout of v_mfma_f32_32x32x2_f32 is the input layout of the next one (ck_tile.h), as the blocks whose hand-off it
+// prepares for the next step, in registers:
+//   A  t = log y_{s-1} + e_s on the wave's blocks (registers); row maximum M over ALL units: per wave in registers, across
+//      the waves through LDS; p = exp(t - M) goes to the activation tile in LDS in operand layout (block q, register group
+//      g, lane: one ds_read_b128 per MFMA operand quad, no bank conflict); the row's log scale gains M.  (p carries a factor
+//      2^96 that the logarithm takes off again: kHmmHead.)
+//   B  y = W_s p on v_mfma_f32_32x32x2_f32 (exact fp32; weights as operand A, activations as B): every wave contracts
+//      ALL K inputs from the shared tile against the weight rows of its own output blocks, then takes log y.
+// This is LSESumSemiring's arithmetic (semiring.py:383-408) step for step -- the maximum is clamped to finite values, so a
+// row without mass ends as -inf, never NaN -- and needs no fallback: nothing is renormalised in linear space, so nothing can
+// underflow that the reference's own fp32 evaluation keeps (LAB_NOTES has the cost of the two transcendentals per unit).
+//
+// Weights.  W_s is K^2 floats (4 MiB at K = 1024) and every workgroup reads all of it at about the same time, from L2.  A
+// wave streams the rows of its output blocks in UNITS of 32 outputs x 16 inputs (2 KiB: two global_load_lds_dwordx4 per
+// lane land them in operand layout) through a private ring of NBUF units in LDS; no other wave reads them, so a unit needs
+// no barrier, only the wave's own vmcnt: loads complete in order, so "at most 2 (NBUF - 1) requests outstanding" means unit
+// u has landed once NBUF - 1 younger units are in flight, whatever else (emission rows) was requested around them; the last
+// NBUF - 1 units of a step wait for everything.  The first NBUF - 1 units of a step are requested before its phase A.
+// NBUF = 8 up to K = 512; 3 above, where the activation tile alone takes up to 128 of the 160 KiB.
+//
+// Emissions.  The K-row of step s + 1 is requested before step s contracts (its address depends on x only, and x of step
+// s + 2 is read then too).  Two sources, one kernel: a table addressed by (fold, category) -- the Categorical layer's
+// (F, C + 1, K) table of logarithms -- or a (F, B, K) block that the input layer's own launch wrote.
+// The last step only needs output unit 0: a dot product with row 0 of its weights.
+#include "ck_internal.h"
+#include "ck_tile.h"
+
+namespace {
+
+constexpr int kHmmWaves = 4;
+constexpr int kHmmUnit = 512;  // floats of a weight unit (32 outputs x 16 inputs)
+// p = 2^kHmmHead exp(t - M): the matrix pipe and v_exp_f32 flush denormals, so with the row maximum at 1 a state 88 nats below
+// it is lost -- and it is the one that counts where the maximum meets a weight that small (peaked parameters: emissions 80
+// nats apart).  The exponent range above 1 is free: softmax rows sum to 1, so y <= 2^96 and the states kept reach 154 nats down.
+constexpr float kHmmHead = 96.f;
+// log(y 2^-kHmmHead) from the mantissa and the exponent of y: v_log_f32 of y itself rounds a result near 96 to 2^-17, 5e-6 nats a
+// step where every state is as likely as the next (a row of missing entries), whatever is subtracted afterwards
+__device__ __forceinline__ float log_unscaled(float y) {
+  const float k = static_cast<float>(__builtin_amdgcn_frexp_expf(y)) - kHmmHead;
+  return (__builtin_amdgcn_logf(__builtin_amdgcn_frexp_mantf(y)) + k) * kLN2;
+}
+
+struct HmmArgs {
+  const float* const* w;  // (T) the steps' evaluated weights, row-major (Ko, K)
+  const int32_t* fold;    // (T) input fold of each step
+  const int32_t* var;     // (T) its variable
+  const float* rows;      // emission rows, K floats each
+  const int64_t* x;       // (B, D) categories: row (fold, x) of a (F, C + 1, K) table; nullptr: row (fold, b) of a (F, B, K) block
+  const int32_t* integ;   // (D) != 0: the variable is summed out; or nullptr
+  float* out;             // (B)
+  int C, D, T, B, K;
+};
+
+__device__ __forceinline__ void lds_w4(uint32_t addr, float a, float b, float c, float d) {
+  const f32x4v v = {a, b, c, d};
+  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+__device__ __forceinline__ void sync_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+template <int NOB>
+__global__ void __launch_bounds__(256) hmm_forward_kernel(const HmmArgs a) {
+  constexpr int NBUF = NOB > 4 ? 3 : 8;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int K = a.K, NQ = K >> 5, T = a.T;
+  const int nwaves = blockDim.x >> 6;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int kh = lane >> 5, row = lane & 31;
+  const int b = blockIdx.x * 32 + row;
+  const bool live = b < a.B;
+  const int bl = live ? b : a.B - 1;  // (rows past B repeat the last one and store nothing)
+  int nob = 0;                        // units blocks of this wave
+#pragma unroll
+  for (int j = 0; j < NOB; ++j) nob += wave + nwaves * j < NQ ? 1 : 0;
+
+  // LDS: activation tile [NQ][4][64] float4 | row maxima [4][32] | weight rings [waves][NBUF][2][64] float4
+  const uint32_t act = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(smem));
+  const uint32_t red = act + NQ * 4096;
+  float* const ring_p = smem + NQ * 1024 + kHmmWaves * 32 + wave * (NBUF * kHmmUnit);
+  const uint32_t ring = red + kHmmWaves * 128 + wave * (NBUF * kHmmUnit * 4) + lane * 16;
+
+  bool bad = false;
+  auto load_x = [&](int s) -> int64_t { return (a.x != nullptr && s < T) ? a.x[static_cast<int64_t>(bl) * a.D + a.var[s]] : 0; };
+  auto row_of = [&](int s, int64_t xv) -> const float* {  // nullptr: the entry is missing
+    const int64_t f = a.fold[s];
+    if (a.x == nullptr) return a.rows + (f * a.B + bl) * K;
+    if (xv < 0 || (a.integ != nullptr && a.integ[a.var[s]] != 0)) return nullptr;
+    if (xv >= a.C) {
+      bad = true;
+      return nullptr;
+    }
+    return a.rows + (f * (a.C + 1) + xv) * K;
+  };
+  float e[NOB][16], la[NOB][16];
+  auto load_e = [&](const float* r) {
+#pragma unroll
+    for (int j = 0; j < NOB; ++j) {
+      const int q = wave + nwaves * j;
+      if (q < NQ && r != nullptr) {
+        tile_load(r + 32 * q + 4 * kh, e[j]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) e[j][i] = 0.f;
+      }
+    }
+  };
+  // unit u of a step = (owned block j, input block q, half h): rows 32 ob .. of W, inputs 32 q + 16 h ..
+  auto issue = [&](const float* w, int u) {
+    const int j = u / (2 * NQ), r = u - j * 2 * NQ;
+    const int ob = wave + nwaves * j;
+    const float* src = w + static_cast<int64_t>(32 * ob + row) * K + 16 * r + 4 * kh;
+    float* dst = ring_p + (u % NBUF) * kHmmUnit;
+    __builtin_amdgcn_global_load_lds((ck::gptr_t)src, (ck::lptr_t)dst, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((ck::gptr_t)(src + 8), (ck::lptr_t)(dst + 256), 16, 0, 0);
+  };
+
+#pragma unroll
+  for (int j = 0; j < NOB; ++j)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) la[j][i] = 0.f;
+  float scale = 0.f;
+  load_e(row_of(0, load_x(0)));
+  int64_t xn = load_x(1);
+
+  for (int s = 0; s < T; ++s) {
+    const bool last = s + 1 == T;
+    const float* w = a.w[s];
+    const int U = last ? 0 : nob * NQ * 2;
+    for (int u = 0; u < NBUF - 1 && u < U; ++u) issue(w, u);
+
+    // ---- A: t = log y + e, its row maximum, p = exp(t - M) into the shared tile
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NOB; ++j)
+      if (j < nob) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          e[j][i] += la[j][i];
+          m = fmaxf(m, e[j][i]);
+        }
+      }
+    m = ck::xhalf_max(m);
+    asm volatile("ds_write_b32 %0, %1" ::"v"(red + (wave * 32 + row) * 4), "v"(m) : "memory");
+    sync_lds();
+    for (int k = 0; k < nwaves; ++k) {
+      float o;
+      asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(o) : "v"(red + (k * 32 + row) * 4) : "memory");
+      m = fmaxf(m, o);
+    }
+    m = ck::clamp_finite(m);
+    const float nml = exp_offset(m, kHmmHead);
+    scale += m;
+#pragma unroll
+    for (int j = 0; j < NOB; ++j)
+      if (j < nob) {
+        const uint32_t dst = act + (wave + nwaves * j) * 4096 + lane * 16;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          float p[4];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) p[t] = __builtin_amdgcn_exp2f(fmaf(e[j][4 * g + t], kL2E, nml));
+          lds_w4(dst + g * 1024, p[0], p[1], p[2], p[3]);
+        }
+      }
+    sync_lds();
+    if (last) break;
+
+    // the emission row of step s + 1 travels while this step contracts
+    load_e(row_of(s + 1, xn));
+    xn = load_x(s + 2);
+
+    // ---- B: y = W p on the wave's output blocks, log y stays in registers
+    int u = 0;
+    static_for<0, NOB>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;
+      if (j >= nob) return;
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      for (int r = 0; r < 2 * NQ; ++r, ++u) {
+        if (u + NBUF - 1 < U) {
+          issue(w, u + NBUF - 1);
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (NBUF - 1)) : "memory");
+        } else {
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        f32x4v w0, w1, p0, p1;
+        const uint32_t wa = ring + (u % NBUF) * (kHmmUnit * 4), pa = act + r * 2048 + lane * 16;
+        lds_read4(w0, w1, p0, p1, wa, wa + 1024, pa, pa + 1024);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[t], p0[t], acc, 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[t], p1[t], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) la[j][r] = log_unscaled(acc[r]);
+    });
+  }
+
+  // the last step: output unit 0 only
+  if (wave == 0) {
+    const float* wl = a.w[T - 1];
+    float d = 0.f;
+    for (int q = 0; q < NQ; ++q) {
+      f32x4v p0, p1, p2, p3;
+      const uint32_t pa = act + q * 4096 + lane * 16;
+      lds_read4(p0, p1, p2, p3, pa, pa + 1024, pa + 2048, pa + 3072);
+      const f32x4v* pg[4] = {&p0, &p1, &p2, &p3};
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 w4 = ck::gload4(wl + 32 * q + 8 * g + 4 * kh);
+        d = fmaf(w4.x, (*pg[g])[0], d);
+        d = fmaf(w4.y, (*pg[g])[1], d);
+        d = fmaf(w4.z, (*pg[g])[2], d);
+        d = fmaf(w4.w, (*pg[g])[3], d);
+      }
+    }
+    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(d), __float_as_uint(d), false, false);
+    d = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+    if (live && kh == 0) a.out[b] = bad ? __builtin_nanf("") : scale + log_unscaled(d);
+  }
+}
+
+template <int NOB>
+int hmm_launch(const HmmArgs& a, void* stream) {
+  constexpr int NBUF = NOB > 4 ? 3 : 8;
+  const int NQ = a.K / 32, waves = NQ < kHmmWaves ? NQ : kHmmWaves;
+  const size_t lds = (static_cast<size_t>(NQ) * 1024 + kHmmWaves * 32 + static_cast<size_t>(waves) * NBUF * kHmmUnit) * sizeof(float);
+  const dim3 grid((a.B + 31) / 32), block(64 * waves);
+  return ck::dispatch(
+      [=](hipStream_t s) {
+        if (lds > 48 * 1024) {
+          hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(hmm_forward_kernel<NOB>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+          if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(hmm_forward_kernel<NOB>, grid, block, lds, s, a);
+        return hipGetLastError();
+      },
+      stream);
+}
+
+}  // namespace
+
+extern "C" int ck_hmm_forward(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K,
+                              const float* rows, const int64_t* x, int D, int C, const int32_t* integrate, int B, float* out,
+                              void* stream) {
+  CK_REQUIRE(w_steps && step_fold && step_var && rows && out, "ck_hmm_forward: null operand");
+  CK_REQUIRE(T >= 1 && B >= 1, "ck_hmm_forward: T = %d, B = %d", T, B);
+  CK_REQUIRE(K >= 32 && K <= 1024 && K % 32 == 0, "ck_hmm_forward: K = %d is not a multiple of 32 in 32 .. 1024", K);
+  CK_REQUIRE(x == nullptr || (C >= 1 && D >= 1), "ck_hmm_forward: a table source needs C >= 1 and D >= 1");
+  CK_REQUIRE(x != nullptr || integrate == nullptr, "ck_hmm_forward: a block source has its missing entries in the block");
+  const HmmArgs a{reinterpret_cast<const float* const*>(w_steps), step_fold, step_var, rows, x, integrate, out, C, D, T, B, K};
+  const int NQ = K / 32, waves = NQ < kHmmWaves ? NQ : kHmmWaves;
+  switch ((NQ + waves - 1) / waves) {
+    case 1: return hmm_launch<1>(a, stream);
+    case 2: return hmm_launch<2>(a, stream);
+    case 3: return hmm_launch<3>(a, stream);
+    case 4: return hmm_launch<4>(a, stream);
+    case 5: return hmm_launch<5>(a, stream);
+    case 6: return hmm_launch<6>(a, stream);
+    case 7: return hmm_launch<7>(a, stream);
+    default: return hmm_launch<8>(a, stream);
+  }
+}

@@ -1,0 +1,237 @@
+"""Hidden Markov models on the GPU: the forward algorithm of a chain plan in ONE launch ("Hidden Markov
+models").
+
+`templates.hmm` -- the reference's ``cirkit.templates.pgms.hmm`` compiled with ``fold=True, optimize=True`` -- is one input
+layer with a fold per position, a dense sum and T - 1 CP-T layers of ONE fold each: T dependent layers.  `HipCircuit` evaluates
+them with one launch per layer, each writing a (B, K) block that the next one reads back; `HipHMM.log_prob` recognises the chain
+(`chain_of`) and hands it to `ck_hmm_forward` (cirkit_amd/csrc/ck_hmm.hip), where a workgroup keeps the state of its 32 rows on
+chip from the first position to the last.
+
+A Categorical input layer is read as its (F, C + 1, K) table of logarithms, gathered by the kernel itself: one launch per call.
+Any other input layer (Binomial, Gaussian) is evaluated by its own launch into a (F, B, K) block first, `rows_per_chunk` rows at a
+time.  Missing entries -- a variable in `integrate_vars`, or per entry ``x[b, v] == -1`` (NaN for Gaussian inputs): what padding
+sequences of different lengths needs -- are summed out.
+
+Out of scope: Baum-Welch / expected statistics, smoothing posteriors, Viterbi and sampling of chains; homogeneous chains (the
+kernel's table of weight pointers already allows shared transitions); bf16-piece variants; training beyond what `HipTrainer` does
+with a chain plan layer by layer; routing `HipCircuit.forward` to this kernel.
+"""
+
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Mapping
+
+import numpy as np
+import torch
+
+from . import _capi as capi
+from .plan import Plan, resolve_fold_index
+
+_INPUTS = ("categorical", "binomial", "gaussian")
+_CHUNK_BYTES = 1 << 30  # the (F, rows, K) block of emissions of one chunk (inputs other than Categorical)
+
+
+@dataclass
+class ChainStep:
+    """One position of the chain: the layer whose ``weight`` is its transition, the input fold it multiplies in and that fold's
+    variable."""
+
+    layer: int
+    fold: int
+    var: int
+
+
+def chain_of(plan: Plan) -> list[ChainStep]:
+    """The steps of a chain plan in plan order, or ``NotImplementedError`` naming the layer that breaks the pattern: one input
+    layer with one variable per fold; a dense sum over one of its folds; then per step a CP-T layer of arity 2 -- or the Hadamard
+    layer and the dense sum it was fused from -- over the previous step and one more input fold; one fold per layer, no input
+    fold read twice, the last step the output.  Needs no device."""
+    if plan.semiring != "lse-sum":
+        raise NotImplementedError(f"HipHMM: semiring {plan.semiring!r} (chains are evaluated under lse-sum)")
+    inputs = [i for i, l in enumerate(plan.layers) if l.inputs is None]
+    if len(inputs) != 1:
+        raise NotImplementedError(f"HipHMM: {len(inputs)} input layers (layers {inputs[:4]}); a chain has one, a fold per position")
+    (inp,) = inputs
+    src = plan.layers[inp]
+    if src.type not in _INPUTS or src.scope_idx is None or src.scope_idx.shape[1] != 1:
+        raise NotImplementedError(f"HipHMM: layer {inp} is not a {' / '.join(_INPUTS)} input layer of one variable per fold")
+    K = src.num_output_units
+    folds = [l.num_folds for l in plan.layers]
+    steps: list[ChainStep] = []
+    prev, product, seen = None, None, set()
+
+    def refuse(i: int, why: str):
+        raise NotImplementedError(f"HipHMM: layer {i} ({plan.layers[i].type}) breaks the chain: {why}")
+
+    def take(i: int, f: int) -> None:
+        if f in seen:
+            refuse(i, f"input fold {f} is read twice")
+        seen.add(f)
+
+    for i, l in enumerate(plan.layers):
+        if i == inp:
+            continue
+        if l.num_folds != 1:
+            refuse(i, f"{l.num_folds} folds")
+        ch = [(int(p), int(f)) for p, f in resolve_fold_index(l.inputs, folds)[0]]
+        if l.type in ("sum", "cpt") and l.num_input_units != K:
+            refuse(i, f"{l.num_input_units} input units, the input layer has {K}")
+        if l.type == "sum" and l.arity != 1:
+            refuse(i, f"a sum of arity {l.arity} (a mixing layer)")
+        if l.type in ("cpt", "hadamard") and l.arity != 2:
+            refuse(i, f"arity {l.arity}")
+        if l.type == "sum" and prev is None and product is None:  # the first position
+            if ch[0][0] != inp:
+                refuse(i, "the first sum does not read the input layer")
+            take(i, ch[0][1])
+            steps.append(ChainStep(i, ch[0][1], int(src.scope_idx[ch[0][1], 0])))
+        elif l.type == "sum" and product is not None and ch == [(product[0], 0)]:
+            steps.append(ChainStep(i, product[1], int(src.scope_idx[product[1], 0])))
+            product = None
+        elif l.type in ("cpt", "hadamard") and prev is not None and product is None:
+            leaf = [f for p, f in ch if p == inp]
+            if len(leaf) != 1 or sorted(ch, key=lambda c: c[0] == inp)[0] != (prev, 0):
+                refuse(i, "it does not multiply the previous step with one input fold")
+            take(i, leaf[0])
+            if l.type == "hadamard":
+                product, prev = (i, leaf[0]), None
+                continue
+            steps.append(ChainStep(i, leaf[0], int(src.scope_idx[leaf[0], 0])))
+        else:
+            refuse(i, "not a dense sum, a CP-T layer or a Hadamard layer in chain position")
+        if l.num_output_units != K and i != len(plan.layers) - 1:
+            refuse(i, f"{l.num_output_units} output units inside the chain")
+        prev = i
+    out = [(int(p), int(f)) for p, f in resolve_fold_index(plan.output, folds).reshape(-1, 2)]
+    if not steps or product is not None or out != [(steps[-1].layer, 0)]:
+        raise NotImplementedError("HipHMM: the output of the plan is not the last step of a chain")
+    return steps
+
+
+class HipHMM:
+    """``log p(x)`` of a chain plan (`templates.hmm`, or the same layers compiled by the reference) with the whole chain in one
+    launch.  It owns a layer-wise `HipCircuit` of the plan for the parameter store, the evaluated parameter graphs and the input
+    layer (unit counts padded to 32 where `HipCircuit` pads them); the prepared tables follow the store's state.  Refused
+    (``NotImplementedError``, before anything is allocated): whatever `chain_of` refuses, complex parameter tensors, more than
+    1024 units."""
+
+    def __init__(self, plan: Plan, tensors: Mapping[str, object], *, device: str | torch.device = "cuda:0") -> None:
+        from .circuit import HipCircuit
+
+        chain_of(plan)
+        for n in plan.tensors:
+            v = tensors[n]
+            if np.iscomplexobj(v) or (hasattr(v, "is_complex") and v.is_complex()):
+                raise NotImplementedError("HipHMM: complex parameter tensors")
+        if max(l.num_output_units for l in plan.layers) > 1024:
+            raise NotImplementedError("HipHMM: more than 1024 latent states")
+        self.device = torch.device(device)
+        # (row-major weights: the chain kernel lays a step's rows out itself while it stages them)
+        self.hc = HipCircuit(plan, tensors, device=self.device, fuse=False, tiled_weights=False)
+        self.store = self.hc.store
+        self.plan = self.hc.plan  # (padded where HipCircuit pads)
+        self.steps = chain_of(self.plan)
+        self.input_layer = next(i for i, l in enumerate(self.plan.layers) if l.inputs is None)
+        self.K = self.plan.layers[self.input_layer].num_output_units
+        self.categorical = self.plan.layers[self.input_layer].type == "categorical"
+        self.last_launches = 0  # launches of the last call of `log_prob`
+        self._key = None
+        self._tab: dict | None = None
+
+    @property
+    def num_variables(self) -> int:
+        return self.plan.num_variables
+
+    def tables(self) -> dict:
+        """The parameter graphs evaluated for the current state of the store, and the device tables of the steps."""
+        key = (self.store.version, self.store.state())
+        if self._tab is not None and self._key == key:
+            return self._tab
+        hc = self.hc
+        with torch.cuda.device(self.device):
+            hc._enqueue_params(torch.cuda.current_stream(self.device).cuda_stream)
+        ws = [hc.layers[s.layer]._w for s in self.steps]
+        for s, w in zip(self.steps, ws):
+            l = self.plan.layers[s.layer]
+            if w is None or w.dtype != torch.float32 or not w.is_contiguous() or tuple(w.shape) != (1, l.num_output_units, self.K):
+                raise NotImplementedError(f"HipHMM: the weight of layer {s.layer} is not a real (1, Ko, K) block")
+        tab = {
+            "w": torch.tensor([w.data_ptr() for w in ws], dtype=torch.int64).to(self.device),
+            "keep": ws,
+            "fold": torch.tensor([s.fold for s in self.steps], dtype=torch.int32).to(self.device),
+            "var": torch.tensor([s.var for s in self.steps], dtype=torch.int32).to(self.device),
+        }
+        if self.categorical:
+            t = hc.layers[self.input_layer]._table  # (F, C + 1, K) logarithms, a (fold, category) row contiguous
+            if t is None or t.dtype != torch.float32 or not t.is_contiguous():
+                raise NotImplementedError("HipHMM: the Categorical layer has no real table of logarithms")
+            tab["rows"] = t
+        self._tab, self._key = tab, key
+        return tab
+
+    def _mask(self, integrate_vars) -> torch.Tensor | None:
+        if integrate_vars is None:
+            return None
+        from .squared import _mask_of
+
+        m = _mask_of(integrate_vars, self.plan.num_variables)
+        return torch.from_numpy(m.astype(np.int32)).to(self.device) if m.any() else None
+
+    def rows_per_chunk(self) -> int:
+        """Rows of a chunk by default for inputs other than Categorical: the block of emissions at or below 1 GiB."""
+        return max(1, _CHUNK_BYTES // (len(self.steps) * self.K * 4))
+
+    def log_prob(self, x: torch.Tensor, integrate_vars=None, *, rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B,)`` fp32: ``log p(x)`` with the variables of `integrate_vars` (ids, or a ``(D,)`` bool mask), and every entry
+        ``x[b, v] == -1`` (NaN for Gaussian inputs), summed out.  `x`: ``(B, T)``, int64 for discrete inputs, fp32 for Gaussian
+        ones.  A category outside its layer's range makes the row NaN (inputs other than Categorical: the batch, with
+        `HipCircuit.check_inputs` of the owned circuit raising).  A row's value does not depend on `rows_per_chunk`."""
+        D = self.plan.num_variables
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
+        if rows_per_chunk is not None and int(rows_per_chunk) <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+        B, T = int(x.shape[0]), len(self.steps)
+        if B <= 0:
+            raise ValueError("empty batch")
+        hc, tab = self.hc, self.tables()
+        self.last_launches = 0
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            out = torch.empty(B, dtype=torch.float32, device=self.device)
+            head = (tab["w"].data_ptr(), tab["fold"].data_ptr(), tab["var"].data_ptr(), T, self.K)
+            if self.categorical:
+                mask = self._mask(integrate_vars)
+                x = x.to(self.device).to(torch.int64).contiguous()
+                C = self.plan.layers[self.input_layer].config["num_categories"]
+                capi.call("ck_hmm_forward", *head, tab["rows"].data_ptr(), x.data_ptr(), D, C,
+                          None if mask is None else mask.data_ptr(), B, out.data_ptr(), stream)
+                self.last_launches = 1
+                return out
+            # any other input layer: its own launch writes the (F, rows, K) emissions of a chunk, missing entries included
+            if integrate_vars is not None:
+                x = hc._apply_integration_mask(x.to(self.device), integrate_vars)
+            layer = hc.layers[self.input_layer]
+            n = min(B, int(rows_per_chunk) if rows_per_chunk is not None else self.rows_per_chunk())
+            rows = torch.empty((layer.num_folds, n, self.K), dtype=torch.float32, device=self.device)
+            xt = torch.empty((D, n), dtype=torch.float32 if layer.wants_float_input else torch.int32, device=self.device)
+            for r0 in range(0, B, n):
+                nb = min(n, B - r0)
+                xf, xi = hc._prepare_input(x[r0:r0 + nb])
+                if layer.wants_float_input:
+                    capi.call("ck_transpose_f32", xf.data_ptr(), xt.data_ptr(), nb, D, stream)
+                else:
+                    capi.call("ck_stage_categories", xi.data_ptr(), xt.data_ptr(), nb, D, hc._num_states_dev().data_ptr(),
+                              hc._bad_input.data_ptr(), 0, None, stream)
+                layer.launch_input(xt, D, rows, nb, stream)
+                capi.call("ck_hmm_forward", *head, rows.data_ptr(), None, D, 0, None, nb, out[r0:].data_ptr(), stream)
+                self.last_launches += 3
+            if not layer.wants_float_input:
+                capi.call("ck_poison_outputs", out.data_ptr(), B, hc._bad_input.data_ptr(), stream)
+                self.last_launches += 1
+        return out
+
+    def __call__(self, x: torch.Tensor, *, integrate_vars=None) -> torch.Tensor:
+        """``(B, 1, 1)`` like `HipCircuit.forward`."""
+        return self.log_prob(x, integrate_vars).view(-1, 1, 1)

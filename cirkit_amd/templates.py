@@ -934,3 +934,54 @@ def tabular_data(
         num_input_units=num_input_units, num_sum_units=num_sum_units, num_classes=num_classes,
         use_mixing_weights=use_mixing_weights, semiring=semiring,
     )
+
+
+def hmm(
+    ordering,
+    input_layer: str = "categorical",
+    num_latent_states: int = 1,
+    *,
+    input_layer_kwargs: dict | list | None = None,
+    sum_weight_activation: str = "softmax",
+    semiring: str = "lse-sum",
+) -> Plan:
+    """``pgms.hmm`` (cirkit/templates/pgms.py:76-180) followed by ``compile(fold=True, optimize=True)``: an inhomogeneous
+    hidden Markov model along `ordering`, one input layer and one K x K transition per position.  The chain starts at
+    ``ordering[-1]`` and ends, with a K -> 1 sum, at ``ordering[0]``; folded, it is one input layer of T folds, a dense
+    sum and T - 1 CP-T layers of one fold each ("Hidden Markov models").  `input_layer_kwargs` is
+    one dict for all positions or a list with one per variable (``num_categories``, ``total_count``)."""
+    ordering = list(ordering)
+    if not ordering:
+        raise ValueError("The ordering should be non-empty")
+    T = len(ordering)
+    if set(ordering) != set(range(T)):
+        raise ValueError("The 'ordering' of variables is not valid")
+    if input_layer not in ("categorical", "binomial", "gaussian"):
+        raise ValueError(f"Unknown input layer called {input_layer}")
+    if input_layer_kwargs is None:
+        kwargs = [{}] * T
+    elif isinstance(input_layer_kwargs, list):
+        if len(input_layer_kwargs) != T:
+            raise ValueError(f"The list of input layer kwargs should have length num_variables={T}")
+        if not all(isinstance(kw, dict) for kw in input_layer_kwargs):
+            raise ValueError("The list of input layer kwargs should be a list of dictionaries")
+        kwargs = input_layer_kwargs
+    else:
+        kwargs = [input_layer_kwargs] * T
+    specs = [_tabular_input_spec({"name": input_layer, "args": kw}) for kw in kwargs]
+    K = int(num_latent_states)
+
+    def dense(ko: int) -> _L:
+        return _L("sum", K, ko, params={"weight": _pg_tensor((ko, K), sum_weight_activation)})
+
+    layers = [_input_layer(ordering[-1], specs[-1], K, None), dense(1 if T == 1 else K)]
+    ins: dict[_L, list[_L]] = {layers[1]: [layers[0]]}
+    for i in reversed(range(T - 1)):
+        last, leaf, prod, d = layers[-1], _input_layer(ordering[i], specs[i], K, None), _L("hadamard", K, K, arity=2), dense(1 if i == 0 else K)
+        layers.extend([leaf, prod, d])
+        ins[prod] = [last, leaf]
+        ins[d] = [prod]
+    out = layers[-1]
+    layers = _kahn(layers, ins)
+    layers, ins, out = _optimize_layers(layers, ins, out)
+    return _fold_layers(layers, ins, out, semiring, T, "")

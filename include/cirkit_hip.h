@@ -1793,6 +1793,24 @@ int ck_squared_path_steps(const float* full, const float* cst, const float* rank
                           int64_t cd_row, int64_t cd_step, float* log_prob, int64_t lp_row, int64_t lp_step, int C_max, int B,
                           int rows_per_block, int complex_values, void* stream);
 
+/* ---- hidden Markov models ("Hidden Markov models"; additive, ABI 51) ----
+ * The forward algorithm of a chain plan in ONE launch: what the reference evaluates as T dependent layers of one fold each --
+ * a dense sum, then T - 1 CP-T layers (layers/optimized.py:106-178: Hadamard product with the step's input fold, then the
+ * K x K sum), each through LSESumSemiring.apply_reduce (semiring.py:383-408) -- with v_{-1} = 0, for s = 0 .. T - 1:
+ *     v_s[b, o] = log sum_i W_s[o, i] exp(v_{s-1}[b, i] + e_s[b, i]),      out[b] = v_{T-1}[b, 0]     (fp32)
+ * w_steps (T) DEVICE table of device pointers: the evaluated weights of step s, row-major (Ko, K), Ko = K but for the last
+ * step, of which only row 0 is read.  step_fold / step_var (T) int32 on the device: the input fold and the variable of a step.
+ * K: a multiple of 32 in 32 .. 1024.  The K log emissions e_s[b, :] are one row of `rows`:
+ *   x != NULL -- (B, D) int64 categories: `rows` is a Categorical layer's (F, C + 1, K) table of logarithms (see
+ *     ck_categorical_fwd) and the row is (step_fold[s], x[b, step_var[s]]); a NEGATIVE entry, or integrate[step_var[s]] != 0
+ *     (integrate: (D) int32 on the device, or NULL), sums the variable out: e_s[b, :] = 0; an entry >= C makes out[b] NaN;
+ *   x == NULL -- `rows` is the (F, B, K) block an input layer's own launch wrote (ck_gaussian_fwd, ck_categorical_fwd on a
+ *     Binomial table), missing entries included, and the row is (step_fold[s], b).
+ * A row without mass is -inf, never NaN.  A workgroup owns 32 rows for the whole chain (ck_hmm.hip); a row's result does not
+ * depend on B or on its place in the batch. */
+int ck_hmm_forward(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, const float* rows,
+                   const int64_t* x, int D, int C, const int32_t* integrate, int B, float* out, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
