@@ -12,7 +12,11 @@ Any other input layer (Binomial, Gaussian) is evaluated by its own launch into a
 time.  Missing entries -- a variable in `integrate_vars`, or per entry ``x[b, v] == -1`` (NaN for Gaussian inputs): what padding
 sequences of different lengths needs -- are summed out.
 
-Out of scope: Baum-Welch / expected statistics, smoothing posteriors, Viterbi and sampling of chains; homogeneous chains (the
+`HipHMM.state_posteriors` is forward-backward smoothing, ``p(z_v = k | evidence)`` for every position: the forward launch
+instantiated to leave its hand-off in the ``(B, D, K)`` result, and `ck_hmm_backward`, which walks the chain back with the weights
+transposed and turns that buffer into posteriors in place -- two launches where `log_prob` takes one.
+
+Out of scope: Baum-Welch / pairwise expected statistics, Viterbi and sampling of chains; homogeneous chains (the
 kernel's table of weight pointers already allows shared transitions); bf16-piece variants; training beyond what `HipTrainer` does
 with a chain plan layer by layer; routing `HipCircuit.forward` to this kernel.
 """
@@ -120,6 +124,7 @@ class HipHMM:
         from .circuit import HipCircuit
 
         chain_of(plan)
+        self.num_states = next(l for l in plan.layers if l.inputs is None).num_output_units  # (before any padding)
         for n in plan.tensors:
             v = tensors[n]
             if np.iscomplexobj(v) or (hasattr(v, "is_complex") and v.is_complex()):
@@ -135,7 +140,7 @@ class HipHMM:
         self.input_layer = next(i for i, l in enumerate(self.plan.layers) if l.inputs is None)
         self.K = self.plan.layers[self.input_layer].num_output_units
         self.categorical = self.plan.layers[self.input_layer].type == "categorical"
-        self.last_launches = 0  # launches of the last call of `log_prob`
+        self.last_launches = 0  # launches of the last call of `log_prob` or `state_posteriors`
         self._key = None
         self._tab: dict | None = None
 
@@ -187,6 +192,25 @@ class HipHMM:
         ``x[b, v] == -1`` (NaN for Gaussian inputs), summed out.  `x`: ``(B, T)``, int64 for discrete inputs, fp32 for Gaussian
         ones.  A category outside its layer's range makes the row NaN (inputs other than Categorical: the batch, with
         `HipCircuit.check_inputs` of the owned circuit raising).  A row's value does not depend on `rows_per_chunk`."""
+        return self._chain(x, integrate_vars, rows_per_chunk, False)[0]
+
+    def state_posteriors(self, x: torch.Tensor, integrate_vars=None, *, rows_per_chunk: int | None = None,
+                         return_log_prob: bool = False):
+        """``(B, D, K)`` fp32 smoothing posteriors ``[b, v, k] = p(z_v = k | evidence of row b)``, indexed by variable id, `K` the
+        number of latent states (a view of the buffer padded to 32 units; padded units carry 0); with `return_log_prob` also the
+        ``(B,)`` log-likelihood of the same pass.  `x`, `integrate_vars` and `rows_per_chunk` as for `log_prob`.  Forward-backward
+        in two launches (`ck_hmm_forward_keep`, `ck_hmm_backward`) where `log_prob` takes one: the forward leaves its hand-off in
+        the result buffer and the backward pass turns it into posteriors in place, each (row, position) normalised by its own
+        sum -- no ``(T, B, K)`` scratch besides the result.  A row without mass (``log p = -inf``) is NaN in every entry, and so is
+        whatever `log_prob` makes NaN (a category outside its layer's range).  A row's values do not depend on
+        `rows_per_chunk`."""
+        out, post = self._chain(x, integrate_vars, rows_per_chunk, True)
+        post = post[:, :, :self.num_states]
+        return (post, out) if return_log_prob else post
+
+    def _chain(self, x: torch.Tensor, integrate_vars, rows_per_chunk: int | None, keep: bool):
+        """``(log_prob, None)`` by the forward launch, or ``(log_prob, (B, D, K) posteriors)`` by the keeping forward and the
+        backward pass."""
         D = self.plan.num_variables
         if x.dim() != 2 or x.shape[1] != D:
             raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
@@ -199,16 +223,28 @@ class HipHMM:
         self.last_launches = 0
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            out = torch.empty(B, dtype=torch.float32, device=self.device)
+            # one buffer for both results (the range check of discrete inputs poisons it in one launch): the posteriors start
+            # 16-byte aligned, and are 0 for a variable that no step reads
+            Bp = -(-B // 4) * 4
+            flat = (torch.zeros if keep and D != T else torch.empty)(Bp + (B * D * self.K if keep else 0), dtype=torch.float32,
+                                                                     device=self.device)
+            out, post = flat[:B], (flat[Bp:].view(B, D, self.K) if keep else None)
             head = (tab["w"].data_ptr(), tab["fold"].data_ptr(), tab["var"].data_ptr(), T, self.K)
+
+            def run(source, nb, r0):
+                if not keep:
+                    capi.call("ck_hmm_forward", *head, *source, nb, out[r0:].data_ptr(), stream)
+                    return 1
+                capi.call("ck_hmm_forward_keep", *head, *source, nb, out[r0:].data_ptr(), post[r0:].data_ptr(), stream)
+                capi.call("ck_hmm_backward", *head, *source, nb, out[r0:].data_ptr(), post[r0:].data_ptr(), stream)
+                return 2
+
             if self.categorical:
                 mask = self._mask(integrate_vars)
                 x = x.to(self.device).to(torch.int64).contiguous()
                 C = self.plan.layers[self.input_layer].config["num_categories"]
-                capi.call("ck_hmm_forward", *head, tab["rows"].data_ptr(), x.data_ptr(), D, C,
-                          None if mask is None else mask.data_ptr(), B, out.data_ptr(), stream)
-                self.last_launches = 1
-                return out
+                self.last_launches = run((tab["rows"].data_ptr(), x.data_ptr(), D, C, None if mask is None else mask.data_ptr()), B, 0)
+                return out, post
             # any other input layer: its own launch writes the (F, rows, K) emissions of a chunk, missing entries included
             if integrate_vars is not None:
                 x = hc._apply_integration_mask(x.to(self.device), integrate_vars)
@@ -225,12 +261,11 @@ class HipHMM:
                     capi.call("ck_stage_categories", xi.data_ptr(), xt.data_ptr(), nb, D, hc._num_states_dev().data_ptr(),
                               hc._bad_input.data_ptr(), 0, None, stream)
                 layer.launch_input(xt, D, rows, nb, stream)
-                capi.call("ck_hmm_forward", *head, rows.data_ptr(), None, D, 0, None, nb, out[r0:].data_ptr(), stream)
-                self.last_launches += 3
+                self.last_launches += 2 + run((rows.data_ptr(), None, D, 0, None), nb, r0)
             if not layer.wants_float_input:
-                capi.call("ck_poison_outputs", out.data_ptr(), B, hc._bad_input.data_ptr(), stream)
+                capi.call("ck_poison_outputs", flat.data_ptr(), flat.numel(), hc._bad_input.data_ptr(), stream)
                 self.last_launches += 1
-        return out
+        return out, post
 
     def __call__(self, x: torch.Tensor, *, integrate_vars=None) -> torch.Tensor:
         """``(B, 1, 1)`` like `HipCircuit.forward`."""

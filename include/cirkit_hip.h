@@ -1811,6 +1811,24 @@ int ck_squared_path_steps(const float* full, const float* cst, const float* rank
 int ck_hmm_forward(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, const float* rows,
                    const int64_t* x, int D, int C, const int32_t* integrate, int B, float* out, void* stream);
 
+/* Forward-backward smoothing of the same chain in TWO launches ("Smoothing posteriors"; additive, ABI 51).
+ * Operands as for ck_hmm_forward; D >= T is also the row stride of `keep`, a (B, D, K) fp32 buffer indexed by VARIABLE.
+ * ck_hmm_forward_keep is ck_hmm_forward's kernel, instantiated to store per step the hand-off t_s = v_{s-1} + e_s, minus a
+ * per-row, per-step constant (the row's running scale before the step), into keep[b, step_var[s], :], each wave its own blocks
+ * of units straight from registers; log_prob (B) receives what ck_hmm_forward writes to `out` (NaN for a category >= C).
+ * ck_hmm_backward then runs, with beta_{T-1}[i] = log W_{T-1}[0, i], for s = T - 1 .. 0
+ *     gamma_s[b, i]    = exp(t_s[i] + beta_s[i]) / sum_j exp(t_s[j] + beta_s[j])        -> keep[b, step_var[s], :], in place
+ *     beta_{s-1}[b, i] = log sum_o W_{s-1}[o, i] exp(e_s[b, o] + beta_s[b, o])           (minus a per-row, per-step constant)
+ * so that keep[b, v, k] = p(z_v = k | evidence of row b): every (row, step) is normalised by its own sum, log_prob is read only
+ * for its NaN.  A row the forward marked NaN is NaN in every entry; so is a row without mass (0 / 0); units whose weights
+ * columns are zero (padding) come out 0.  Entries of keep that no step names are left alone.  The same 32 rows per workgroup and
+ * unit blocks per wave as the forward; the weights are streamed TRANSPOSED, 16 rows x 32 columns a unit (ck_hmm.hip).  A row's
+ * result does not depend on B or on its place in the batch. */
+int ck_hmm_forward_keep(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, const float* rows,
+                        const int64_t* x, int D, int C, const int32_t* integrate, int B, float* log_prob, float* keep, void* stream);
+int ck_hmm_backward(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, const float* rows,
+                    const int64_t* x, int D, int C, const int32_t* integrate, int B, const float* log_prob, float* keep, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
