@@ -23,9 +23,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # which matter because fp32-input MFMA shares the fp32 ALUs with the VALU -- DESIGN.md section 4.2).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]
-# per-file additions: ck_hmm.hip is compiled without packed fp32 instructions (v_pk_mul_f32 and its kin); the host pass of
-# hipcc does not know the feature and says so, the device pass honours it
-FILE_FLAGS = {"ck_hmm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# per-file additions: the chain kernels are compiled without packed fp32 instructions (v_pk_mul_f32 and its kin); the host pass
+# of hipcc does not know the feature and says so, the device pass honours it
+_NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"ck_hmm.hip": _NO_PACKED_FP32, "ck_hmm_viterbi.hip": _NO_PACKED_FP32}
 
 
 def _newer(target: str, deps: list[str]) -> bool:

@@ -16,9 +16,13 @@ sequences of different lengths needs -- are summed out.
 instantiated to leave its hand-off in the ``(B, D, K)`` result, and `ck_hmm_backward`, which walks the chain back with the weights
 transposed and turns that buffer into posteriors in place -- two launches where `log_prob` takes one.
 
-Out of scope: Baum-Welch / pairwise expected statistics, Viterbi and sampling of chains; homogeneous chains (the
+`HipHMM.viterbi` is the most probable state sequence, ``argmax_z p(z, evidence)``, and its log-probability: a max-product forward
+pass on the vector ALU that keeps the same hand-off (`ck_hmm_viterbi_forward`) and a walk back over it, one wave a row
+(`ck_hmm_viterbi_backtrack`; cirkit_amd/csrc/ck_hmm_viterbi.hip) -- two launches again.
+
+Out of scope: Baum-Welch / pairwise expected statistics, sampling of paths and k-best paths; homogeneous chains (the
 kernel's table of weight pointers already allows shared transitions); bf16-piece variants; training beyond what `HipTrainer` does
-with a chain plan layer by layer; routing `HipCircuit.forward` to this kernel.
+with a chain plan layer by layer; routing `HipCircuit.forward` or `HipCircuit.mpe` to these kernels.
 """
 
 from __future__ import annotations
@@ -140,7 +144,7 @@ class HipHMM:
         self.input_layer = next(i for i, l in enumerate(self.plan.layers) if l.inputs is None)
         self.K = self.plan.layers[self.input_layer].num_output_units
         self.categorical = self.plan.layers[self.input_layer].type == "categorical"
-        self.last_launches = 0  # launches of the last call of `log_prob` or `state_posteriors`
+        self.last_launches = 0  # launches of the last call of `log_prob`, `state_posteriors` or `viterbi`
         self._key = None
         self._tab: dict | None = None
 
@@ -192,7 +196,7 @@ class HipHMM:
         ``x[b, v] == -1`` (NaN for Gaussian inputs), summed out.  `x`: ``(B, T)``, int64 for discrete inputs, fp32 for Gaussian
         ones.  A category outside its layer's range makes the row NaN (inputs other than Categorical: the batch, with
         `HipCircuit.check_inputs` of the owned circuit raising).  A row's value does not depend on `rows_per_chunk`."""
-        return self._chain(x, integrate_vars, rows_per_chunk, False)[0]
+        return self._chain(x, integrate_vars, rows_per_chunk, "log_prob")[0]
 
     def state_posteriors(self, x: torch.Tensor, integrate_vars=None, *, rows_per_chunk: int | None = None,
                          return_log_prob: bool = False):
@@ -204,13 +208,27 @@ class HipHMM:
         sum -- no ``(T, B, K)`` scratch besides the result.  A row without mass (``log p = -inf``) is NaN in every entry, and so is
         whatever `log_prob` makes NaN (a category outside its layer's range).  A row's values do not depend on
         `rows_per_chunk`."""
-        out, post = self._chain(x, integrate_vars, rows_per_chunk, True)
+        out, post, _ = self._chain(x, integrate_vars, rows_per_chunk, "posteriors")
         post = post[:, :, :self.num_states]
         return (post, out) if return_log_prob else post
 
-    def _chain(self, x: torch.Tensor, integrate_vars, rows_per_chunk: int | None, keep: bool):
-        """``(log_prob, None)`` by the forward launch, or ``(log_prob, (B, D, K) posteriors)`` by the keeping forward and the
-        backward pass."""
+    def viterbi(self, x: torch.Tensor, integrate_vars=None, *, rows_per_chunk: int | None = None):
+        """``(states, score)``: the most probable state sequence given the observed entries of each row, and its log-probability
+        ``max_z log p(z, observed entries)`` -- ``(B,)`` fp32.  ``states`` is ``(B, D)`` int64 indexed by variable id:
+        ``states[b, var_s]`` is the state of step ``s``, the unit index that is the last axis of `state_posteriors`, always
+        ``< num_states``; -1 for a variable that no step reads.  `x`, `integrate_vars` and `rows_per_chunk` as for `log_prob`:
+        missing entries are summed out (their emission row is zeros).  Between paths of equal score the choice is free.  A row
+        without a path of positive mass has score -inf, a row that `log_prob` makes NaN has score NaN; both have -1 in every
+        state.  Two launches: the max-product forward (`ck_hmm_viterbi_forward`) keeps its hand-off in a ``(B, D, K)`` scratch,
+        the walk back (`ck_hmm_viterbi_backtrack`) recomputes each decision from it and one weight row.  A row's result does
+        not depend on `rows_per_chunk`."""
+        out, _, states = self._chain(x, integrate_vars, rows_per_chunk, "viterbi")
+        return states, out
+
+    def _chain(self, x: torch.Tensor, integrate_vars, rows_per_chunk: int | None, query: str):
+        """``(log_prob, None, None)`` by the forward launch; ``(log_prob, (B, D, K) posteriors, None)`` by the keeping forward
+        and the backward pass; ``(score, (B, D, K) hand-off, (B, D) states)`` by the max-product forward and the walk back."""
+        keep, viterbi = query != "log_prob", query == "viterbi"
         D = self.plan.num_variables
         if x.dim() != 2 or x.shape[1] != D:
             raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
@@ -226,15 +244,27 @@ class HipHMM:
             # one buffer for both results (the range check of discrete inputs poisons it in one launch): the posteriors start
             # 16-byte aligned, and are 0 for a variable that no step reads
             Bp = -(-B // 4) * 4
-            flat = (torch.zeros if keep and D != T else torch.empty)(Bp + (B * D * self.K if keep else 0), dtype=torch.float32,
-                                                                     device=self.device)
+            flat = (torch.zeros if keep and not viterbi and D != T else torch.empty)(Bp + (B * D * self.K if keep else 0),
+                                                                                     dtype=torch.float32, device=self.device)
             out, post = flat[:B], (flat[Bp:].view(B, D, self.K) if keep else None)
+            states = None
+            if viterbi:  # (-1 where no step writes)
+                states = (torch.empty((B, D), dtype=torch.int64, device=self.device) if D == T else
+                          torch.full((B, D), -1, dtype=torch.int64, device=self.device))
             head = (tab["w"].data_ptr(), tab["fold"].data_ptr(), tab["var"].data_ptr(), T, self.K)
+
+            def backtrack(nb, r0):
+                capi.call("ck_hmm_viterbi_backtrack", tab["w"].data_ptr(), tab["var"].data_ptr(), T, self.K, self.num_states, D, nb,
+                          out[r0:].data_ptr(), post[r0:].data_ptr(), states[r0:].data_ptr(), stream)
+                return 1
 
             def run(source, nb, r0):
                 if not keep:
                     capi.call("ck_hmm_forward", *head, *source, nb, out[r0:].data_ptr(), stream)
                     return 1
+                if viterbi:
+                    capi.call("ck_hmm_viterbi_forward", *head, *source, nb, out[r0:].data_ptr(), post[r0:].data_ptr(), stream)
+                    return 1 + (backtrack(nb, r0) if self.categorical else 0)
                 capi.call("ck_hmm_forward_keep", *head, *source, nb, out[r0:].data_ptr(), post[r0:].data_ptr(), stream)
                 capi.call("ck_hmm_backward", *head, *source, nb, out[r0:].data_ptr(), post[r0:].data_ptr(), stream)
                 return 2
@@ -244,7 +274,7 @@ class HipHMM:
                 x = x.to(self.device).to(torch.int64).contiguous()
                 C = self.plan.layers[self.input_layer].config["num_categories"]
                 self.last_launches = run((tab["rows"].data_ptr(), x.data_ptr(), D, C, None if mask is None else mask.data_ptr()), B, 0)
-                return out, post
+                return out, post, states
             # any other input layer: its own launch writes the (F, rows, K) emissions of a chunk, missing entries included
             if integrate_vars is not None:
                 x = hc._apply_integration_mask(x.to(self.device), integrate_vars)
@@ -265,7 +295,9 @@ class HipHMM:
             if not layer.wants_float_input:
                 capi.call("ck_poison_outputs", flat.data_ptr(), flat.numel(), hc._bad_input.data_ptr(), stream)
                 self.last_launches += 1
-        return out, post
+            if viterbi:  # the walk back reads the score, so it follows the range check's verdict on it
+                self.last_launches += sum(backtrack(min(n, B - r0), r0) for r0 in range(0, B, n))
+        return out, post, states
 
     def __call__(self, x: torch.Tensor, *, integrate_vars=None) -> torch.Tensor:
         """``(B, 1, 1)`` like `HipCircuit.forward`."""

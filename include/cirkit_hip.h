@@ -1829,6 +1829,25 @@ int ck_hmm_forward_keep(const void* const* w_steps, const int32_t* step_fold, co
 int ck_hmm_backward(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, const float* rows,
                     const int64_t* x, int D, int C, const int32_t* integrate, int B, const float* log_prob, float* keep, void* stream);
 
+/* Viterbi decoding of the same chain in TWO launches ("Viterbi decoding"; additive, ABI 51).
+ * ck_hmm_viterbi_forward: operands as for ck_hmm_forward_keep.  The max-product pass
+ *     delta_s[b, o] = log max_i W_s[o, i] exp(delta_{s-1}[b, i] + e_s[b, i]),   delta_{-1} = 0
+ * with the forward's ownership (32 rows per workgroup on chip for the whole chain, blocks of 32 units per wave) and its
+ * hand-off; the contraction runs on the vector ALU (ck_hmm_viterbi.hip).  score (B) receives delta_{T-1}[b, 0] =
+ * max_z log p(z, observed entries of row b): -inf for a row without a path of positive mass, NaN for a category >= C.
+ * keep[b, step_var[s], :] receives t_s = delta_{s-1} + e_s minus a per-row, per-step constant; other entries are left alone.
+ * ck_hmm_viterbi_backtrack: one wave a row walks from step T - 1 down,
+ *     z_{T-1} = argmax_i t_{T-1}[i] + log W_{T-1}[0, i],    z_{s-1} = argmax_i t_{s-1}[i] + log W_{s-1}[z_s, i]
+ * over i < num_states only (1 <= num_states <= K: padded units never win), the lowest index between equal values, and writes
+ * states[b, step_var[s]] = z_s as int64 into the (B, D) buffer `states`; -1 at every step of a row whose score is -inf or NaN.
+ * Entries of `states` that no step names are left alone.  It reads `score` and `keep` as launch 1 (and whatever ran between
+ * them) left them.  A row's result does not depend on B or on its place in the batch. */
+int ck_hmm_viterbi_forward(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K,
+                           const float* rows, const int64_t* x, int D, int C, const int32_t* integrate, int B, float* score, float* keep,
+                           void* stream);
+int ck_hmm_viterbi_backtrack(const void* const* w_steps, const int32_t* step_var, int T, int K, int num_states, int D, int B,
+                             const float* score, const float* keep, int64_t* states, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
