@@ -32,6 +32,8 @@ struct HmmArgs {
   float* out;             // (B)
   int C, D, T, B, K;
   float* keep;            // (B, D, K) or nullptr: the hand-off of every step (KEEP forward), turned into posteriors in place (backward)
+  float* pair_a;          // (B, D, K) or nullptr: the statistics backward leaves the pair sum's operand rows a'_s and r'_s here
+  float* pair_r;          //   (ck_hmm_stats.hip), by variable like `keep`
 };
 
 __device__ __forceinline__ void lds_w4(uint32_t addr, float a, float b, float c, float d) {

@@ -248,9 +248,20 @@ __device__ __forceinline__ void lds_read_wt(f32x2v& w01, f32x2v& w23, f32x2v& w4
       : "memory");
 }
 
-template <int NOB>
+//
+// STATS (ck_hmm_backward_stats, DESIGN.md section 11, "Expected statistics (Baum-Welch E-step)"): the same pass also leaves,
+// per (row, step), the two operand rows of the pair sum  N_s = W_s o (R_{s+1}^T A_s)  of ck_hmm_stats.hip:
+//     a_s = exp(t_s - M_s)  (M_s the forward's clamped row maximum of t_s: a third maximum in the first exchange)
+//     r_s = exp(q_s - Mu_s) / z_s = exp(q_s - Mq_s) c_s,   c_s = exp(Mq_s - Mu_s) / z_s
+// Since exp(t_{s+1}[o]) = exp(e_{s+1}[o]) sum_i W_s[o, i] a_s[i], sum_{o,i} r_{s+1}[o] W_s[o, i] a_s[i] = 1 for a live row, log p
+// never subtracted.  c reaches e^154 where y is tiny (peaked parameters), so its power of two 2^lc is SPLIT: r' = 2^h exp(q - Mq)
+// with h = floor(lc / 2) goes to pair_r[b, var_s, :] and a'_{s-1} = 2^(lc - h) exp(t_{s-1} - M_{s-1}) to pair_a[b, var_{s-1}, :] one step
+// later, both folded into the offset of the exponential: operands of a pair that counts stay within 2^+-111.  A DEAD row (log p not
+// finite) is zeros in gamma and in both operands.  The STATS = false instantiation is the code it was.
+template <int NOB, bool STATS = false>
 __global__ void __launch_bounds__(256) hmm_backward_kernel(const HmmArgs a) {
   constexpr int NBUF = NOB > 4 ? 3 : 8;
+  constexpr int NMAX = STATS ? 3 : 2;  // row maxima of the first exchange
   constexpr bool EARLY = NOB <= 4;  // three register tiles a block (e, t, beta): above, t is read back after the contraction
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int K = a.K, NQ = K >> 5, T = a.T;
@@ -264,14 +275,16 @@ __global__ void __launch_bounds__(256) hmm_backward_kernel(const HmmArgs a) {
 #pragma unroll
   for (int j = 0; j < NOB; ++j) nob += wave + nwaves * j < NQ ? 1 : 0;
 
-  // LDS: activation tile [NQ][4][64] float4 | row maxima [2][4][32] | row sums [4][32] | weight rings [waves][NBUF][8][64] float
+  // LDS: activation tile [NQ][4][64] float4 | row maxima [NMAX][4][32] | row sums [4][32] | weight rings [waves][NBUF][8][64] float
   const uint32_t act = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(smem));
   const uint32_t red = act + NQ * 4096;
-  const uint32_t rsum = red + 2 * kHmmWaves * 128;
-  float* const ring_p = smem + NQ * 1024 + 3 * kHmmWaves * 32 + wave * (NBUF * kHmmUnit);
+  const uint32_t rsum = red + NMAX * kHmmWaves * 128;
+  float* const ring_p = smem + NQ * 1024 + (NMAX + 1) * kHmmWaves * 32 + wave * (NBUF * kHmmUnit);
   const uint32_t ring = rsum + kHmmWaves * 128 + wave * (NBUF * kHmmUnit * 4) + lane * 4;
 
   const bool bad = a.out[bl] != a.out[bl];  // the forward's verdict on the row
+  const bool dead = STATS && !(fabsf(a.out[bl]) < INFINITY);  // (NaN, or no mass)
+  float ca = 0.f;  // STATS: lc - h of the step above, the exponent that a' of this step carries
   auto load_x = [&](int s) -> int64_t { return (a.x != nullptr && s >= 0) ? a.x[static_cast<int64_t>(bl) * a.D + a.var[s]] : 0; };
   auto row_of = [&](int s, int64_t xv) -> const float* {  // nullptr: the entry is missing (or out of range: the row is NaN)
     const int64_t f = a.fold[s];
@@ -341,21 +354,30 @@ __global__ void __launch_bounds__(256) hmm_backward_kernel(const HmmArgs a) {
     for (int u = 0; u < NBUF - 1 && u < U; ++u) issue(w, u);
 
     // ---- A: q = e + beta, u = t + beta, their row maxima in one exchange
-    float mq = -INFINITY, mu = -INFINITY;
+    float mq = -INFINITY, mu = -INFINITY, mt = -INFINITY;
 #pragma unroll
     for (int j = 0; j < NOB; ++j)
       if (j < nob) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           e[j][i] += be[j][i];
-          t[j][i] += be[j][i];
           mq = fmaxf(mq, e[j][i]);
-          mu = fmaxf(mu, t[j][i]);
+          if constexpr (STATS) {  // (t itself stays until a' is formed from it)
+            mt = fmaxf(mt, t[j][i]);
+            mu = fmaxf(mu, t[j][i] + be[j][i]);
+          } else {
+            t[j][i] += be[j][i];
+            mu = fmaxf(mu, t[j][i]);
+          }
         }
       }
     mq = ck::xhalf_max(mq);
     mu = ck::xhalf_max(mu);
     asm volatile("ds_write_b32 %0, %1\n\tds_write_b32 %0, %2 offset:512" ::"v"(red + (wave * 32 + row) * 4), "v"(mq), "v"(mu) : "memory");
+    if constexpr (STATS) {
+      mt = ck::xhalf_max(mt);
+      asm volatile("ds_write_b32 %0, %1 offset:1024" ::"v"(red + (wave * 32 + row) * 4), "v"(mt) : "memory");
+    }
     sync_lds();
     for (int k = 0; k < nwaves; ++k) {
       float o0, o1;
@@ -365,9 +387,35 @@ __global__ void __launch_bounds__(256) hmm_backward_kernel(const HmmArgs a) {
                    : "memory");
       mq = fmaxf(mq, o0);
       mu = fmaxf(mu, o1);
+      if constexpr (STATS) {
+        float o2;
+        asm volatile("ds_read_b32 %0, %1 offset:1024\n\ts_waitcnt lgkmcnt(0)" : "=v"(o2) : "v"(red + (k * 32 + row) * 4) : "memory");
+        mt = fmaxf(mt, o2);
+      }
     }
     mq = ck::clamp_finite(mq);
     mu = ck::clamp_finite(mu);
+    if constexpr (STATS) {
+      // a'_s = 2^ca exp(t_s - M_s) for the pair sum of step s (none above the last step), then u = t + beta as before
+      if (s + 1 < T && live) {
+        const float nma = exp_offset(ck::clamp_finite(mt), ca);
+        float* dst = a.pair_a + (static_cast<int64_t>(b) * a.D + a.var[s]) * K + 4 * kh;
+#pragma unroll
+        for (int j = 0; j < NOB; ++j)
+          if (j < nob) {
+            float p[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) p[i] = dead ? 0.f : __builtin_amdgcn_exp2f(fmaf(t[j][i], kL2E, nma));
+            keep_store(dst + 32 * (wave + nwaves * j), p);
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < NOB; ++j)
+        if (j < nob) {
+#pragma unroll
+          for (int i = 0; i < 16; ++i) t[j][i] += be[j][i];
+        }
+    }
     // g = exp(u - Mu) and the wave's share of its row sum; p = 2^96 exp(q - Mq) into the shared tile
     const float nmu = exp_offset(mu, 0.f);
     float z = 0.f;
@@ -411,9 +459,27 @@ __global__ void __launch_bounds__(256) hmm_backward_kernel(const HmmArgs a) {
       for (int j = 0; j < NOB; ++j)
         if (j < nob) {
 #pragma unroll
-          for (int i = 0; i < 16; ++i) t[j][i] *= inv;
+          for (int i = 0; i < 16; ++i) t[j][i] = STATS && dead ? 0.f : t[j][i] * inv;
           keep_store(dst + 32 * (wave + nwaves * j), t[j]);
         }
+    }
+    if constexpr (STATS) {
+      // r'_s = 2^h exp(q_s - Mq_s) for the pair sum of step s - 1; the rest of c_s = 2^lc travels with a'_{s-1}
+      const float lc = (mq - mu) * kL2E - __builtin_amdgcn_logf(z);
+      const float h = floorf(0.5f * lc);
+      ca = lc - h;
+      if (!first && live) {
+        const float nmr = exp_offset(mq, h);
+        float* dst = a.pair_r + (static_cast<int64_t>(b) * a.D + a.var[s]) * K + 4 * kh;
+#pragma unroll
+        for (int j = 0; j < NOB; ++j)
+          if (j < nob) {
+            float p[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) p[i] = dead ? 0.f : __builtin_amdgcn_exp2f(fmaf(e[j][i], kL2E, nmr));
+            keep_store(dst + 32 * (wave + nwaves * j), p);
+          }
+      }
     }
     if (first) break;
 
@@ -456,27 +522,30 @@ __global__ void __launch_bounds__(256) hmm_backward_kernel(const HmmArgs a) {
   }
 }
 
-enum class HmmPass { kForward, kForwardKeep, kBackward };
+enum class HmmPass { kForward, kForwardKeep, kBackward, kBackwardStats };
 template <int NOB>
 int hmm_launch_pass(HmmPass pass, const HmmArgs& a, void* stream) {
   constexpr int NBUF = NOB > 4 ? 3 : 8;
   switch (pass) {
     case HmmPass::kForward: return hmm_launch(hmm_forward_kernel<NOB>, NBUF, kHmmWaves * 32, a, stream);
     case HmmPass::kForwardKeep: return hmm_launch(hmm_forward_kernel<NOB, true>, NBUF, kHmmWaves * 32, a, stream);
-    default: return hmm_launch(hmm_backward_kernel<NOB>, NBUF, 3 * kHmmWaves * 32, a, stream);
+    case HmmPass::kBackward: return hmm_launch(hmm_backward_kernel<NOB>, NBUF, 3 * kHmmWaves * 32, a, stream);
+    default: return hmm_launch(hmm_backward_kernel<NOB, true>, NBUF, 4 * kHmmWaves * 32, a, stream);
   }
 }
 
 int hmm_run(const char* name, HmmPass pass, const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T,
             int K, const float* rows, const int64_t* x, int D, int C, const int32_t* integrate, int B, float* out, float* keep,
-            void* stream) {
+            void* stream, float* pair_a = nullptr, float* pair_r = nullptr) {
   CK_REQUIRE(w_steps && step_fold && step_var && rows && out, "%s: null operand", name);
   CK_REQUIRE(T >= 1 && B >= 1, "%s: T = %d, B = %d", name, T, B);
   CK_REQUIRE(K >= 32 && K <= 1024 && K % 32 == 0, "%s: K = %d is not a multiple of 32 in 32 .. 1024", name, K);
   CK_REQUIRE(x == nullptr || (C >= 1 && D >= 1), "%s: a table source needs C >= 1 and D >= 1", name);
   CK_REQUIRE(x != nullptr || integrate == nullptr, "%s: a block source has its missing entries in the block", name);
   CK_REQUIRE(pass == HmmPass::kForward || (keep != nullptr && D >= T), "%s: needs the (B, D, K) hand-off buffer and D >= T", name);
-  const HmmArgs a{reinterpret_cast<const float* const*>(w_steps), step_fold, step_var, rows, x, integrate, out, C, D, T, B, K, keep};
+  CK_REQUIRE(pass != HmmPass::kBackwardStats || (pair_a != nullptr && pair_r != nullptr), "%s: needs both operand buffers", name);
+  const HmmArgs a{reinterpret_cast<const float* const*>(w_steps), step_fold, step_var, rows, x, integrate, out, C, D, T, B, K, keep,
+                  pair_a, pair_r};
   const int NQ = K / 32, waves = NQ < kHmmWaves ? NQ : kHmmWaves;
   switch ((NQ + waves - 1) / waves) {
     case 1: return hmm_launch_pass<1>(pass, a, stream);
@@ -513,3 +582,9 @@ extern "C" int ck_hmm_backward(const void* const* w_steps, const int32_t* step_f
                  const_cast<float*>(log_prob), keep, stream);
 }
 
+extern "C" int ck_hmm_backward_stats(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K,
+                                     const float* rows, const int64_t* x, int D, int C, const int32_t* integrate, int B,
+                                     const float* log_prob, float* keep, float* pair_a, float* pair_r, void* stream) {
+  return hmm_run("ck_hmm_backward_stats", HmmPass::kBackwardStats, w_steps, step_fold, step_var, T, K, rows, x, D, C, integrate, B,
+                 const_cast<float*>(log_prob), keep, stream, pair_a, pair_r);
+}

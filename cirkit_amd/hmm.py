@@ -20,9 +20,16 @@ transposed and turns that buffer into posteriors in place -- two launches where 
 pass on the vector ALU that keeps the same hand-off (`ck_hmm_viterbi_forward`) and a walk back over it, one wave a row
 (`ck_hmm_viterbi_backtrack`; cirkit_amd/csrc/ck_hmm_viterbi.hip) -- two launches again.
 
-Out of scope: Baum-Welch / pairwise expected statistics, sampling of paths and k-best paths; homogeneous chains (the
-kernel's table of weight pointers already allows shared transitions); bf16-piece variants; training beyond what `HipTrainer` does
-with a chain plan layer by layer; routing `HipCircuit.forward` or `HipCircuit.mpe` to these kernels.
+`HipHMM.expected_statistics` is the Baum-Welch E-step, the `ExpectedStatistics` of `HipCircuit.expected_statistics` for a chain
+with a Categorical input layer: the keeping forward, a variant of the backward pass that also leaves the two operand rows of every
+pairwise posterior (`ck_hmm_backward_stats`), their product reduced over the rows of the batch on the matrix pipe
+(`ck_hmm_pair_sum`) and the emission histogram (`ck_hmm_leaf_sum`; both cirkit_amd/csrc/ck_hmm_stats.hip) -- four launches per chunk
+of rows where the layer-wise path takes several per layer.  `HipEMTrainer.apply` turns the result into an M-step.
+
+Out of scope: an M-step of `HipHMM`'s own; expected statistics of inputs other than Categorical; sampling of paths and k-best
+paths; homogeneous chains (the kernel's table of weight pointers already allows shared transitions; their statistics would be
+summed over the steps); bf16-piece variants; training beyond what `HipTrainer` and `HipEMTrainer` do with a chain plan layer by
+layer; routing `HipCircuit.forward` or `HipCircuit.mpe` to these kernels.
 """
 
 from __future__ import annotations
@@ -34,6 +41,7 @@ import numpy as np
 import torch
 
 from . import _capi as capi
+from .expected import ExpectedStatistics
 from .plan import Plan, resolve_fold_index
 
 _INPUTS = ("categorical", "binomial", "gaussian")
@@ -144,7 +152,7 @@ class HipHMM:
         self.input_layer = next(i for i, l in enumerate(self.plan.layers) if l.inputs is None)
         self.K = self.plan.layers[self.input_layer].num_output_units
         self.categorical = self.plan.layers[self.input_layer].type == "categorical"
-        self.last_launches = 0  # launches of the last call of `log_prob`, `state_posteriors` or `viterbi`
+        self.last_launches = 0  # launches of the last call of `log_prob`, `state_posteriors`, `viterbi` or `expected_statistics`
         self._key = None
         self._tab: dict | None = None
 
@@ -224,6 +232,83 @@ class HipHMM:
         not depend on `rows_per_chunk`."""
         out, _, states = self._chain(x, integrate_vars, rows_per_chunk, "viterbi")
         return states, out
+
+    def expected_statistics(self, x: torch.Tensor, integrate_vars=None, *, rows_per_chunk: int | None = None) -> ExpectedStatistics:
+        """The Baum-Welch E-step: the expected sufficient statistics of every parameter under ``p(z | evidence)``, summed over the
+        LIVE rows of the batch (evidence in range, finite ``log p``; a dead row contributes exactly nothing) -- the
+        `ExpectedStatistics` of `HipCircuit.expected_statistics`, in the user plan's shapes and indexed by its layer index, so that
+        `HipEMTrainer.apply` takes it.  ``edge[j]`` ``(1, Ko, K)`` of step ``s``'s layer: ``sum_b p(z_s = i, z_{s+1} = o | evidence of
+        b)`` in entry ``[o, i]`` (the last step: ``Ko = 1``, ``sum_b gamma_{T-1}[b, i]``).  ``leaf[input layer]`` ``(F, K, C)``: fold
+        ``f`` of step ``s`` gets ``gamma_s[b, k]`` in entry ``[k, x[b, var_s]]``; a live row that misses the variable (-1, or
+        `integrate_vars`) spreads it over the layer's own ``p(c | k)``.  ``unit[j]`` the edge sums over the entries (step layers) or
+        over the outputs (input folds), ``log_evidence`` ``(B,)`` what `log_prob` returns, ``rows`` the number of live rows.
+        Categorical input layers only: any other raises ``NotImplementedError`` naming the layer before anything is allocated or
+        launched.  Nothing is written into the parameter store.  Four launches per chunk of `rows_per_chunk` rows
+        (`ck_hmm_forward_keep`, `ck_hmm_backward_stats`, `ck_hmm_pair_sum`, `ck_hmm_leaf_sum`) whatever ``T``, ``B`` and ``K``; by
+        default a chunk holds each of its three ``(rows, D, K)`` buffers at or below 1 GiB.  Chunks add to the same sums in call
+        order and no sum uses float atomics: the same `x` and `rows_per_chunk` give the same bits; different `rows_per_chunk`
+        agree to rounding."""
+        src = self.hc.user_plan.layers[self.input_layer]
+        if not self.categorical:
+            raise NotImplementedError(f"HipHMM.expected_statistics: layer {self.input_layer} ({src.type}) is not a Categorical "
+                                      "input layer")
+        D, T, K = self.plan.num_variables, len(self.steps), self.K
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
+        if rows_per_chunk is not None and int(rows_per_chunk) <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+        B = int(x.shape[0])
+        if B <= 0:
+            raise ValueError("empty batch")
+        tab = self.tables()
+        user = self.hc.user_plan.layers
+        C, F = self.plan.layers[self.input_layer].config["num_categories"], int(tab["rows"].shape[0])
+        n = min(B, int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // (D * K * 4)))
+        self.last_launches = 0
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            mask = self._mask(integrate_vars)
+            x = x.to(self.device).to(torch.int64).contiguous()
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)  # noqa: E731
+            out, gamma, pa, pr = new(B), new(n, D, K), new(n, D, K), new(n, D, K)
+            edge = torch.zeros((T - 1) * K * K + K, dtype=torch.float32, device=self.device)
+            leaf = torch.zeros((F, K, C), dtype=torch.float32, device=self.device)
+            units = max(capi.load().ck_hmm_stats_scratch(T, K, C, nb) for nb in {n, B % n or n})
+            capi.check(min(units, 0), "ck_hmm_stats_scratch")
+            scratch = new(units * 1024) if units else None
+            sp, sn = (None, 0) if scratch is None else (scratch.data_ptr(), scratch.numel())
+            head = (tab["w"].data_ptr(), tab["fold"].data_ptr(), tab["var"].data_ptr(), T, K)
+            mp = None if mask is None else mask.data_ptr()
+            for r0 in range(0, B, n):
+                nb = min(n, B - r0)
+                source = (tab["rows"].data_ptr(), x[r0:].data_ptr(), D, C, mp, nb, out[r0:].data_ptr(), gamma.data_ptr())
+                capi.call("ck_hmm_forward_keep", *head, *source, stream)
+                capi.call("ck_hmm_backward_stats", *head, *source, pa.data_ptr(), pr.data_ptr(), stream)
+                capi.call("ck_hmm_pair_sum", tab["w"].data_ptr(), tab["var"].data_ptr(), T, K, D, nb, pa.data_ptr(), pr.data_ptr(),
+                          gamma.data_ptr(), edge.data_ptr(), sp, sn, stream)
+                capi.call("ck_hmm_leaf_sum", tab["fold"].data_ptr(), tab["var"].data_ptr(), T, K, tab["rows"].data_ptr(),
+                          x[r0:].data_ptr(), D, C, mp, nb, gamma.data_ptr(), leaf.data_ptr(), sp, sn, stream)
+                self.last_launches += 4
+            # back to the user plan's shapes (a padded unit carries no flow, a padded entry has weight 0)
+            ku = self.num_states
+            res = ExpectedStatistics({}, {}, [None] * len(user), out, torch.isfinite(out).sum(), kinds=[l.type for l in user])
+            inner = edge[:(T - 1) * K * K].view(T - 1, K, K)[:, :ku, :ku]
+            last = edge[-K:].view(1, K)[:, :ku]
+            by_out, by_in = torch.cat([inner.sum(-1), last.sum(-1, keepdim=True).expand(1, ku)]), torch.cat([inner.sum(-2), last])
+            into = torch.zeros((F, ku), dtype=torch.float32, device=self.device)  # flow into each input fold
+            into.index_copy_(0, tab["fold"].long(), by_in)
+            folds = [l.num_folds for l in self.plan.layers]
+            for s, (st, w) in enumerate(zip(self.steps, tab["keep"])):
+                ko = user[st.layer].num_output_units
+                e = inner[s:s + 1] if s + 1 < T else last[None]
+                res.edge[st.layer], res.support[st.layer] = e, w[:, :ko, :ku] > 0
+                res.unit[st.layer] = by_out[s:s + 1, :ko]
+                if s and user[st.layer].type == "sum":  # (unfused: the Hadamard layer below passes the same flow on)
+                    res.unit[int(resolve_fold_index(self.plan.layers[st.layer].inputs, folds)[0][0][0])] = by_in[s:s + 1]
+            res.unit[self.input_layer] = into
+            res.leaf[self.input_layer] = leaf[:, :ku]
+            res.support[self.input_layer] = (tab["rows"][:, :C, :ku] > -float("inf")).transpose(1, 2)
+        return res
 
     def _chain(self, x: torch.Tensor, integrate_vars, rows_per_chunk: int | None, query: str):
         """``(log_prob, None, None)`` by the forward launch; ``(log_prob, (B, D, K) posteriors, None)`` by the keeping forward

@@ -1848,6 +1848,34 @@ int ck_hmm_viterbi_forward(const void* const* w_steps, const int32_t* step_fold,
 int ck_hmm_viterbi_backtrack(const void* const* w_steps, const int32_t* step_var, int T, int K, int num_states, int D, int B,
                              const float* score, const float* keep, int64_t* states, void* stream);
 
+/* The Baum-Welch E-step of the same chain ("Expected statistics (Baum-Welch E-step)"; additive, ABI 51):
+ * after ck_hmm_forward_keep, FOUR calls per chunk of rows whatever T, B and K.
+ * ck_hmm_backward_stats is ck_hmm_backward's kernel instantiated to leave, besides gamma in `keep`, the operand rows of the pair
+ * sum in pair_a and pair_r, two more (B, D, K) fp32 buffers indexed like `keep`: with M_s the forward's row maximum of t_s,
+ * q_s = e_s + beta_s, Mq_s / Mu_s the row maxima of q_s / t_s + beta_s, z_s the row sum behind gamma_s and
+ * 2^lc = exp(Mq_s - Mu_s) / z_s, h = floor(lc / 2):
+ *     pair_r[b, step_var[s], :]     = 2^h exp(q_s - Mq_s)                   (s >= 1)
+ *     pair_a[b, step_var[s - 1], :] = 2^(lc - h) exp(t_{s-1} - M_{s-1})     (s >= 1)
+ * so that sum_{o,i} pair_r[b, var_{s+1}, o] W_s[o, i] pair_a[b, var_s, i] = 1 for a live row.  A row whose log_prob is not finite
+ * is ZEROS in keep, pair_a and pair_r.  Entries that no step names are left alone.
+ * ck_hmm_pair_sum ADDS to edge, (T - 1) K^2 + K fp32 accumulators: for s <= T - 2
+ *     edge[s K^2 + o K + i] += W_s[o, i] sum_b pair_r[b, var_{s+1}, o] pair_a[b, var_s, i]       (v_mfma_f32_32x32x2_f32, exact fp32)
+ * and edge[(T - 1) K^2 + i] += sum_b gamma[b, var_{T-1}, i].  ck_hmm_leaf_sum ADDS to leaf, (F, K, C) fp32 accumulators: entry
+ * [step_fold[s], k, c] gains gamma[b, var_s, k] from every row with x[b, var_s] = c, and gamma[b, var_s, k] exp(table[fold, c, k])
+ * from every row that misses the variable (a negative entry, or integrate[var_s] != 0); an entry >= C gains nothing.  Both split
+ * the rows into slices (a function of the shapes alone) and add the slices in index order, through `scratch` -- at least 1024 x
+ * ck_hmm_stats_scratch(T, K, C, B) floats; 0: no slices, scratch may be NULL -- and a second kernel of the same call: no float
+ * atomics, results are bit-identical from call to call.  ck_hmm_stats_scratch returns -1 for shapes it refuses. */
+int ck_hmm_backward_stats(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, const float* rows,
+                          const int64_t* x, int D, int C, const int32_t* integrate, int B, const float* log_prob, float* keep,
+                          float* pair_a, float* pair_r, void* stream);
+int ck_hmm_stats_scratch(int T, int K, int C, int B);
+int ck_hmm_pair_sum(const void* const* w_steps, const int32_t* step_var, int T, int K, int D, int B, const float* pair_a,
+                    const float* pair_r, const float* gamma, float* edge, float* scratch, int64_t scratch_floats, void* stream);
+int ck_hmm_leaf_sum(const int32_t* step_fold, const int32_t* step_var, int T, int K, const float* table, const int64_t* x, int D, int C,
+                    const int32_t* integrate, int B, const float* gamma, float* leaf, float* scratch, int64_t scratch_floats,
+                    void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
