@@ -26,7 +26,13 @@ pairwise posterior (`ck_hmm_backward_stats`), their product reduced over the row
 (`ck_hmm_pair_sum`) and the emission histogram (`ck_hmm_leaf_sum`; both cirkit_amd/csrc/ck_hmm_stats.hip) -- four launches per chunk
 of rows where the layer-wise path takes several per layer.  `HipEMTrainer.apply` turns the result into an M-step.
 
-Out of scope: an M-step of `HipHMM`'s own; expected statistics of inputs other than Categorical; sampling of paths and k-best
+`HipHMM.sample_posterior` draws state paths from ``p(z | evidence)`` and completes the missing entries of each row from the
+emissions of the drawn states -- forward-filter-backward-sample: the keeping forward and a walk back that draws where Viterbi's
+takes a maximum, a (row, sample) pair to a group of lanes sized to K (`ck_hmm_sample_paths`; cirkit_amd/csrc/ck_hmm_sample.hip) --
+two launches per chunk of rows whatever T, B, K and the number of samples.  `HipHMM.sample` is the same walk on one row without
+evidence.
+
+Out of scope: an M-step of `HipHMM`'s own; expected statistics and sampling of inputs other than Categorical; k-best
 paths; homogeneous chains (the kernel's table of weight pointers already allows shared transitions; their statistics would be
 summed over the steps); bf16-piece variants; training beyond what `HipTrainer` and `HipEMTrainer` do with a chain plan layer by
 layer; routing `HipCircuit.forward` or `HipCircuit.mpe` to these kernels.
@@ -152,7 +158,7 @@ class HipHMM:
         self.input_layer = next(i for i, l in enumerate(self.plan.layers) if l.inputs is None)
         self.K = self.plan.layers[self.input_layer].num_output_units
         self.categorical = self.plan.layers[self.input_layer].type == "categorical"
-        self.last_launches = 0  # launches of the last call of `log_prob`, `state_posteriors`, `viterbi` or `expected_statistics`
+        self.last_launches = 0  # launches of the last call of a query
         self._key = None
         self._tab: dict | None = None
 
@@ -309,6 +315,93 @@ class HipHMM:
             res.leaf[self.input_layer] = leaf[:, :ku]
             res.support[self.input_layer] = (tab["rows"][:, :C, :ku] > -float("inf")).transpose(1, 2)
         return res
+
+    def _need_categorical(self, query: str) -> None:
+        if not self.categorical:
+            src = self.hc.user_plan.layers[self.input_layer]
+            raise NotImplementedError(f"HipHMM.{query}: layer {self.input_layer} ({src.type}) is not a Categorical input layer")
+
+    def _emission_cdf(self, tab: dict, stream) -> int:
+        """Leaves the ``(F, K, C)`` table of `sample_posterior` in ``tab["cdf"]``; the number of launches that took."""
+        if "cdf" in tab:
+            return 0
+        rows = tab["rows"]
+        F, C = int(rows.shape[0]), int(rows.shape[1]) - 1
+        cdf = torch.empty((F, self.K, C), dtype=torch.float32, device=self.device)
+        capi.call("ck_hmm_emission_cdf", rows.data_ptr(), F, self.K, C, cdf.data_ptr(), stream)
+        tab["cdf"] = cdf
+        return 1
+
+    def sample_posterior(self, x: torch.Tensor, integrate_vars=None, *, num_samples: int = 1, seed: int = 0,
+                         rows_per_chunk: int | None = None, return_log_prob: bool = False):
+        """``(states, completed)``, both ``(B, S, D)`` int64 with ``S = num_samples``: `S` state paths per row drawn from
+        ``p(z | evidence of the row)``, and the row completed along each.  ``states[b, j, var_s]`` is the state of step ``s`` in
+        sample ``j`` of row ``b``, the unit index of `viterbi` and `state_posteriors`, always ``< num_states``; -1 for a variable
+        that no step reads.  ``completed[b, j, v]`` is ``x[b, v]`` where that entry is observed and, where it is missing (-1, or
+        `integrate_vars`), a draw from the emission ``p(c | z_s)`` of its step's fold given the sampled state.  With
+        `return_log_prob` also the ``(B,)`` log-likelihood of the same forward pass.  `x` and `integrate_vars` as for `log_prob`.
+        A row whose `log_prob` is -inf or NaN (no mass; a category outside the layer's range) has -1 in every state and at every
+        missing entry; its observed entries are still copied.
+
+        Forward-filter-backward-sample in two launches per chunk of `rows_per_chunk` rows (`ck_hmm_forward_keep`,
+        `ck_hmm_sample_paths`) whatever ``T``, ``B``, ``K`` and ``S``; by default a chunk keeps the ``(rows, D, K)`` hand-off, which
+        is scratch, at or below 1 GiB.  The first call after the parameters changed takes one launch more
+        (`ck_hmm_emission_cdf`): the ``(F, K, C)`` fp32 table of cumulative emission probabilities, a contiguous row per (fold,
+        state), kept with the other tables until the parameters change -- 67 MB at ``T, K, C = 256, 256, 256`` and at ``64, 1024,
+        256``; the other queries never build it.  Draws follow the samplers' contract ("Sampling paths"):
+        Philox4x32-10 keyed by `seed`, counter ``(b S + j, s, 0, 0)`` with ``b`` the row's index in `x`, one call per (sample,
+        step), word 0 for the state and word 1 for the emission -- a sample depends on ``(seed, b, j)`` only, not on
+        `rows_per_chunk` or on the other rows of the batch.  Categorical input layers only: any other raises
+        ``NotImplementedError`` naming the layer before anything is allocated or launched.  Nothing is written into the
+        parameter store."""
+        self._need_categorical("sample_posterior")
+        D, T, K = self.plan.num_variables, len(self.steps), self.K
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
+        if rows_per_chunk is not None and int(rows_per_chunk) <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+        B, S = int(x.shape[0]), int(num_samples)
+        if B <= 0:
+            raise ValueError("empty batch")
+        if S <= 0:
+            raise ValueError("num_samples must be positive")
+        if B * S >= 2**32:
+            raise ValueError(f"B * num_samples = {B * S} does not fit the 32-bit sample index of the draw's counter")
+        tab = self.tables()
+        C = self.plan.layers[self.input_layer].config["num_categories"]
+        n = min(B, int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // (D * K * 4)))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self.last_launches = self._emission_cdf(tab, stream)
+            mask = self._mask(integrate_vars)
+            mp = None if mask is None else mask.data_ptr()
+            x = x.to(self.device).to(torch.int64).contiguous()
+            out = torch.empty(B, dtype=torch.float32, device=self.device)
+            keep = torch.empty((n, D, K), dtype=torch.float32, device=self.device)
+            if D == T:
+                states, completed = (torch.empty((B, S, D), dtype=torch.int64, device=self.device) for _ in range(2))
+            else:  # (a variable that no step reads: no state, and its entry as it came)
+                states = torch.full((B, S, D), -1, dtype=torch.int64, device=self.device)
+                completed = x[:, None, :].expand(B, S, D).contiguous()
+            head = (tab["w"].data_ptr(), tab["fold"].data_ptr(), tab["var"].data_ptr(), T, K)
+            for r0 in range(0, B, n):
+                nb = min(n, B - r0)
+                capi.call("ck_hmm_forward_keep", *head, tab["rows"].data_ptr(), x[r0:].data_ptr(), D, C, mp, nb, out[r0:].data_ptr(),
+                          keep.data_ptr(), stream)
+                capi.call("ck_hmm_sample_paths", *head, self.num_states, tab["cdf"].data_ptr(), x[r0:].data_ptr(), D, C, mp, nb, S, r0,
+                          int(seed) & (2**64 - 1), out[r0:].data_ptr(), keep.data_ptr(), states[r0:].data_ptr(),
+                          completed[r0:].data_ptr(), stream)
+                self.last_launches += 2
+        return (states, completed, out) if return_log_prob else (states, completed)
+
+    def sample(self, num_samples: int, *, seed: int = 0):
+        """``(x, states)``, both ``(N, D)`` int64: `N` sequences from the model with the state paths that emitted them --
+        `sample_posterior` of ONE row without evidence with ``num_samples = N``: the forward runs for one row, and the samples
+        of that row carry the parallelism of the walk back."""
+        self._need_categorical("sample")
+        x = torch.full((1, self.plan.num_variables), -1, dtype=torch.int64, device=self.device)
+        states, completed = self.sample_posterior(x, num_samples=num_samples, seed=seed)
+        return completed[0], states[0]
 
     def _chain(self, x: torch.Tensor, integrate_vars, rows_per_chunk: int | None, query: str):
         """``(log_prob, None, None)`` by the forward launch; ``(log_prob, (B, D, K) posteriors, None)`` by the keeping forward

@@ -1876,6 +1876,28 @@ int ck_hmm_leaf_sum(const int32_t* step_fold, const int32_t* step_var, int T, in
                     const int32_t* integrate, int B, const float* gamma, float* leaf, float* scratch, int64_t scratch_floats,
                     void* stream);
 
+/* Posterior path sampling of the same chain ("Sampling paths"; additive, ABI 51): after
+ * ck_hmm_forward_keep, ONE call per chunk of rows whatever T, B, K and S.
+ * ck_hmm_emission_cdf: cdf (F, K, C) fp32 receives the inclusive sums over c of exp(table[f, c, k]) of the Categorical layer's
+ * (F, C + 1, K) table of logarithms (the last row, the integral, is not read): one contiguous row per (fold, state).  Once per
+ * parameter state.
+ * ck_hmm_sample_paths draws S paths per row from p(z | evidence of the row), from step T - 1 down:
+ *     p(z_s = i | z_{s+1} = o) ~ exp(t_s[i]) W_s[o, i]        (o = 0 above the last step; t_s = keep[b, step_var[s], :])
+ * over i < num_states only (1 <= num_states <= K).  Sample j of row b is n = b S + j of this call; states and completed are
+ * (B, S, D) int64: states[n, step_var[s]] receives z_s, completed[n, step_var[s]] the entry x[b, step_var[s]] where it is
+ * observed and a draw from the emission p(c | z_s) of fold step_fold[s] (row [fold, z_s, :] of cdf) where it is missing (negative,
+ * or integrate[var] != 0).  Entries that no step names are left alone.  Draws: Philox4x32-10 (ck_philox.h), key the two halves of
+ * `seed`, counter ((row0 + b) S + j, s, 0, 0) -- row0 the index of this call's row 0 in the whole batch, (row0 + B) S <= 2^32 --
+ * ONE call per (sample, step): with u = (x >> 8) 2^-24, word x0 draws the state and word x1 the emission, each as the smallest index
+ * whose inclusive cumulative sum exceeds u times the total, or the last index with mass if rounding leaves none.  A row whose
+ * log_prob is not > -inf (no mass, or NaN) gets -1 in every state and at every missing entry; its observed entries are copied.
+ * A (row, sample) is served by a group of 8 (K = 32), 16 (64), 32 (up to 128) or 64 lanes (ck_hmm_sample.hip); a sample does not
+ * depend on B, S, row0's chunking or its place in the batch beyond its counter. */
+int ck_hmm_emission_cdf(const float* table, int F, int K, int C, float* cdf, void* stream);
+int ck_hmm_sample_paths(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, int num_states,
+                        const float* cdf, const int64_t* x, int D, int C, const int32_t* integrate, int B, int S, int64_t row0,
+                        uint64_t seed, const float* log_prob, const float* keep, int64_t* states, int64_t* completed, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
