@@ -395,6 +395,8 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_hmm_stats_scratch": [_i, _i, _i, _i],
     "ck_hmm_pair_sum": [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _l, _p],
     "ck_hmm_leaf_sum": [_p, _p, _i, _i, _p, _p, _i, _i, _p, _i, _p, _p, _p, _l, _p],
+    "ck_hmm_scan_segments": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p],
+    "ck_hmm_scan_combine": [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p],
     "ck_hmm_emission_cdf": [_p, _i, _i, _i, _p, _p],
     "ck_hmm_sample_paths": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _i, _l, C.c_uint64, _p, _p, _p, _p, _p],
     "ck_em_job_blocks": [_i, _l, _i],

@@ -12,6 +12,12 @@ Any other input layer (Binomial, Gaussian) is evaluated by its own launch into a
 time.  Missing entries -- a variable in `integrate_vars`, or per entry ``x[b, v] == -1`` (NaN for Gaussian inputs): what padding
 sequences of different lengths needs -- are summed out.
 
+`HipHMM.log_prob(segments=P)` is the same value for SMALL batches, parallel in time: the one launch costs a single row what it
+costs 4096, so the steps are cut into `P` segments, `ck_hmm_scan_segments` evaluates the ``K x K`` log transfer matrix of every
+segment of every row at once (virtual rows started from one-hot vectors) and `ck_hmm_scan_combine` chains them in the log domain
+(cirkit_amd/csrc/ck_hmm_scan.hip) -- two launches per chunk of rows, Categorical inputs, up to 512 units; ``segments="auto"`` takes
+it where it measured faster (`HipHMM.auto_segments`).
+
 `HipHMM.state_posteriors` is forward-backward smoothing, ``p(z_v = k | evidence)`` for every position: the forward launch
 instantiated to leave its hand-off in the ``(B, D, K)`` result, and `ck_hmm_backward`, which walks the chain back with the weights
 transposed and turns that buffer into posteriors in place -- two launches where `log_prob` takes one.
@@ -205,12 +211,97 @@ class HipHMM:
         """Rows of a chunk by default for inputs other than Categorical: the block of emissions at or below 1 GiB."""
         return max(1, _CHUNK_BYTES // (len(self.steps) * self.K * 4))
 
-    def log_prob(self, x: torch.Tensor, integrate_vars=None, *, rows_per_chunk: int | None = None) -> torch.Tensor:
+    def log_prob(self, x: torch.Tensor, integrate_vars=None, *, rows_per_chunk: int | None = None,
+                 segments: int | str | None = None) -> torch.Tensor:
         """``(B,)`` fp32: ``log p(x)`` with the variables of `integrate_vars` (ids, or a ``(D,)`` bool mask), and every entry
         ``x[b, v] == -1`` (NaN for Gaussian inputs), summed out.  `x`: ``(B, T)``, int64 for discrete inputs, fp32 for Gaussian
         ones.  A category outside its layer's range makes the row NaN (inputs other than Categorical: the batch, with
-        `HipCircuit.check_inputs` of the owned circuit raising).  A row's value does not depend on `rows_per_chunk`."""
-        return self._chain(x, integrate_vars, rows_per_chunk, "log_prob")[0]
+        `HipCircuit.check_inputs` of the owned circuit raising).  A row's value does not depend on `rows_per_chunk`.
+
+        `segments` = ``P``, an int with ``2 <= P <= T``, takes the time-parallel path for small batches (DESIGN.md section 11,
+        "Time-parallel forward"): the steps are cut at ``floor(p T / P)``, `ck_hmm_scan_segments` evaluates the ``K x K`` log
+        transfer matrix of every segment of every row at the same time and `ck_hmm_scan_combine` chains them -- two launches per
+        chunk of `rows_per_chunk` rows whatever ``T``, ``K``, ``B`` and ``P``, ``K`` times the arithmetic of the sequential walk
+        on a dependent chain of about ``T / P + P`` steps instead of ``T``.  Same semantics (missing entries summed out, a row
+        without mass -inf and never NaN, a category >= C NaN); a row's value depends on ``P`` to rounding only, not on
+        `rows_per_chunk` or on the other rows, and the same ``(x, P)`` gives the same bits.  By default a chunk keeps the
+        scratch -- per row ``(P - 2)`` matrices of ``num_states`` rounded up to 32 by ``K`` floats, two vectors and ``P`` flag
+        words -- at or below 1 GiB.  Any other int, or ``T = 1``, raises ``ValueError``; an input layer other than Categorical, or
+        more than 512 units after padding (the path multiplies the arithmetic by ``K``), raises ``NotImplementedError`` before
+        anything is allocated.  ``segments="auto"`` takes what `auto_segments` picks for the batch."""
+        if segments is None:
+            return self._chain(x, integrate_vars, rows_per_chunk, "log_prob")[0]
+        return self._scan(x, integrate_vars, rows_per_chunk, segments)
+
+    _SCAN_MAX_UNITS = 512
+
+    def auto_segments(self, B: int) -> int | None:
+        """What ``log_prob(segments="auto")`` takes for a batch of `B` rows: ``None`` (the sequential walk) or a number of
+        segments.  Fitted to the table of DESIGN.md section 11, "Time-parallel forward": ``None`` wherever the sequential walk
+        measured faster than the scan or within 10 % of it, and wherever the scan does not apply."""
+        T, K = len(self.steps), self.K
+        if not self.categorical or K > self._SCAN_MAX_UNITS or T < 64:  # (chains shorter than 64 steps: not measured)
+            return None
+        # workgroups of launch 1 that the device holds at once: LDS of one (activation tile, row maxima, weight rings) in the
+        # 160 KiB of a CU.  The scan measured faster than the sequential walk by more than 10 % wherever the (row, tile of start
+        # states) pairs of ONE segment fill at most half of them, and level with it or slower where they fill all.
+        lds = 4 * (32 * K + 128 + min(K // 32, 4) * 8 * 512)
+        held = torch.cuda.get_device_properties(self.device).multi_processor_count * max(1, (160 << 10) // lds)
+        pairs = B * -(-self.num_states // 32)
+        if 2 * pairs > held:
+            return None
+        # sqrt(T) segments balance the two chains where a boundary of launch 2 costs about a step (K = 32) and all segments run at
+        # once; half as many where a boundary costs more than a step (K >= 256) or the segments queue for the device
+        full = max(2, round(T ** 0.5))
+        return full if K < 256 and pairs * (full - 1) <= held else max(2, round(T ** 0.5 / 2))
+
+    def _scan(self, x: torch.Tensor, integrate_vars, rows_per_chunk: int | None, segments) -> torch.Tensor:
+        """`log_prob` by the time-parallel path: per chunk of rows `ck_hmm_scan_segments` and `ck_hmm_scan_combine`."""
+        D, T, K = self.plan.num_variables, len(self.steps), self.K
+        auto = isinstance(segments, str) and segments == "auto"
+        if auto and self.auto_segments(1) is None:  # (no batch is small enough, or the path does not apply)
+            return self._chain(x, integrate_vars, rows_per_chunk, "log_prob")[0]
+        self._need_categorical("log_prob(segments=)")
+        if K > self._SCAN_MAX_UNITS:
+            raise NotImplementedError(f"HipHMM.log_prob(segments=): {K} units after padding, the time-parallel path serves up to "
+                                      f"{self._SCAN_MAX_UNITS}")
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
+        if rows_per_chunk is not None and int(rows_per_chunk) <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+        B = int(x.shape[0])
+        if B <= 0:
+            raise ValueError("empty batch")
+        if auto:
+            segments = self.auto_segments(B)
+            if segments is None:
+                return self._chain(x, integrate_vars, None, "log_prob")[0]
+        if isinstance(segments, bool) or not isinstance(segments, (int, np.integer)) or not 2 <= int(segments) <= T:
+            raise ValueError(f"segments must be None, 'auto' or an int in 2 .. T = {T}, found {segments!r}")
+        P = int(segments)
+        tab = self.tables()
+        C = self.plan.layers[self.input_layer].config["num_categories"]
+        ns32 = -(-self.num_states // 32) * 32
+        per_row = 4 * ((P - 2) * ns32 * K + 2 * K + P)
+        n = min(B, int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // per_row))
+        self.last_launches = 0
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            mask = self._mask(integrate_vars)
+            mp = None if mask is None else mask.data_ptr()
+            x = x.to(self.device).to(torch.int64).contiguous()
+            out = torch.empty(B, dtype=torch.float32, device=self.device)
+            lg = torch.empty((n, P - 2, ns32, K), dtype=torch.float32, device=self.device) if P > 2 else None
+            first, last = (torch.empty((n, K), dtype=torch.float32, device=self.device) for _ in range(2))
+            flags = torch.empty((n, P), dtype=torch.int32, device=self.device)
+            scratch = (first.data_ptr(), None if lg is None else lg.data_ptr(), last.data_ptr(), flags.data_ptr())
+            for r0 in range(0, B, n):
+                nb = min(n, B - r0)
+                capi.call("ck_hmm_scan_segments", tab["w"].data_ptr(), tab["fold"].data_ptr(), tab["var"].data_ptr(), T, K,
+                          self.num_states, tab["rows"].data_ptr(), x[r0:].data_ptr(), D, C, mp, nb, P, *scratch, stream)
+                capi.call("ck_hmm_scan_combine", T, K, self.num_states, nb, P, *scratch, out[r0:].data_ptr(), stream)
+                self.last_launches += 2
+        return out
 
     def state_posteriors(self, x: torch.Tensor, integrate_vars=None, *, rows_per_chunk: int | None = None,
                          return_log_prob: bool = False):

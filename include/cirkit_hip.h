@@ -1898,6 +1898,26 @@ int ck_hmm_sample_paths(const void* const* w_steps, const int32_t* step_fold, co
                         const float* cdf, const int64_t* x, int D, int C, const int32_t* integrate, int B, int S, int64_t row0,
                         uint64_t seed, const float* log_prob, const float* keep, int64_t* states, int64_t* completed, void* stream);
 
+/* The forward algorithm of the same chain, parallel in TIME, in TWO launches whatever T, K, B and P (DESIGN.md section 11,
+ * "Time-parallel forward"; additive, ABI 51): what ck_hmm_forward computes, to rounding, for small batches.  Operands as for
+ * ck_hmm_forward with a table source (x != NULL); T >= 2, K a multiple of 32 in 32 .. 512, 1 <= num_states <= K the units that are
+ * not padding, 2 <= P <= T.  The steps are cut at s_p = floor(p T / P); segment p is steps [s_p, s_{p+1}).
+ * ck_hmm_scan_segments evaluates every segment in one launch (ck_hmm_scan.hip): segment 0 is the forward on 32 real rows a
+ * workgroup and leaves first[b, :] = v_{s_1 - 1}[b, :]; a workgroup of a segment p >= 1 owns (row b, segment p, 32 start states j)
+ * and walks 32 copies of row b, copy j started from the one-hot vector of j, so that a middle segment leaves the logarithm of its
+ * transfer matrix, lg[b, p - 1, j, o] = log G_p[o, j], and the last one last[b, j] = log of the closing K -> 1 step's result.
+ * first (B, K), lg (B, P - 2, 32 ceil(num_states / 32), K) (may be NULL for P = 2), last (B, K) fp32; start states >= num_states
+ * are neither written nor read.  flags (B, P) int32: every word is written, != 0 where the segment met a category >= C.
+ * ck_hmm_scan_combine chains them, one workgroup a row, in the log domain (the maximum first, clamped finite, then the sum):
+ *     v <- first[b, :];  v'[o] = log sum_{j < num_states} exp(lg[b, p - 1, j, o] + v[j]), p = 1 .. P - 2;
+ *     out[b] = log sum_j exp(last[b, j] + v[j]);  NaN if a flag of the row is set; -inf for a row without mass, never NaN.
+ * A row's result depends on P to rounding only, and not on B or on its place in the batch. */
+int ck_hmm_scan_segments(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, int num_states,
+                         const float* rows, const int64_t* x, int D, int C, const int32_t* integrate, int B, int P, float* first,
+                         float* lg, float* last, int32_t* flags, void* stream);
+int ck_hmm_scan_combine(int T, int K, int num_states, int B, int P, const float* first, const float* lg, const float* last,
+                        const int32_t* flags, float* out, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
