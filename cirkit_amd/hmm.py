@@ -38,7 +38,17 @@ takes a maximum, a (row, sample) pair to a group of lanes sized to K (`ck_hmm_sa
 two launches per chunk of rows whatever T, B, K and the number of samples.  `HipHMM.sample` is the same walk on one row without
 evidence.
 
-Out of scope: an M-step of `HipHMM`'s own; expected statistics and sampling of inputs other than Categorical; k-best
+`HipHMM.autoregressive_log_probs`, `autoregressive_conditionals` and `coding_tables` are the chain-rule decomposition
+``p(x_{o_j} = c | x_{o_0 .. o_{j-1}})`` along `generative_order`: the chain generates from its last step down, so the backward
+recursion is the predictive filter of that order and ONE walk down the chain (`ck_hmm_predict`;
+cirkit_amd/csrc/ck_hmm_predict.hip) gives every position -- one launch, ``O(T)`` steps a row where the owned `HipCircuit` expands
+every row into ``T`` rows of ``T`` layers each.  The conditionals contract the predictive state with a cached linear emission
+table on the matrix pipe (`ck_hmm_emission_table`, once per parameter state); the coding tables pass them through the
+quantiser `HipCircuit.coding_tables` uses.
+
+Out of scope: an M-step of `HipHMM`'s own; expected statistics, sampling and autoregressive conditionals of inputs other than
+Categorical; autoregressive conditionals of a subset of positions, along any order but the generative one, or parallel in
+time; a decoder-side table provider for cirkit_amd/codec.py; k-best
 paths; homogeneous chains (the kernel's table of weight pointers already allows shared transitions; their statistics would be
 summed over the steps); bf16-piece variants; training beyond what `HipTrainer` and `HipEMTrainer` do with a chain plan layer by
 layer; routing `HipCircuit.forward` or `HipCircuit.mpe` to these kernels.
@@ -493,6 +503,126 @@ class HipHMM:
         x = torch.full((1, self.plan.num_variables), -1, dtype=torch.int64, device=self.device)
         states, completed = self.sample_posterior(x, num_samples=num_samples, seed=seed)
         return completed[0], states[0]
+
+    @property
+    def generative_order(self) -> list[int]:
+        """The variables in the order the chain generates them: the plan's last step holds the prior, so position ``j`` is the
+        variable of step ``T - 1 - j`` -- for `templates.hmm(ordering)`, ``ordering`` itself."""
+        return [s.var for s in reversed(self.steps)]
+
+    def _emission_table(self, tab: dict, stream) -> int:
+        """Leaves the ``(F, Cp, K)`` linear emission table of `autoregressive_conditionals` in ``tab["emission"]``; the number of
+        launches that took."""
+        if "emission" in tab:
+            return 0
+        rows = tab["rows"]
+        F, C = int(rows.shape[0]), int(rows.shape[1]) - 1
+        em = torch.empty((F, -(-C // 32) * 32, self.K), dtype=torch.float32, device=self.device)
+        capi.call("ck_hmm_emission_table", rows.data_ptr(), F, self.K, C, em.data_ptr(), stream)
+        tab["emission"] = em
+        return 1
+
+    def _predict_checks(self, x: torch.Tensor, query: str) -> int:
+        self._need_categorical(query)
+        D = self.plan.num_variables
+        if x.dim() != 2 or x.shape[1] != D:
+            raise ValueError(f"expected x of shape (B, {D}), found {tuple(x.shape)}")
+        if int(x.shape[0]) <= 0:
+            raise ValueError("empty batch")
+        return int(x.shape[0])
+
+    def _predict(self, tab: dict, x: torch.Tensor, mask, nb: int, lp: torch.Tensor, cond: torch.Tensor | None, stream) -> None:
+        """One `ck_hmm_predict` launch on the first `nb` rows of `x` (a device tensor, int64, contiguous)."""
+        C = self.plan.layers[self.input_layer].config["num_categories"]
+        capi.call("ck_hmm_predict", tab["w"].data_ptr(), tab["fold"].data_ptr(), tab["var"].data_ptr(), len(self.steps), self.K,
+                  tab["rows"].data_ptr(), x.data_ptr(), self.plan.num_variables, C, None if mask is None else mask.data_ptr(), nb,
+                  lp.data_ptr(), None if cond is None else tab["emission"].data_ptr(), None if cond is None else cond.data_ptr(),
+                  stream)
+
+    def autoregressive_log_probs(self, x: torch.Tensor, integrate_vars=None) -> torch.Tensor:
+        """``(B, T)`` fp32: entry ``[b, j]`` is ``log p(x[b, order[j]] | observed entries of row b among order[:j])`` with ``order =
+        generative_order`` -- the chain-rule decomposition of `log_prob`, whose value a row sums to.  Exactly 0 where the row
+        misses ``order[j]`` (-1, or `integrate_vars`).  Entries of `x` at ``order[j + 1:]`` do not influence position ``j``.  Where
+        only the observed value has no mass the entry is -inf and every later one NaN (the prefix has no mass); a category
+        ``>= C`` makes its own position and every later one NaN; no row affects another.  ONE launch (`ck_hmm_predict`,
+        cirkit_amd/csrc/ck_hmm_predict.hip) whatever ``T``, ``B`` and ``K``: one walk down the chain, ``O(T)`` steps a row where
+        `HipCircuit.autoregressive_log_probs` takes ``O(T^2)``; no forward pass, no ``(B, D, K)`` buffer, no host
+        synchronisation, nothing written into the parameter store.  Categorical input layers only: any other raises
+        ``NotImplementedError`` naming the layer before anything is allocated or launched."""
+        B = self._predict_checks(x, "autoregressive_log_probs")
+        tab = self.tables()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            mask = self._mask(integrate_vars)
+            x = x.to(self.device).to(torch.int64).contiguous()
+            lp = torch.empty((B, len(self.steps)), dtype=torch.float32, device=self.device)
+            self._predict(tab, x, mask, B, lp, None, stream)
+            self.last_launches = 1
+        return lp
+
+    def autoregressive_conditionals(self, x: torch.Tensor, integrate_vars=None, *, return_log_probs: bool = False):
+        """``(B, T, C)`` fp32 linear probabilities, as `HipCircuit.autoregressive_conditionals` returns them: entry ``[b, j, c]``
+        is ``p(X_{order[j]} = c | observed entries of row b among order[:j])`` with ``order = generative_order`` -- also where the
+        row misses ``order[j]``: that is the forecast.  A view of a buffer padded to 32 categories.  With `return_log_probs` also
+        what `autoregressive_log_probs` returns, from the same launch.  Entries of `x` at ``order[j:]`` do not influence position
+        ``j``; after a position whose observed value has no mass, and from a category ``>= C`` on, the row is NaN.  ONE launch
+        (`ck_hmm_predict` with the predictive state contracted against the step's emission matrix on the matrix pipe); the first
+        call after the parameters changed takes one more (`ck_hmm_emission_table`): the ``(F, Cp, K)`` fp32 table of linear
+        emission probabilities, a contiguous row per (fold, category), kept with the other tables until the parameters change.
+        Refusals, synchronisation and the parameter store as for `autoregressive_log_probs`."""
+        B = self._predict_checks(x, "autoregressive_conditionals")
+        tab = self.tables()
+        C = self.plan.layers[self.input_layer].config["num_categories"]
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            launches = self._emission_table(tab, stream)
+            mask = self._mask(integrate_vars)
+            x = x.to(self.device).to(torch.int64).contiguous()
+            lp = torch.empty((B, len(self.steps)), dtype=torch.float32, device=self.device)
+            cond = torch.empty((B, len(self.steps), int(tab["emission"].shape[1])), dtype=torch.float32, device=self.device)
+            self._predict(tab, x, mask, B, lp, cond, stream)
+            self.last_launches = launches + 1
+        return (cond[:, :, :C], lp) if return_log_probs else cond[:, :, :C]
+
+    def coding_tables(self, x: torch.Tensor, integrate_vars=None, *, precision: int = 16,
+                      rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B, T, C + 1)`` int32: the cumulative frequency table at ``2**precision`` of every conditional of
+        `autoregressive_conditionals`, by the quantiser of `HipCircuit.coding_tables` (`ck_ar_quantise`) -- what the encoder of
+        cirkit_amd/codec.py reads.  `precision` is checked as `autoregressive.check_precision` checks it, before anything is
+        allocated or launched.  Two launches per chunk of `rows_per_chunk` rows (by default the chunk's conditionals at or below
+        1 GiB), and the emission table's on the first call; a row's tables do not depend on `rows_per_chunk`."""
+        from .autoregressive import check_precision
+
+        B = self._predict_checks(x, "coding_tables")
+        C, T = self.plan.layers[self.input_layer].config["num_categories"], len(self.steps)
+        precision = check_precision(precision, C)
+        if rows_per_chunk is not None and int(rows_per_chunk) <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+        tab = self.tables()
+        Cp = -(-C // 32) * 32
+        n = min(B, int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // (T * Cp * 4)))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self.last_launches = self._emission_table(tab, stream)
+            mask = self._mask(integrate_vars)
+            x = x.to(self.device).to(torch.int64).contiguous()
+            lp = torch.empty((n, T), dtype=torch.float32, device=self.device)
+            cond = torch.empty((n, T, Cp), dtype=torch.float32, device=self.device)
+            # the quantiser sees Cp states of which the first C are live: the padded ones get no count, and entry C is the total
+            out = torch.empty((B, T, C + 1), dtype=torch.int32, device=self.device)
+            wide = out if Cp == C else torch.empty((n, T, Cp + 1), dtype=torch.int32, device=self.device)
+            rowvar = torch.zeros(n * T, dtype=torch.int32, device=self.device)
+            states = torch.full((1,), C, dtype=torch.int32, device=self.device)
+            for r0 in range(0, B, n):
+                nb = min(n, B - r0)
+                self._predict(tab, x[r0:], mask, nb, lp, cond, stream)
+                dst = out[r0:] if Cp == C else wide
+                capi.call("ck_ar_quantise", cond.data_ptr(), rowvar.data_ptr(), states.data_ptr(), nb * T, Cp, precision,
+                          dst.data_ptr(), stream)
+                if Cp != C:
+                    out[r0:r0 + nb] = wide[:nb, :, :C + 1]
+                self.last_launches += 2
+        return out
 
     def _chain(self, x: torch.Tensor, integrate_vars, rows_per_chunk: int | None, query: str):
         """``(log_prob, None, None)`` by the forward launch; ``(log_prob, (B, D, K) posteriors, None)`` by the keeping forward

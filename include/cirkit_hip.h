@@ -1918,6 +1918,27 @@ int ck_hmm_scan_segments(const void* const* w_steps, const int32_t* step_fold, c
 int ck_hmm_scan_combine(int T, int K, int num_states, int B, int P, const float* first, const float* lg, const float* last,
                         const int32_t* flags, float* out, void* stream);
 
+/* The chain-rule decomposition of the same chain in ONE launch ("Autoregressive conditionals of chains";
+ * additive, ABI 51).  The chain generates from step T - 1 down, so position j of the generative order is step T - 1 - j.  Operands
+ * as for ck_hmm_forward with a table source (x != NULL).  With beta_{T-1}[i] = log W_{T-1}[0, i],
+ * beta_{s-1}[i] = log sum_o W_{s-1}[o, i] exp(e_s[o] + beta_s[o]) (minus a per-row, per-step constant) and q_s = e_s + beta_s:
+ *     log_probs[b, T - 1 - s] = logsumexp(q_s) - logsumexp(beta_s) = log p(x[b, var_s] | observed entries of the steps above s)
+ * exactly 0 where the entry is missing (negative, or integrate[var_s] != 0); -inf where only the observed value has no mass, and
+ * then NaN at every later position; NaN from its own position on for an entry >= C.  log_probs is (B, T) fp32.
+ * cond != NULL: also cond[b, T - 1 - s, c] = sum_k emission[step_fold[s], c, k] exp(beta_s[k]) / sum_k exp(beta_s[k]), the
+ * predictive distribution of the position whether its entry is observed or not, contracted on v_mfma_f32_32x32x2_f32 (exact fp32).
+ * cond is (B, T, Cp) fp32 with Cp = C rounded up to 32, every entry written (0, or NaN, past C); NaN wherever log_probs is NaN and
+ * at every position after a -inf.  emission is ck_hmm_emission_table's table, NULL exactly when cond is.
+ * ck_hmm_emission_table: emission (F, Cp, K) fp32 receives exp(table[f, c, k]) of the Categorical layer's (F, C + 1, K) table of
+ * logarithms for c < C and 0 for C <= c < Cp: linear probabilities, a (fold, category) row contiguous.  Once per parameter state.
+ * The backward pass's ownership (ck_hmm_predict.hip): 32 rows per workgroup on chip for the whole chain, blocks of 32 units per
+ * wave, blocks of 32 categories dealt to the waves.  A row's result does not depend on B, on its place in the batch or on
+ * entries of x at later positions. */
+int ck_hmm_emission_table(const float* table, int F, int K, int C, float* emission, void* stream);
+int ck_hmm_predict(const void* const* w_steps, const int32_t* step_fold, const int32_t* step_var, int T, int K, const float* rows,
+                   const int64_t* x, int D, int C, const int32_t* integrate, int B, float* log_probs, const float* emission,
+                   float* cond, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
