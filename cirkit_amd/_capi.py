@@ -401,6 +401,9 @@ SIGNATURES: dict[str, list[Any]] = {
     "ck_hmm_sample_paths": [_p, _p, _p, _i, _i, _i, _p, _p, _i, _i, _p, _i, _i, _l, C.c_uint64, _p, _p, _p, _p, _p],
     "ck_hmm_emission_table": [_p, _i, _i, _i, _p, _p],
     "ck_hmm_predict": [_p, _p, _p, _i, _i, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p],
+    "ck_hmm_soft_rows": [_p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p],
+    "ck_hmm_soft_flag": [_p, _i, _i, _p, _p],
+    "ck_hmm_soft_leaf": [_p, _i, _i, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _i, _i, _p, _p, _p],
     "ck_em_job_blocks": [_i, _l, _i],
     "ck_em_update": [_p, _p, _i, _f, _f, _p],
     "ck_jobs_cat_bwd": [_p, _i, _p, _i, _i, _p, _p],

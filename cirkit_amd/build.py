@@ -27,7 +27,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # of hipcc does not know the feature and says so, the device pass honours it
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"ck_hmm.hip": _NO_PACKED_FP32, "ck_hmm_viterbi.hip": _NO_PACKED_FP32, "ck_hmm_stats.hip": _NO_PACKED_FP32,
-              "ck_hmm_sample.hip": _NO_PACKED_FP32, "ck_hmm_scan.hip": _NO_PACKED_FP32, "ck_hmm_predict.hip": _NO_PACKED_FP32}
+              "ck_hmm_sample.hip": _NO_PACKED_FP32, "ck_hmm_scan.hip": _NO_PACKED_FP32, "ck_hmm_predict.hip": _NO_PACKED_FP32,
+              "ck_hmm_soft.hip": _NO_PACKED_FP32}
 
 
 def _newer(target: str, deps: list[str]) -> bool:

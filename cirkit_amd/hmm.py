@@ -46,8 +46,16 @@ every row into ``T`` rows of ``T`` layers each.  The conditionals contract the p
 table on the matrix pipe (`ck_hmm_emission_table`, once per parameter state); the coding tables pass them through the
 quantiser `HipCircuit.coding_tables` uses.
 
+`HipHMM.soft_evidence_log_prob`, `soft_state_posteriors`, `soft_posterior_marginals` and `soft_viterbi` take soft (likelihood)
+evidence, a ``(B, S, C)`` block of log weights per soft variable, with `HipCircuit`'s argument conventions: a soft emission is the
+contraction ``log sum_c lambda_c p(c | k)``, so `ck_hmm_soft_rows` writes the ``(F, rows, K)`` block of log emissions of a chunk
+on the matrix pipe (cirkit_amd/csrc/ck_hmm_soft.hip) and the chain kernels above take it as their row source unchanged;
+`ck_hmm_soft_flag` makes the rows with a NaN or ``+inf`` weight NaN and `ck_hmm_soft_leaf` contracts ``gamma / y`` with the same
+emission table into the posteriors of the soft variables -- 3, 4, 5 and 4 launches per chunk.
+
 Out of scope: an M-step of `HipHMM`'s own; expected statistics, sampling and autoregressive conditionals of inputs other than
-Categorical; autoregressive conditionals of a subset of positions, along any order but the generative one, or parallel in
+Categorical; soft evidence in `expected_statistics`, `sample_posterior`, the time-parallel forward and the autoregressive queries,
+on Binomial or Gaussian chains, fused into the chain kernels' step, or with a set of soft variables per row; autoregressive conditionals of a subset of positions, along any order but the generative one, or parallel in
 time; a decoder-side table provider for cirkit_amd/codec.py; k-best
 paths; homogeneous chains (the kernel's table of weight pointers already allows shared transitions; their statistics would be
 summed over the steps); bf16-piece variants; training beyond what `HipTrainer` and `HipEMTrainer` do with a chain plan layer by
@@ -623,6 +631,138 @@ class HipHMM:
                     out[r0:r0 + nb] = wide[:nb, :, :C + 1]
                 self.last_launches += 2
         return out
+
+    def soft_evidence_log_prob(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, integrate_vars=None,
+                               rows_per_chunk: int | None = None) -> torch.Tensor:
+        """``(B,)`` fp32: ``log Z(lambda) = log sum_x p(x) prod_s lambda[b, s, x_{v_s}]`` under soft (likelihood, Pearl's virtual)
+        evidence, with `HipCircuit.soft_evidence_log_prob`'s argument conventions (`soft_evidence.soft_ids` and
+        `check_arguments` on the user plan: the same forms, checks and error types).  `log_lik`: ``(B, S, C')`` floating point,
+        ``C' >= C``, the logarithms of the weights of the soft variables in ascending order of variable id; entries at
+        ``c >= C`` are never read.  `soft_vars`: one set for the batch, ``None`` for every variable.  `x`: ``(B, D)`` int64 hard
+        evidence for the other variables, -1 missing, ``None`` all missing; its entries at soft variables are ignored.
+        `integrate_vars` sums hard variables out as in `log_prob`; naming a soft variable there is a ``ValueError``.  Point
+        evidence, missing entries and a set of allowed values per position are the 0 / 1 special cases of `log_lik`.
+
+        Three launches per chunk of `rows_per_chunk` rows ("Soft evidence on chains"): `ck_hmm_soft_rows`
+        writes the ``(F, rows, K)`` block of log emissions -- a soft one is ``log sum_c lambda_c p(c | k)``, contracted with the
+        cached linear emission table on the matrix pipe -- `ck_hmm_forward` takes it as its row source and `ck_hmm_soft_flag`
+        makes the flagged rows NaN.  The first call after the parameters changed takes one more (`ck_hmm_emission_table`).  By
+        default a chunk keeps the block at or below 1 GiB.  A NaN or ``+inf`` entry read, or a hard category ``>= C``, makes its
+        own row NaN; a soft variable whose entries read are all -inf makes it -inf; no row affects another and a row's value
+        does not depend on `rows_per_chunk`.  `log_lik` is read where it lies (staged only if it is not contiguous fp32), no host
+        synchronisation, nothing written into the parameter store.  Categorical input layers only: any other raises
+        ``NotImplementedError`` naming the layer before anything is allocated or launched."""
+        return self._soft("soft_evidence_log_prob", log_lik, x, soft_vars, integrate_vars, rows_per_chunk)[0]
+
+    def soft_state_posteriors(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, integrate_vars=None,
+                              rows_per_chunk: int | None = None, return_log_evidence: bool = False):
+        """``(B, D, num_states)`` fp32: ``p(z_v = k | lambda, x)``, `state_posteriors` under the evidence of
+        `soft_evidence_log_prob` (same arguments, same row rules: a flagged row or one without mass is NaN in every entry); with
+        `return_log_evidence` also ``log Z``.  Four launches per chunk: the block of emissions, the keeping forward, the flag,
+        `ck_hmm_backward`."""
+        out, post, _, _ = self._soft("soft_state_posteriors", log_lik, x, soft_vars, integrate_vars, rows_per_chunk)
+        post = post[:, :, :self.num_states]
+        return (post, out) if return_log_evidence else post
+
+    def soft_posterior_marginals(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, integrate_vars=None,
+                                 rows_per_chunk: int | None = None, return_log_evidence: bool = False):
+        """``(B, S, C)`` fp32: the posterior of every soft variable, ``[b, s, c] = d log Z / d log_lik[b, s, c] = p(x_{v_s} = c |
+        lambda, x)``, with the meaning and NaN rules of `HipCircuit.soft_posterior_marginals` (not renormalised; a flagged row
+        or one without mass is NaN; 0 where the weight is 0) -- a view of a buffer padded to 32 categories; with
+        `return_log_evidence` also ``log Z``.  Five launches per chunk: the block of emissions, the keeping forward, the flag, the
+        backward pass into a ``(rows, D, K)`` scratch (at or below 1 GiB by default) and `ck_hmm_soft_leaf`, which contracts
+        ``gamma / y`` with the same emission table on the matrix pipe."""
+        out, _, marg, _ = self._soft("soft_posterior_marginals", log_lik, x, soft_vars, integrate_vars, rows_per_chunk)
+        marg = marg[:, :, :self.plan.layers[self.input_layer].config["num_categories"]]
+        return (marg, out) if return_log_evidence else marg
+
+    def soft_viterbi(self, log_lik: torch.Tensor, x: torch.Tensor | None = None, *, soft_vars=None, integrate_vars=None,
+                     rows_per_chunk: int | None = None):
+        """``(states, score)``: ``argmax_z sum_x p(z, x) prod_s lambda_s(x_{v_s})`` and its log value, with `viterbi`'s conventions
+        (``states`` ``(B, D)`` int64 by variable id; a row without a path of positive mass has score -inf, a flagged row NaN, both
+        -1 in every state).  Four launches per chunk: the block of emissions, `ck_hmm_viterbi_forward`, the flag -- before the walk
+        back, which reads the score -- and `ck_hmm_viterbi_backtrack`."""
+        out, _, _, states = self._soft("soft_viterbi", log_lik, x, soft_vars, integrate_vars, rows_per_chunk)
+        return states, out
+
+    def _soft(self, query: str, log_lik, x, soft_vars, integrate_vars, rows_per_chunk: int | None):
+        """``(log Z or score, (B, D, K) state posteriors, (B, S, Cp) soft posteriors, (B, D) states)``, ``None`` where `query` does
+        not ask for it."""
+        from . import soft_evidence as se
+        from .squared import _mask_of
+
+        self._need_categorical(query)
+        if rows_per_chunk is not None and int(rows_per_chunk) <= 0:
+            raise ValueError("rows_per_chunk must be positive")
+        ids = se.soft_ids(self.hc.user_plan, soft_vars)
+        se.check_arguments(self.hc.user_plan, log_lik, x, ids)
+        D, T, K = self.plan.num_variables, len(self.steps), self.K
+        if integrate_vars is not None:
+            both = [v for v in ids if _mask_of(integrate_vars, D)[v]]
+            if both:
+                raise ValueError(f"variables {both[:8]} are soft and in integrate_vars")
+        keep, viterbi, leaf = query != "soft_evidence_log_prob", query == "soft_viterbi", query == "soft_posterior_marginals"
+        whole = query == "soft_state_posteriors"  # (the (B, D, K) buffer is the result: no scratch per chunk)
+        B, S, Cl = (int(n) for n in log_lik.shape)
+        tab = self.tables()
+        C, F = self.plan.layers[self.input_layer].config["num_categories"], int(tab["rows"].shape[0])
+        Cp = -(-C // 32) * 32
+        per_row = 4 * K * max(F, D if keep and not whole else 0)
+        n = min(B, int(rows_per_chunk) if rows_per_chunk is not None else max(1, _CHUNK_BYTES // per_row))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self.last_launches = self._emission_table(tab, stream)
+            sets = tab.setdefault("soft", {})
+            if tuple(ids) not in sets:  # the soft slot of every step, and the step of every soft slot
+                slot_of = {v: j for j, v in enumerate(ids)}
+                step_of = {s.var: t for t, s in enumerate(self.steps)}
+                sets[tuple(ids)] = tuple(torch.tensor(a, dtype=torch.int32).to(self.device) for a in (
+                    [slot_of.get(s.var, -1) for s in self.steps], [step_of.get(v, -1) for v in ids]))
+            step_slot, soft_step = sets[tuple(ids)]
+            mask = self._mask(integrate_vars) if x is not None else None
+            mp = None if mask is None else mask.data_ptr()
+            ll = log_lik.to(self.device).to(torch.float32).contiguous()  # (as it lies where it is contiguous fp32 on the device)
+            ldx = 0
+            if x is not None:
+                x = x.to(self.device).to(torch.int64).contiguous()
+                ldx = int(x.shape[1])
+            new = lambda *shape: (torch.zeros if D != T else torch.empty)(shape, dtype=torch.float32, device=self.device)  # noqa: E731
+            out = torch.empty(B, dtype=torch.float32, device=self.device)
+            block = torch.empty((F, n, K), dtype=torch.float32, device=self.device)
+            m = torch.empty((T, n), dtype=torch.float32, device=self.device)
+            flags = torch.empty((T, n), dtype=torch.int32, device=self.device)
+            post = new(B if whole else n, D, K) if keep else None
+            marg = torch.empty((B, S, Cp), dtype=torch.float32, device=self.device) if leaf else None
+            states = None
+            if viterbi:  # (-1 where no step writes)
+                states = (torch.empty((B, D), dtype=torch.int64, device=self.device) if D == T else
+                          torch.full((B, D), -1, dtype=torch.int64, device=self.device))
+            em = tab["emission"].data_ptr()
+            steps = (tab["fold"].data_ptr(), tab["var"].data_ptr(), T, K)
+            head = (tab["w"].data_ptr(), *steps)
+            for r0 in range(0, B, n):
+                nb = min(n, B - r0)
+                lp, o = ll[r0:].data_ptr(), out[r0:].data_ptr()
+                kp = None if post is None else (post[r0:] if whole else post).data_ptr()
+                capi.call("ck_hmm_soft_rows", lp, S, Cl, step_slot.data_ptr(), *steps, tab["rows"].data_ptr(), em,
+                          None if x is None else x[r0:].data_ptr(), ldx, C, mp, nb, block.data_ptr(), m.data_ptr(), flags.data_ptr(),
+                          stream)
+                source = (block.data_ptr(), None, D, 0, None, nb, o)  # (a block source: its missing entries are in the block)
+                if not keep:
+                    capi.call("ck_hmm_forward", *head, *source, stream)
+                else:
+                    capi.call("ck_hmm_viterbi_forward" if viterbi else "ck_hmm_forward_keep", *head, *source, kp, stream)
+                capi.call("ck_hmm_soft_flag", flags.data_ptr(), T, nb, o, stream)
+                if viterbi:
+                    capi.call("ck_hmm_viterbi_backtrack", tab["w"].data_ptr(), tab["var"].data_ptr(), T, K, self.num_states, D, nb, o,
+                              kp, states[r0:].data_ptr(), stream)
+                elif keep:
+                    capi.call("ck_hmm_backward", *head, *source, kp, stream)
+                if leaf:
+                    capi.call("ck_hmm_soft_leaf", lp, S, Cl, soft_step.data_ptr(), *steps, em, C, block.data_ptr(), m.data_ptr(), kp, D,
+                              nb, o, marg[r0:].data_ptr(), stream)
+                self.last_launches += 3 + keep + leaf
+        return out, (post if whole else None), marg, states
 
     def _chain(self, x: torch.Tensor, integrate_vars, rows_per_chunk: int | None, query: str):
         """``(log_prob, None, None)`` by the forward launch; ``(log_prob, (B, D, K) posteriors, None)`` by the keeping forward

@@ -1939,6 +1939,34 @@ int ck_hmm_predict(const void* const* w_steps, const int32_t* step_fold, const i
                    const int64_t* x, int D, int C, const int32_t* integrate, int B, float* log_probs, const float* emission,
                    float* cond, void* stream);
 
+/* Soft (likelihood) evidence for the same chain ("Soft evidence on chains"; additive, ABI 51): the
+ * (F, n, K) block of log emissions that the chain entries above take as their row source (x == NULL), and the posteriors of the
+ * soft variables.  log_lik is (n, S, Cl) fp32, contiguous, Cl >= C; entries at c >= C are never read.  step_fold / step_var
+ * (T), rows (F, C + 1, K) and emission (F, Cp, K; ck_hmm_emission_table) as above; C <= 1024.
+ * ck_hmm_soft_rows: step_slot (T) int32 is the soft slot s of step t's variable, or -1.  For a soft step, with m the maximum of
+ * log_lik[b, s, :C] clamped finite, block[step_fold[t], b, k] = m + log sum_c exp(log_lik[b, s, c] - m) emission[f, c, k],
+ * contracted on v_mfma_f32_32x32x2_f32 with 2^96 of headroom (terms 150 nats below the largest survive); all entries -inf: the
+ * row is -inf, never NaN.  m[t, b] receives the maximum.  For a hard step the row (f, x[b, step_var[t]]) of rows is copied;
+ * zeros where the entry is negative, integrate[step_var[t]] != 0 or x == NULL (x is (n, ldx) int64; integrate needs x).
+ * flags is (T, n) int32, EVERY word written by the workgroup that owns its (step, row): nonzero where an entry read of log_lik is
+ * NaN or +inf, or a hard category is >= C.  m is (T, n) fp32, written at soft steps only.  A workgroup per (32 rows, step).
+ * ck_hmm_soft_flag: out[b] = NaN where flags[t, b] != 0 for any t; other entries untouched.  Between the forward launch and
+ * whatever reads its (n) result.
+ * ck_hmm_soft_leaf: soft_step (S) int32 is the step that reads soft slot s, or -1 (its posterior is 0).  gamma is (n, D, K), the
+ * state posteriors ck_hmm_backward leaves, by variable; block and m what ck_hmm_soft_rows wrote for the same n; log_z (n) the
+ * flagged forward result.  post (n, S, Cp) fp32, Cp = C rounded up to 32, every entry written:
+ *     post[b, s, c] = exp(log_lik[b, s, c] - m) sum_k gamma[b, v, k] / y[b, k] emission[f, c, k],   y = exp(block[f, b, :] - m)
+ * = d log Z / d log_lik[b, s, c]; 0 for c >= C, for a weight that underflowed and for states with gamma = 0 or y = 0; NaN in
+ * every entry of a row whose log_z is not finite.  A workgroup per (32 rows, soft slot).  No entry uses atomics; no row's
+ * result depends on another row or on n. */
+int ck_hmm_soft_rows(const float* log_lik, int S, int Cl, const int32_t* step_slot, const int32_t* step_fold, const int32_t* step_var,
+                     int T, int K, const float* rows, const float* emission, const int64_t* x, int ldx, int C,
+                     const int32_t* integrate, int n, float* block, float* m, int32_t* flags, void* stream);
+int ck_hmm_soft_flag(const int32_t* flags, int T, int n, float* out, void* stream);
+int ck_hmm_soft_leaf(const float* log_lik, int S, int Cl, const int32_t* soft_step, const int32_t* step_fold, const int32_t* step_var,
+                     int T, int K, const float* emission, int C, const float* block, const float* m, const float* gamma, int D, int n,
+                     const float* log_z, float* post, void* stream);
+
 /* Lend a device scratch buffer to the launches this THREAD issues or records from now on (NULL, 0: take it back).  It
  * must be ZERO when lent; the part that has to stay zero (ticket counters behind the first CUs x 3 x (32 KiB + 512 B)) is zero
  * again after every launch that used it; launches that share it must be ordered (one stream, or one recorded program).  Used
